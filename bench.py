@@ -12,10 +12,22 @@ optimizer iteration: grad_accum x (fwd + bwd) with the bucketed RCCL
 all-reduce overlapped on the last micro-step, global-norm clip, fused AdamW.
 
     python bench.py --gpus 1 --steps 5 --warmup 2
+    python bench.py --gpus 1 --steps 5 --warmup 2 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 \
         --master-addr 127.0.0.1 --master-port 29500 bench.py --gpus 8 --steps 10 --warmup 3
 
 Rank 0 prints exactly one JSON line on stdout (everything else goes to stderr).
+
+A plain run does only what the headline figure needs: set up, warm up, time the
+steps, print the record.  ``--full`` adds the measurements that take runs of
+their own (the 'box' block: DPM clocks around the timed loop and the calibration
+GEMM; with N > 1 the RCCL all-reduce sweep).  ``--dump-outputs DIR`` writes what
+the last timed step returned and left behind (``loss.npy``, ``grad_norm.npy``,
+``params_sample.npy``), so two builds can be compared output for output: the
+seed fixes the initial weights and the synthetic batches.  The default step
+accumulates with fp32 atomics, so two runs agree to rounding (AdamW's first
+steps turn that into weight differences of the order of the learning rate);
+``--deterministic`` fixes the summation order.
 """
 
 from __future__ import annotations
@@ -27,6 +39,7 @@ import os
 import sys
 import time
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -74,6 +87,25 @@ def rccl_summary(report, sweep, reducer=None, exposed=None, early=None) -> dict 
     return out
 
 
+PARAMS_SAMPLE = 1 << 22  # elements of the fp32 master weights kept by --dump-outputs (16 MiB)
+
+
+def dump_outputs(out_dir: str, tr, loss: float, norm) -> None:
+    """--dump-outputs: what the last timed ``train_step`` handed back (the optimizer step's
+    loss and its global gradient norm) and what it left in the flat store (a fixed, seeded
+    sample of the fp32 master weights after the update), one float32 ``.npy`` each."""
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"), np.asarray([loss], dtype=np.float32))
+    if norm is not None:
+        np.save(os.path.join(out_dir, "grad_norm.npy"), norm.detach().float().cpu().numpy().reshape(1))
+    master = tr.store.master
+    n = master.numel()
+    if n > PARAMS_SAMPLE:
+        idx = np.sort(np.random.default_rng(1234).choice(n, size=PARAMS_SAMPLE, replace=False))
+        master = master[torch.from_numpy(idx).to(master.device)]
+    np.save(os.path.join(out_dir, "params_sample.npy"), master.detach().float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -108,11 +140,18 @@ def main():
     ap.add_argument("--real-data", default="",
                     help="dataset name or directory with train.bin/val.bin (nanoGPT bench.py real_data); "
                          "default: synthetic uniform tokens")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the record's 'box' block (DPM clock "
+                         "levels around the timed loop, the calibration GEMM) and, when WORLD_SIZE > 1, the "
+                         "RCCL all-reduce sweep")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write what the last one computed as DIR/<name>.npy (float32): "
+                         "loss, grad_norm and a fixed seeded sample of the updated fp32 master weights")
     ap.add_argument("--rccl-sweep", default="4,16,64,256",
-                    help="all-reduce sizes (MiB) timed once before the timed steps when WORLD_SIZE > 1 "
+                    help="--full: all-reduce sizes (MiB) timed once before the timed steps when WORLD_SIZE > 1 "
                          "(bus bandwidth by bucket size, printed to stderr); '' disables")
     ap.add_argument("--calib-seconds", type=float, default=2.0,
-                    help="box calibration after the timed steps: our NT GEMM on a fixed shape for this many "
+                    help="--full: box calibration after the timed steps: our NT GEMM on a fixed shape for this many "
                          "seconds (TF/s in the record's 'box' block, with the sclk/mclk DPM levels read before "
                          "and after the timed loop); 0 disables")
     ap.add_argument("--per-rank-of", type=int, default=0, metavar="N",
@@ -129,6 +168,8 @@ def main():
                     help="nanoGPT bench.py profile mode: torch.profiler over the timed steps "
                          "(schedule wait 1 / warmup 1 / active rest), TensorBoard trace under ./bench_log")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     emu = args.per_rank_of if args.per_rank_of > 1 else 0
@@ -200,7 +241,7 @@ def main():
         for k, v in gemm_kernels.items():
             print(f"gemm {k}: {v}")
         sweep = []
-        if world > 1 and args.rccl_sweep:
+        if args.full and world > 1 and args.rccl_sweep:
             from nanosandbox_amd.parallel import allreduce_sweep
             sweep = allreduce_sweep(tr.info, [int(v) for v in args.rccl_sweep.split(",") if v])
         multi = dist.is_initialized() and world > 1
@@ -221,13 +262,13 @@ def main():
                            profile_memory=False, with_stack=False)
             prof.start()
         clk_before = None
-        if cuda:
+        if cuda and args.full:
             from nanosandbox_amd.utils.boxcal import read_clocks
             clk_before = read_clocks(torch.device(tr.device).index or 0)
         sync()
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            loss, _, X, Y = tr.train_step(X, Y)
+            loss, norm, X, Y = tr.train_step(X, Y)
             if prof is not None:
                 prof.step()
         sync()
@@ -251,8 +292,10 @@ def main():
         if prof is not None:
             prof.stop()
             print("profiler trace written under ./bench_log (not a clean timing: profiled steps)")
+        if args.dump_outputs and tr.info.rank == 0:
+            dump_outputs(args.dump_outputs, tr, lossf, norm)
         box = None
-        if cuda:
+        if cuda and args.full:
             # outside the timed region: DPM clock levels after the loop, then the calibration GEMM
             # (the same binary and shape on every box: its TF/s tells a slow box from slow code)
             clk_after = read_clocks(torch.device(tr.device).index or 0)

@@ -51,7 +51,7 @@ def test_multirank_record_carries_rccl_block(tmp_path):
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(root, "bench.py"),
                         "--gpus", "2", "--device", "cpu", "--model", "tiny", "--micro-batch", "24",
-                        "--block-size", "32", "--steps", "1", "--warmup", "1", "--rccl-sweep", "1,2"],
+                        "--block-size", "32", "--steps", "1", "--warmup", "1", "--full", "--rccl-sweep", "1,2"],
                        cwd=str(tmp_path), env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -70,6 +70,45 @@ def test_multirank_record_carries_rccl_block(tmp_path):
     assert all(n >= 1 for n in rc["buckets_launched_in_backward"])
     assert "gemm_kernels" in rec  # per GEMM shape the kernel that ran it (empty on the CPU)
     assert "box" in rec and rec["box"] is None  # clocks + calibration GEMM: GPU runs only
+
+
+@pytest.mark.slow
+def test_plain_and_full_runs_dump_the_same_outputs(tmp_path):
+    """A plain run and a --full run of the same arguments (one process, the tiny plumbing
+    model on the CPU) start from the same weights and batches: --dump-outputs writes the
+    last timed step's loss, gradient norm and updated weights, equal between the two runs,
+    and --steps sets the number of timed steps the record's ms_per_step is averaged over."""
+    import json
+    import subprocess
+    import sys
+
+    import numpy as np
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, OMP_NUM_THREADS="4", PYTHONPATH=root)
+    env.pop("WORLD_SIZE", None)
+    outs = {}
+    for mode in ("plain", "full"):
+        d = tmp_path / mode
+        p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--device", "cpu",
+                            "--model", "tiny", "--micro-batch", "480", "--block-size", "4", "--steps", "2",
+                            "--warmup", "1", "--dump-outputs", str(d)] + (["--full"] if mode == "full" else []),
+                           cwd=str(tmp_path), env=env, capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-3000:]
+        lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, p.stdout
+        rec = json.loads(lines[0])
+        assert rec["steps"] == 2 and rec["warmup"] == 1 and rec["ms_per_step"] > 0
+        assert rec["unit"] == "tokens/s" and rec["higher_is_better"] is True
+        assert abs(rec["value"] - rec["config"]["tokens_per_step"] / rec["ms_per_step"] * 1e3) <= 1e-3 * rec["value"]
+        assert rec["box"] is None and rec["rccl"] is None  # one CPU process: nothing for --full to add
+        outs[mode] = {f: np.load(str(d / f)) for f in sorted(os.listdir(str(d)))}
+        assert sorted(outs[mode]) == ["grad_norm.npy", "loss.npy", "params_sample.npy"]
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in outs[mode].values())
+        assert sum(a.nbytes for a in outs[mode].values()) <= 64 << 20
+        assert abs(float(outs[mode]["loss.npy"][0]) - rec["loss"]) < 1e-3
+    for f in outs["plain"]:
+        assert np.array_equal(outs["plain"][f], outs["full"][f]), f
 
 
 def test_read_clocks_parses_dpm_tables(tmp_path, monkeypatch):
