@@ -65,15 +65,15 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
-// grid (B*H, n_split), 256 threads
+// grid (B*H, n_split), 256 threads; pos_dev[b * pos_stride] is row b's position
 // append: also store the new token's K / V rows at position pos (kc_w / vc_w alias
 // kc / vc; separate non-restrict pointers for the one write)
 __global__ __launch_bounds__(256) void decode_attn_partial_kernel(const bf16_t* __restrict__ qkv,
                                                                   const bf16_t* __restrict__ kc,
                                                                   const bf16_t* __restrict__ vc, bf16_t* kc_w,
                                                                   bf16_t* vc_w, const int64_t* __restrict__ pos_dev,
-                                                                  float* __restrict__ ws, int H, int Tmax,
-                                                                  float scale_log2, int append) {
+                                                                  int pos_stride, float* __restrict__ ws, int H,
+                                                                  int Tmax, float scale_log2, int append) {
   __shared__ float qs[DA_D];
   __shared__ float ps[DA_CHUNK];
   __shared__ float red[2][4];
@@ -81,11 +81,13 @@ __global__ __launch_bounds__(256) void decode_attn_partial_kernel(const bf16_t* 
   const int bh = blockIdx.x, s = blockIdx.y, n_split = gridDim.y;
   const int b = bh / H, hh = bh % H;
   const int C = H * DA_D;
-  const int pos = (int)*pos_dev;  // the query's own position = the newest key
+  // the query's own position = the newest key: one for the batch (pos_stride 0) or one per
+  // row (pos_stride 1); b comes from blockIdx, so every branch on it is workgroup-uniform
+  const int pos = (int)pos_dev[(int64_t)b * pos_stride];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   float* part = ws + ((int64_t)bh * n_split + s) * DA_PART;
   const int k0 = s * DA_CHUNK;
-  if (k0 > pos) {  // chunk beyond the live context: empty partial
+  if (k0 > pos || pos >= Tmax) {  // chunk beyond the live context (or no such cache row): empty partial
     if (tid < DA_PART) part[tid] = tid == 0 ? -INFINITY : 0.0f;
     return;
   }
@@ -197,7 +199,9 @@ __global__ __launch_bounds__(64) void decode_attn_combine_kernel(const float* __
 // Otherwise (no top-k, k > 1024, or > 4096 candidates): bisection over all keys with
 // block reductions and a block-wide scan (the single-CU VALU cost of 32 passes over
 // 50k keys made this ~70 us per row; the top-k path is a few us).
-// The chosen id is written to tok[b] and gen[b, *pos].
+// The chosen id is written to tok[b] and gen[b, pos] (pos = *pos, or pos[b] in the
+// per-row form, where a row whose done[b] is set is skipped and a row that draws
+// stop_token sets it).
 // ---------------------------------------------------------------------------
 constexpr int SMP_THREADS = 1024;
 constexpr int SMP_CAP = 4096;  // top-k candidates compacted into LDS
@@ -357,9 +361,9 @@ template <bool VEC4>
 __global__ __launch_bounds__(SMP_THREADS) void sample_topk_kernel(const float* __restrict__ logits, int V, int ld,
                                                                   float scale_log2, int top_k, uint64_t salt,
                                                                   const uint64_t* __restrict__ salt_dev,
-                                                                  const int64_t* __restrict__ pos,
+                                                                  const int64_t* __restrict__ pos, int pos_stride,
                                                                   int64_t* __restrict__ tok, int64_t* __restrict__ gen,
-                                                                  int gen_ld) {
+                                                                  int gen_ld, int stop_token, int64_t* done) {
   __shared__ uint32_t redu[SMP_THREADS / 64];
   __shared__ float scan[SMP_THREADS];
   __shared__ __attribute__((aligned(16))) uint32_t tmx[SMP_THREADS];
@@ -369,6 +373,9 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_topk_kernel(const float* _
   __shared__ uint32_t lo_sh;
   __shared__ uint32_t wtot[SMP_THREADS / 64];
   const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, w = t >> 6;
+  // a finished row draws nothing: tok[b], gen and done[b] stay as they are (block-uniform
+  // exit before the first barrier; done[b] is only ever written by this row's own block)
+  if (done && done[b] != 0) return;
   const float* row = logits + (int64_t)b * ld;
   // element j * 1024 + t stays in registers as an order-preserving key (key 0 = padding,
   // below every real key)
@@ -408,7 +415,7 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_topk_kernel(const float* _
   kmax = block_reduce<uint32_t>(kmax, redu, true);
   SMP_TICK(1);
   const float m = key_val(kmax);
-  const int p = (int)*pos;
+  const int p = (int)pos[(int64_t)b * pos_stride];  // shared (stride 0) or per-row (stride 1) position
   // the device salt (when given) is read at run time, so a captured sampling graph draws a
   // fresh stream whenever the caller rewrites it (one per generate call)
   const uint64_t sl = salt ^ (salt_dev ? *salt_dev : 0ull);
@@ -498,6 +505,7 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_topk_kernel(const float* _
             if (ck[i] >= thr) pick = ci[i];
           tok[b] = pick;
           gen[(int64_t)b * gen_ld + p] = pick;
+          if (done && pick == stop_token) done[b] = 1;  // stop_token < 0: never (pick >= 0)
         }
         SMP_TICK(5);
       }
@@ -545,13 +553,13 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_topk_kernel(const float* _
     int pick = -1, tt = t;
     asm volatile("" : "+v"(tt));
     float acc = before;
-    bool done = false;
+    bool found = false;
 #pragma unroll
     for (int j = 0; j < SMP_MAXC; ++j) {
-      if (!done && key[j] >= thr) {
+      if (!found && key[j] >= thr) {
         acc += exp2f((key_val(key[j]) - m) * scale_log2);
         pick = VEC4 ? 4 * ((j >> 2) * SMP_THREADS + tt) + (j & 3) : j * SMP_THREADS + tt;
-        done = acc > u;
+        found = acc > u;
       }
     }
     if (pick < 0) {  // no kept element in this thread (u >= total on the last one): any kept one
@@ -563,7 +571,15 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_topk_kernel(const float* _
     }
     tok[b] = pick;
     gen[(int64_t)b * gen_ld + p] = pick;
+    if (done && pick == stop_token) done[b] = 1;
   }
+}
+
+// The per-row decode step's position update: an unfinished row moves on by one, a
+// finished row stays where it is (it is fed the same token at the same position again).
+__global__ void pos_advance_kernel(int64_t* __restrict__ pos, const int64_t* __restrict__ done, int B) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b < B && done[b] == 0) pos[b] += 1;
 }
 
 // ---------------------------------------------------------------------------
@@ -968,35 +984,76 @@ NSA_API hipError_t nsa_kv_append(const void* qkv, void* kc, void* vc, const void
 // append != 0: the new token's K / V are taken from qkv and stored at *pos (fused
 // kv_append); otherwise the caches must already hold position *pos.  out == NULL leaves
 // the partials in ws for nsa_gemv_attn.
-NSA_API hipError_t nsa_decode_attn(const void* qkv, void* kc, void* vc, const void* pos, void* ws, void* out, int B,
-                                   int H, int D, int Tmax, float scale, int append, hipStream_t s) {
+static hipError_t decode_attn_launch(const void* qkv, void* kc, void* vc, const void* pos, int pos_stride, void* ws,
+                                     void* out, int B, int H, int D, int Tmax, float scale, int append,
+                                     hipStream_t s) {
   if (D != DA_D || B < 1 || H < 1 || Tmax < 1) return hipErrorInvalidValue;
   const int n_split = (Tmax + DA_CHUNK - 1) / DA_CHUNK;
   decode_attn_partial_kernel<<<dim3(B * H, n_split), 256, 0, s>>>(
       (const bf16_t*)qkv, (const bf16_t*)kc, (const bf16_t*)vc, (bf16_t*)kc, (bf16_t*)vc, (const int64_t*)pos,
-      (float*)ws, H, Tmax, scale * 1.4426950408889634f, append);
+      pos_stride, (float*)ws, H, Tmax, scale * 1.4426950408889634f, append);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess || !out) return e;  // out == NULL: the consumer combines (nsa_gemv_attn)
   decode_attn_combine_kernel<<<B * H, 64, 0, s>>>((const float*)ws, (bf16_t*)out, H, n_split);
   return hipGetLastError();
 }
 
+NSA_API hipError_t nsa_decode_attn(const void* qkv, void* kc, void* vc, const void* pos, void* ws, void* out, int B,
+                                   int H, int D, int Tmax, float scale, int append, hipStream_t s) {
+  return decode_attn_launch(qkv, kc, vc, pos, 0, ws, out, B, H, D, Tmax, scale, append, s);
+}
+
+// The same with one position per row: pos is int64[B], row b attends over keys
+// 0 .. pos[b] and (append) stores its K / V at pos[b].  Same kernels, same partials.
+NSA_API hipError_t nsa_decode_attn_rows(const void* qkv, void* kc, void* vc, const void* pos, void* ws, void* out,
+                                        int B, int H, int D, int Tmax, float scale, int append, hipStream_t s) {
+  return decode_attn_launch(qkv, kc, vc, pos, 1, ws, out, B, H, D, Tmax, scale, append, s);
+}
+
 // Top-k / temperature sampling of logits [B, V] (fp32, row stride ld) on the device:
 // writes tok[b] and gen[b * gen_ld + *pos].  top_k <= 0 keeps every logit.  The uniform is a
 // counter hash of (salt ^ *salt_dev, row, position); salt_dev may be NULL.
-NSA_API hipError_t nsa_sample_topk(const void* logits, int B, int V, int ld, float temperature, int top_k,
-                                   uint64_t salt, const void* salt_dev, const void* pos, void* tok, void* gen,
-                                   int gen_ld, hipStream_t s) {
+static hipError_t sample_topk_launch(const void* logits, int B, int V, int ld, float temperature, int top_k,
+                                     uint64_t salt, const void* salt_dev, const void* pos, int pos_stride, void* tok,
+                                     void* gen, int gen_ld, int stop_token, void* done, hipStream_t s) {
   if (B < 1 || V < 1 || V > SMP_THREADS * SMP_MAXC || !(temperature > 0.0f)) return hipErrorInvalidValue;
   const bool vec4 = V % 4 == 0 && ld % 4 == 0 && ((uintptr_t)logits & 15) == 0;
   if (vec4)
     sample_topk_kernel<true><<<B, SMP_THREADS, 0, s>>>((const float*)logits, V, ld, 1.4426950408889634f / temperature,
                                                        top_k, salt, (const uint64_t*)salt_dev, (const int64_t*)pos,
-                                                       (int64_t*)tok, (int64_t*)gen, gen_ld);
+                                                       pos_stride, (int64_t*)tok, (int64_t*)gen, gen_ld, stop_token,
+                                                       (int64_t*)done);
   else
     sample_topk_kernel<false><<<B, SMP_THREADS, 0, s>>>((const float*)logits, V, ld, 1.4426950408889634f / temperature,
                                                         top_k, salt, (const uint64_t*)salt_dev, (const int64_t*)pos,
-                                                        (int64_t*)tok, (int64_t*)gen, gen_ld);
+                                                        pos_stride, (int64_t*)tok, (int64_t*)gen, gen_ld, stop_token,
+                                                        (int64_t*)done);
+  return hipGetLastError();
+}
+
+NSA_API hipError_t nsa_sample_topk(const void* logits, int B, int V, int ld, float temperature, int top_k,
+                                   uint64_t salt, const void* salt_dev, const void* pos, void* tok, void* gen,
+                                   int gen_ld, hipStream_t s) {
+  return sample_topk_launch(logits, B, V, ld, temperature, top_k, salt, salt_dev, pos, 0, tok, gen, gen_ld, -1,
+                            nullptr, s);
+}
+
+// The per-row form: row b draws at position pos[b * pos_stride] (pos_stride 1: int64[B];
+// 0: one shared position).  done (int64[B], may be NULL): a row with done[b] != 0 is
+// skipped (tok[b], gen and done[b] untouched); a row that draws stop_token (< 0: none)
+// sets done[b] = 1 after writing the id.
+NSA_API hipError_t nsa_sample_topk_rows(const void* logits, int B, int V, int ld, float temperature, int top_k,
+                                        uint64_t salt, const void* salt_dev, const void* pos, int pos_stride,
+                                        void* tok, void* gen, int gen_ld, int stop_token, void* done, hipStream_t s) {
+  if (pos_stride != 0 && pos_stride != 1) return hipErrorInvalidValue;
+  return sample_topk_launch(logits, B, V, ld, temperature, top_k, salt, salt_dev, pos, pos_stride, tok, gen, gen_ld,
+                            stop_token, done, s);
+}
+
+// pos[b] += 1 for every row with done[b] == 0 (int64[B] each): the per-row step's advance.
+NSA_API hipError_t nsa_pos_advance(void* pos, const void* done, int B, hipStream_t s) {
+  if (B < 1 || !pos || !done) return hipErrorInvalidValue;
+  pos_advance_kernel<<<(B + 63) / 64, 64, 0, s>>>((int64_t*)pos, (const int64_t*)done, B);
   return hipGetLastError();
 }
 

@@ -382,3 +382,14 @@ class GPT(nn.Module):
         from ..runtime.decode import generate_cached
         return generate_cached(self, idx, max_new_tokens, temperature=temperature, top_k=top_k, use_graph=use_graph,
                                decoder=decoder)
+
+    @torch.no_grad()
+    def generate_batch(self, prompts, max_new_tokens, temperature=1.0, top_k=None, stop_token=None, use_graph=None,
+                       decoder=None):
+        """``generate_cached`` for a list of 1-D prompts of unequal lengths, decoded as one
+        batch with a position per row; returns a list of 1-D tensors (prompt + new tokens).
+        A row that draws ``stop_token`` ends with it; the others get exactly
+        ``max_new_tokens`` new tokens (``runtime/decode.py``)."""
+        from ..runtime.decode import generate_batch
+        return generate_batch(self, prompts, max_new_tokens, temperature=temperature, top_k=top_k,
+                              stop_token=stop_token, use_graph=use_graph, decoder=decoder)

@@ -907,9 +907,17 @@ def attention(qkv, n_head: int, p: float, training: bool):
 
 def kv_append(qkv, kc, vc, pos=None, pos0: int = 0):
     """Write the K / V rows of ``qkv`` [B, S, 3C] into the caches [B, H, Tmax, D] at
-    positions p0 .. p0+S-1, p0 = ``pos`` (int64 device tensor, graph-safe) or ``pos0``."""
+    positions p0 .. p0+S-1, p0 = ``pos`` (int64 device tensor, graph-safe) or ``pos0``.
+    ``pos`` with one entry per row (B > 1) places every row at its own p0 (eager torch)."""
     B, S, C3 = qkv.shape
     _, H, Tmax, D = kc.shape
+    if pos is not None and pos.numel() > 1:
+        assert pos.numel() == B
+        k, v = qkv.view(B, S, 3, H, D)[:, :, 1:].permute(2, 0, 3, 1, 4)
+        for b, p0 in enumerate(pos.tolist()):
+            kc[b, :, p0:p0 + S] = k[b].to(kc.dtype)
+            vc[b, :, p0:p0 + S] = v[b].to(vc.dtype)
+        return
     if qkv.is_cuda and qkv.dtype == BF16 and D % 8 == 0:
         qkv = qkv.contiguous()
         _lib.call("nsa_kv_append", _lib.ptr(qkv), _lib.ptr(kc), _lib.ptr(vc), _lib.ptr(pos), int(pos0), B, S, H, D,
@@ -932,7 +940,10 @@ class AttnPartials(NamedTuple):
 
 def decode_attention(qkv, kc, vc, pos, n_head: int, append: bool = False, combine: bool = True):
     """Causal attention of the newest token (position ``pos``) over the caches:
-    qkv [B, 1, 3C] -> [B, 1, C].  ``append``: also store the token's K / V at ``pos``
+    qkv [B, 1, 3C] -> [B, 1, C].  ``pos`` is an int64 device tensor with one entry (every
+    row at the same position) or B entries (row b at ``pos[b]``: attends over keys
+    0 .. pos[b]); for equal positions the two forms give bitwise the same result.
+    ``append``: also store the token's K / V at its position
     (the fused form of ``kv_append``).  GPU (head dim 64): split-K flash-decoding
     kernels; otherwise fp32 torch (CPU reference).  ``combine=False`` with one row on the
     GPU returns the partials (``AttnPartials``) for ``decode_linear`` to combine."""
@@ -940,19 +951,28 @@ def decode_attention(qkv, kc, vc, pos, n_head: int, append: bool = False, combin
     C = C3 // 3
     _, H, Tmax, D = kc.shape
     scale = 1.0 / math.sqrt(D)
+    per_row = pos.numel() > 1
+    assert pos.numel() == (B if per_row else 1), "pos holds one position, or one per row"
     if qkv.is_cuda and qkv.dtype == BF16 and D == 64:
         qkv = qkv.contiguous()
         n_split = -(-Tmax // 256)
         ws = torch.empty(B * H * n_split * (4 + D), device=qkv.device, dtype=F32)  # (m, l, pad, o[D]) per chunk
         partial = not combine and B == 1 and GEMV_MAX_ROWS >= 1 and C <= 8192
         out = None if partial else torch.empty(B, 1, C, device=qkv.device, dtype=qkv.dtype)
-        _lib.call("nsa_decode_attn", _lib.ptr(qkv), _lib.ptr(kc), _lib.ptr(vc), _lib.ptr(pos), _lib.ptr(ws),
-                  _lib.ptr(out), B, H, D, Tmax, scale, 1 if append else 0, _lib.stream())
+        _lib.call("nsa_decode_attn_rows" if per_row else "nsa_decode_attn", _lib.ptr(qkv), _lib.ptr(kc), _lib.ptr(vc),
+                  _lib.ptr(pos), _lib.ptr(ws), _lib.ptr(out), B, H, D, Tmax, scale, 1 if append else 0, _lib.stream())
         return AttnPartials(ws, n_split, C) if partial else out
     if append:
         kv_append(qkv, kc, vc, pos)
-    p = int(pos.item())
     q = qkv.view(B, 3, H, D)[:, 0].float()                      # [B, H, D]
+    if per_row:  # every row over its own context (eager by construction: pos is read back)
+        y = torch.empty(B, H, D, dtype=F32, device=qkv.device)
+        for b, p in enumerate(pos.tolist()):
+            k, v = kc[b, :, :p + 1].float(), vc[b, :, :p + 1].float()      # [H, p+1, D]
+            att = torch.softmax(torch.einsum("hd,hkd->hk", q[b], k) * scale, dim=-1)
+            y[b] = torch.einsum("hk,hkd->hd", att, v)
+        return y.reshape(B, 1, C).to(qkv.dtype)
+    p = int(pos.item())
     k = kc[:, :, :p + 1].float()                                 # [B, H, p+1, D]
     v = vc[:, :, :p + 1].float()
     att = torch.softmax(torch.einsum("bhd,bhkd->bhk", q, k) * scale, dim=-1)
@@ -1097,17 +1117,32 @@ def decode_embed_linear_ln(tok, pos, wte, wpe, ln_w, ln_b, w, b=None, dtype=BF16
     return decode_linear_ln(x, None, ln_w, ln_b, w, b, out_dtype=out_dtype)
 
 
-def sample_topk_(logits, temperature: float, top_k, salt: int, pos, tok, gen, salt_dev=None):
+def sample_topk_(logits, temperature: float, top_k, salt: int, pos, tok, gen, salt_dev=None, stop_token=None,
+                 done=None):
     """Device-side nanoGPT sampling (logits / temperature, top-k, softmax, multinomial)
     of logits [B, V] fp32: the drawn ids go to ``tok`` [B, 1] and ``gen[:, pos]``
-    (``pos``: int64 device scalar).  One kernel, graph-capturable; the uniform draw is a
+    (``pos``: int64 device tensor with one entry, or with B entries: row b writes
+    ``gen[b, pos[b]]``).  One kernel, graph-capturable; the uniform draw is a
     counter hash of (salt ^ salt_dev, row, position), so a run is reproducible from its
-    salts.  ``salt_dev`` (int64 device scalar, optional) is read at run time: rewriting it
-    gives a captured sampling graph a fresh stream."""
+    salts and equal positions draw the same ids in both forms.  ``salt_dev`` (int64 device
+    scalar, optional) is read at run time: rewriting it
+    gives a captured sampling graph a fresh stream.  ``done`` (int64 [B], optional): a row
+    with ``done[b] != 0`` is skipped (``tok[b]``, ``gen`` and ``done[b]`` stay as they are); a
+    row that draws ``stop_token`` (None or < 0: no stop token) sets ``done[b]`` to 1."""
     B, V = logits.shape
     k = 0 if top_k is None else min(int(top_k), V)
+    per_row = pos.numel() > 1
+    assert pos.numel() == (B if per_row else 1), "pos holds one position, or one per row"
+    stop = -1 if stop_token is None else int(stop_token)
+    if done is not None:
+        assert done.numel() == B and done.dtype == torch.int64 and done.is_contiguous()
     if logits.is_cuda:
         lg = logits if logits.dtype == F32 and logits.stride(1) == 1 else logits.float().contiguous()
+        if per_row or done is not None:
+            _lib.call("nsa_sample_topk_rows", _lib.ptr(lg), B, V, lg.stride(0), float(temperature), k,
+                      int(salt) & (2 ** 64 - 1), _lib.ptr(salt_dev), _lib.ptr(pos), 1 if per_row else 0, _lib.ptr(tok),
+                      _lib.ptr(gen), gen.stride(0), stop, _lib.ptr(done), _lib.stream())
+            return
         _lib.call("nsa_sample_topk", _lib.ptr(lg), B, V, lg.stride(0), float(temperature), k, int(salt) & (2 ** 64 - 1),
                   _lib.ptr(salt_dev), _lib.ptr(pos), _lib.ptr(tok), _lib.ptr(gen), gen.stride(0), _lib.stream())
         return
@@ -1116,8 +1151,27 @@ def sample_topk_(logits, temperature: float, top_k, salt: int, pos, tok, gen, sa
         v, _ = torch.topk(lg, k)
         lg = lg.masked_fill(lg < v[:, -1:], -float("Inf"))
     nxt = torch.multinomial(torch.softmax(lg, dim=-1), num_samples=1)
-    tok.copy_(nxt.view_as(tok))
-    gen.index_copy_(1, pos, nxt)
+    if not per_row and done is None:
+        tok.copy_(nxt.view_as(tok))
+        gen.index_copy_(1, pos, nxt)
+        return
+    live = torch.ones(B, dtype=torch.bool, device=logits.device) if done is None else done.view(B) == 0
+    tok.copy_(torch.where(live.view_as(tok), nxt.view_as(tok), tok))
+    rows = live.nonzero().view(-1)
+    gen[rows, pos.view(-1).expand(B)[rows]] = nxt.view(B)[rows]
+    if done is not None and stop >= 0:
+        done.view(B)[live & (nxt.view(B) == stop)] = 1
+
+
+def advance_pos_(pos, done):
+    """The per-row decode step's position update: ``pos[b] += 1`` for every row with
+    ``done[b] == 0`` (int64 [B] each); a finished row stays where it is.  One tiny kernel
+    on the GPU (graph-capturable), torch elsewhere."""
+    assert pos.numel() == done.numel() and pos.dtype == done.dtype == torch.int64
+    if pos.is_cuda:
+        _lib.call("nsa_pos_advance", _lib.ptr(pos), _lib.ptr(done), pos.numel(), _lib.stream())
+        return
+    pos.add_((done == 0).to(pos.dtype).view_as(pos))
 
 
 # ----------------------------------------------------------------------------

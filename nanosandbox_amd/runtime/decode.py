@@ -24,6 +24,13 @@ device by one kernel (``ops.sample_topk_``: radix-select threshold, softmax mass
 counter-hash uniform) that writes the id straight into the fed-token buffer and into
 ``gen`` at the device position.  ``run(n)`` captures step + sampling as one graph, so
 n tokens are n replays with no host round trip.
+``Decoder(..., per_row=True)`` keeps one position and one finished flag per sequence
+(``pos`` and ``done``, int64 [B] on the device): prompts of unequal lengths share a
+batch (``prefill(idx, lengths)`` on a right-padded ``idx``), the attention and sampling
+kernels read ``pos[b]``, and a row that draws the stop token is frozen inside the
+captured step: its position stops, it is fed the same token again (rewriting the same
+cache row with the same values) and it draws nothing.  ``generate_batch`` is the
+list-of-prompts front end.
 The caches hold at most ``block_size`` positions; ``GPT.generate_cached`` falls
 back to the recompute loop when prompt + new tokens exceed that (nanoGPT crops the
 context there, which a cache cannot do without re-encoding).
@@ -37,8 +44,10 @@ from .. import ops
 
 
 class Decoder:
-    def __init__(self, model, batch_size: int, max_len: int | None = None, use_graph: bool | None = None):
+    def __init__(self, model, batch_size: int, max_len: int | None = None, use_graph: bool | None = None,
+                 per_row: bool = False):
         self.model = model
+        self.per_row = per_row
         cfg = model.config
         self.B = batch_size
         self.T = max_len or cfg.block_size
@@ -52,7 +61,11 @@ class Decoder:
         shape = (batch_size, self.H, self.T, self.D)
         self.kc = [torch.zeros(shape, device=self.device, dtype=self.dtype) for _ in range(cfg.n_layer)]
         self.vc = [torch.zeros(shape, device=self.device, dtype=self.dtype) for _ in range(cfg.n_layer)]
-        self.pos = torch.zeros(1, device=self.device, dtype=torch.int64)  # position of the token being fed
+        # position of the token being fed: one for the whole batch, or (per_row) one per sequence
+        self.pos = torch.zeros(batch_size if per_row else 1, device=self.device, dtype=torch.int64)
+        # per_row: done[b] != 0 once row b has drawn the stop token; such a row is frozen (it is
+        # fed the same token at the same position in every later step and draws nothing)
+        self.done = torch.zeros(batch_size, device=self.device, dtype=torch.int64) if per_row else None
         self.tok = torch.zeros(batch_size, 1, device=self.device, dtype=torch.int64)
         # generated tokens by position: gen[:, p] is the token fed at position p
         self.gen = torch.zeros(batch_size, self.T + 1, device=self.device, dtype=torch.int64)
@@ -67,7 +80,7 @@ class Decoder:
             # which a captured graph cannot do: run those configs eagerly
             self.use_graph = False
         self.graph = None      # step(): logits only
-        self.sgraphs = {}      # run(): step + sampling + token feedback, per (temperature, top_k)
+        self.sgraphs = {}      # run(): step + sampling + token feedback, per (temperature, top_k[, stop_token])
         self.logits = None
         self.replays = 0
         # compute-dtype weight shadows (``param.compute``, what every op reads): a trained
@@ -146,19 +159,39 @@ class Decoder:
             branch = ops.decode_linear(u, mlp.c_proj.weight, mlp.c_proj.bias)
         lnf = tr.ln_f
         _, logits = ops.decode_linear_ln(x, branch, lnf.weight, lnf.bias, self.model.lm_head.weight, None,
-                                         out_f32=True, out_dtype=lnf.out_dtype, pos_inc=self.pos)
+                                         out_f32=True, out_dtype=lnf.out_dtype,
+                                         pos_inc=None if self.per_row else self.pos)
+        if self.per_row:
+            ops.advance_pos_(self.pos, self.done)  # unfinished rows move on, finished rows stay
         return logits  # pos has advanced (by the head kernel itself on the fused path)
 
     @torch.no_grad()
-    def prefill(self, idx: torch.Tensor) -> torch.Tensor:
-        """Encode the prompt [B, T0]; returns the last position's logits [B, V] (fp32)."""
+    def prefill(self, idx: torch.Tensor, lengths: torch.Tensor | None = None) -> torch.Tensor:
+        """Encode the prompt [B, T0]; returns the last position's logits [B, V] (fp32).
+
+        ``lengths`` (per_row decoders; int64 [B], 1 <= lengths[b] <= T0): ``idx`` is
+        right-padded with any valid token id and row b's prompt is its first ``lengths[b]``
+        tokens.  Causality keeps the padding invisible to the row's own positions, and the
+        K / V rows it leaves at positions >= lengths[b] are overwritten by the step that
+        feeds that position before any step reads them.  Returns the logits of position
+        ``lengths[b] - 1`` of each row and sets ``pos`` to ``lengths``."""
         B, T0 = idx.shape
         assert B == self.B and 1 <= T0 <= self.T
         tr = self.model.transformer
+        if lengths is not None:
+            assert self.per_row, "unequal prompt lengths need Decoder(..., per_row=True)"
+            lengths = torch.as_tensor(lengths, dtype=torch.int64).to(self.device).view(B)
+            assert int(lengths.min()) >= 1 and int(lengths.max()) <= T0
         x = ops.embedding(idx, tr.wte.weight, tr.wpe.weight, 0.0, False, dtype=self.rdtype, cdtype=self.dtype)
         h = self._prefill_layers(x)
-        self.pos.fill_(T0)
-        return ops.lm_head_logits(h[:, [-1], :], self.model.lm_head.weight)[:, 0]
+        if self.per_row:
+            self.done.zero_()
+        if lengths is None:
+            self.pos.fill_(T0)
+            return ops.lm_head_logits(h[:, [-1], :], self.model.lm_head.weight)[:, 0]
+        self.pos.copy_(lengths)
+        last = h[torch.arange(B, device=self.device), lengths - 1].unsqueeze(1)  # [B, 1, C]
+        return ops.lm_head_logits(last, self.model.lm_head.weight)[:, 0]
 
     def _step_impl(self):
         return self._decode_layers()[:, 0]  # also advances pos
@@ -181,12 +214,18 @@ class Decoder:
         # current position without advancing it or changing the fed token: the captured
         # step rewrites the same cache rows when it runs
         tok = self.tok.clone()
+        if self.per_row:  # a warm-up draw may hit the stop token: positions and flags are put back
+            pos, done = self.pos.clone(), self.done.clone()
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
             for _ in range(2):
                 fn()
-                self.pos.sub_(1)
+                if self.per_row:
+                    self.pos.copy_(pos)
+                    self.done.copy_(done)
+                else:
+                    self.pos.sub_(1)
                 self.tok.copy_(tok)
         torch.cuda.current_stream().wait_stream(side)
 
@@ -196,42 +235,68 @@ class Decoder:
         with torch.cuda.graph(self.graph):  # recorded, not executed: pos is unchanged
             self.logits = self._step_impl()
 
-    def sample_into(self, logits, temperature, top_k):
+    def sample_into(self, logits, temperature, top_k, stop_token=None):
         """Draw the next token of every row from ``logits`` [B, V] into ``tok`` and
-        ``gen[:, pos]`` (device kernel on the GPU: ``ops.sample_topk_``)."""
-        ops.sample_topk_(logits, temperature, top_k, self.salt, self.pos, self.tok, self.gen, salt_dev=self.salt_dev)
+        ``gen[:, pos]`` (device kernel on the GPU: ``ops.sample_topk_``).  per_row: row b
+        writes ``gen[b, pos[b]]``; a finished row draws nothing, and a row that draws
+        ``stop_token`` is finished from then on."""
+        if not self.per_row:
+            assert stop_token is None, "a stop token needs Decoder(..., per_row=True)"
+            ops.sample_topk_(logits, temperature, top_k, self.salt, self.pos, self.tok, self.gen,
+                             salt_dev=self.salt_dev)
+            return
+        ops.sample_topk_(logits, temperature, top_k, self.salt, self.pos, self.tok, self.gen, salt_dev=self.salt_dev,
+                         stop_token=stop_token, done=self.done)
 
     def reseed(self):
         """A fresh sampling stream for the next generate call (torch.manual_seed governs)."""
         self.salt_dev.fill_(int(torch.randint(0, 2 ** 62, (1,)).item()))
 
-    def _step_sample_impl(self, temperature, top_k):
-        self.sample_into(self._step_impl(), temperature, top_k)  # pos is now p + 1
+    def _step_sample_impl(self, temperature, top_k, stop_token=None):
+        self.sample_into(self._step_impl(), temperature, top_k, stop_token)  # pos is now p + 1
+
+    DONE_POLL = 16  # run(): replays between two host looks at the finished flags
 
     @torch.no_grad()
-    def run(self, n: int, temperature: float = 1.0, top_k: int | None = None):
+    def run(self, n: int, temperature: float = 1.0, top_k: int | None = None, stop_token: int | None = None):
         """Decode n tokens starting from ``self.tok`` at ``self.pos``: each step feeds the
         token, samples the next one and feeds it back on the device (one graph replay per
-        token on the GPU, no host round trip).  Results land in ``self.gen``."""
+        token on the GPU, no host round trip).  Results land in ``self.gen``.  With a
+        ``stop_token`` (per_row decoders) the finished flags are read back every
+        ``DONE_POLL`` steps and the loop ends early once every row has finished."""
+        if stop_token is not None and stop_token < 0:
+            stop_token = None
+        assert stop_token is None or self.per_row, "a stop token needs Decoder(..., per_row=True)"
         if not self.use_graph:
-            for _ in range(n):
-                self._step_sample_impl(temperature, top_k)
-            return
-        key = (float(temperature), top_k)
-        g = self.sgraphs.get(key)
-        if g is None:
-            self._warmup(lambda: self._step_sample_impl(temperature, top_k))
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                self._step_sample_impl(temperature, top_k)
-            self.sgraphs[key] = g
-        for _ in range(n):
-            g.replay()
-        self.replays += n
+            step = lambda: self._step_sample_impl(temperature, top_k, stop_token)  # noqa: E731
+        else:
+            key = (float(temperature), top_k, stop_token) if self.per_row else (float(temperature), top_k)
+            g = self.sgraphs.get(key)
+            if g is None:
+                self._warmup(lambda: self._step_sample_impl(temperature, top_k, stop_token))
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g):
+                    self._step_sample_impl(temperature, top_k, stop_token)
+                self.sgraphs[key] = g
+            step = g.replay
+        ran = 0
+        while ran < n:
+            if stop_token is not None and ran and ran % self.DONE_POLL == 0 and bool(self.done.all()):
+                break
+            step()
+            ran += 1
+        if self.use_graph:
+            self.replays += ran
 
     @property
     def position(self) -> int:
         return int(self.pos.item())
+
+    @property
+    def positions(self) -> list[int]:
+        """Every row's position (per_row decoders; the shared position repeated otherwise)."""
+        p = self.pos.tolist()
+        return p if self.per_row else p * self.B
 
 
 def sample_next(logits: torch.Tensor, temperature: float = 1.0, top_k: int | None = None,
@@ -270,3 +335,65 @@ def generate_cached(model, idx: torch.Tensor, max_new_tokens: int, temperature: 
     finally:
         if own:
             dec.release()
+
+
+def _cut_at_stop(new: torch.Tensor, stop_token: int | None) -> torch.Tensor:
+    """The new tokens up to and including the first ``stop_token``."""
+    if stop_token is None:
+        return new
+    hit = (new == stop_token).nonzero()
+    return new[:int(hit[0]) + 1] if hit.numel() else new
+
+
+@torch.no_grad()
+def generate_batch(model, prompts, max_new_tokens: int, temperature: float = 1.0, top_k: int | None = None,
+                   stop_token: int | None = None, use_graph: bool | None = None,
+                   decoder: "Decoder | None" = None) -> list[torch.Tensor]:
+    """Generate for a list of prompts of unequal lengths as one batch.
+
+    ``prompts``: 1-D token tensors, each of length >= 1.  Every result is its prompt followed
+    by the new tokens: up to and including the first ``stop_token`` if the row drew it,
+    otherwise exactly ``max_new_tokens`` of them.  The rows share one per_row ``Decoder``
+    (right-padded prefill, then one step per token for the whole batch, every row at its
+    own position; a row that has drawn the stop token is frozen).  A row whose prompt +
+    new tokens exceed block_size cannot live in the cache: it goes through
+    ``generate_cached`` on its own (the recompute loop) and is cut at the stop token.
+
+    ``decoder``: a per_row Decoder of the right batch size to reuse across calls (weight
+    shadows and captured graphs survive); the caller releases it."""
+    if stop_token is not None and stop_token < 0:
+        stop_token = None
+    prompts = [p.view(-1) for p in prompts]
+    assert all(p.numel() >= 1 for p in prompts), "every prompt needs at least one token"
+    if max_new_tokens <= 0:
+        return list(prompts)
+    T = model.config.block_size
+    device = model.lm_head.weight.device
+    outs: list = [None] * len(prompts)
+    rows = [i for i, p in enumerate(prompts) if p.numel() + max_new_tokens - 1 <= T]
+    for i, p in enumerate(prompts):
+        if i not in rows:
+            y = generate_cached(model, p.to(device)[None], max_new_tokens, temperature=temperature, top_k=top_k,
+                                use_graph=use_graph)[0]
+            outs[i] = torch.cat([y[:p.numel()], _cut_at_stop(y[p.numel():], stop_token)])
+    if not rows:
+        return outs
+    B = len(rows)
+    lens = [prompts[i].numel() for i in rows]
+    idx = torch.zeros(B, max(lens), dtype=torch.int64, device=device)  # right-padded (any valid id)
+    for b, i in enumerate(rows):
+        idx[b, :lens[b]] = prompts[i]
+    own = decoder is None or decoder.B != B or not decoder.per_row
+    dec = Decoder(model, B, max_len=T, use_graph=use_graph, per_row=True) if own else decoder
+    try:
+        dec.reseed()
+        logits = dec.prefill(idx, torch.tensor(lens, dtype=torch.int64, device=device))
+        dec.sample_into(logits, temperature, top_k, stop_token)  # gen[b, lens[b]]
+        dec.run(max_new_tokens - 1, temperature, top_k, stop_token)
+        for b, i in enumerate(rows):
+            new = dec.gen[b, lens[b]:lens[b] + max_new_tokens]
+            outs[i] = torch.cat([idx[b, :lens[b]], _cut_at_stop(new, stop_token)])
+    finally:
+        if own:
+            dec.release()
+    return outs

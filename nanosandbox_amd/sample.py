@@ -8,7 +8,10 @@ local HF snapshot (``init_from='gpt2*'``).  Text codec: the dataset's
 tokenizer when available, else raw token ids (``--start="11,42,7"``).
 On MI355X the forward runs the same HIP kernels as training; with ``kv_cache=True``
 (default) each new token runs one position through the model against per-layer
-KV caches, replayed as a HIP graph (``runtime/decode.py``).
+KV caches, replayed as a HIP graph (``runtime/decode.py``).  ``--sample_batch=N`` generates N
+samples of the prompt per decoder run, ``--prompts_file=FILE`` one prompt per line as a
+batch of unequal lengths, ``--stop_token=ID`` ends a sample at that token
+(``GPT.generate_batch``: one position and one finished flag per row on the device).
 """
 
 from __future__ import annotations
@@ -37,7 +40,49 @@ SAMPLE_DEFAULTS = dict(
     compile=False,
     data_dir="",
     kv_cache=True,  # per-layer KV caches + a replayed HIP-graph decode step (runtime/decode.py); False: nanoGPT's recompute loop
+    sample_batch=1,  # samples of the prompt generated per decoder run (num_samples is still the total)
+    prompts_file="",  # one prompt per line, generated as one ragged batch per sample round (start is ignored)
+    stop_token=-1,  # token id that ends a sample (printed text ends before it); -1: none
 )
+
+
+def _generate_batches(model, c, encode, decode, start, device):
+    """sample_batch / prompts_file / stop_token: batches of prompts through
+    ``GPT.generate_batch`` (one per_row decoder per batch size, kept across batches)."""
+    stop = c["stop_token"] if c["stop_token"] >= 0 else None
+    if c["prompts_file"]:
+        with open(c["prompts_file"], "r", encoding="utf-8") as f:
+            texts = [ln.rstrip("\n") for ln in f if ln.strip()]
+        batches = [texts] * c["num_samples"]  # every sample round: all prompts as one ragged batch
+    else:
+        n, sb = c["num_samples"], max(1, c["sample_batch"])
+        batches = [[start] * min(sb, n - i) for i in range(0, n, sb)]
+    decs, outs = {}, []
+    try:
+        for batch in batches:
+            prompts = [torch.tensor(encode(t), dtype=torch.long, device=device) for t in batch]
+            if c["kv_cache"]:
+                from .runtime.decode import Decoder
+                B = len(prompts)
+                if B not in decs:
+                    decs[B] = Decoder(model, B, max_len=model.config.block_size, per_row=True)
+                ys = model.generate_batch(prompts, c["max_new_tokens"], temperature=c["temperature"], top_k=c["top_k"],
+                                          stop_token=stop, decoder=decs[B])
+            else:
+                ys = [model.generate(p[None], c["max_new_tokens"], temperature=c["temperature"], top_k=c["top_k"])[0]
+                      for p in prompts]
+            for p, y in zip(prompts, ys):
+                new = y[p.numel():].tolist()
+                if stop is not None and stop in new:
+                    new = new[:new.index(stop)]
+                text = decode(p.tolist() + new)
+                outs.append(text)
+                print(text)
+                print("---------------")
+    finally:
+        for d in decs.values():
+            d.release()
+    return outs
 
 
 def _codec(checkpoint, data_dir):
@@ -87,6 +132,9 @@ def main(argv=None):
     if start.startswith("FILE:"):
         with open(start[5:], "r", encoding="utf-8") as f:
             start = f.read()
+    if c["sample_batch"] > 1 or c["prompts_file"] or c["stop_token"] >= 0:
+        with torch.no_grad():
+            return _generate_batches(model, c, encode, decode, start, device)
     x = torch.tensor(encode(start), dtype=torch.long, device=device)[None, ...]
     outs = []
     dec = None

@@ -6,6 +6,14 @@ one JSON line per (model, batch, mode) with new tokens/s over the whole batch an
 per-token latency.
 
     python scripts/decode_bench.py [--models gpt2,gpt2-xl] [--batches 1,8,64] [--prompt 128] [--new 256]
+
+Per-row positions (``Decoder(per_row=True)``): mode ``rows`` is the graph mode with one
+position per sequence at equal prompt lengths (what the per-row step costs beside
+``graph``); ``--ragged`` adds mode ``ragged``, the same with unequal prompt lengths
+(--prompt/2 .. --prompt spread evenly over the batch, no stop token).  ``--repeat N`` runs
+the whole mode list N times, interleaved, for the run-to-run spread.  ``--samples N``
+times sample.py's flow for N samples of one prompt: a reused batch-1 decoder N times over
+(``sample_loop``) against one ``generate_batch`` of N rows (``sample_batch``).
 """
 
 import argparse
@@ -42,6 +50,46 @@ def run_cached(model, idx, new, use_graph):
     return dt
 
 
+def ragged_lengths(B, prompt):
+    """--prompt/2 .. --prompt, spread evenly over the batch."""
+    lo = max(1, prompt // 2)
+    return [prompt if B == 1 else lo + (prompt - lo) * b // (B - 1) for b in range(B)]
+
+
+def run_rows(model, idx, new, lengths=None):
+    """The graph mode on a per_row decoder: equal lengths, or (lengths) a ragged batch."""
+    B = idx.shape[0]
+    dec = Decoder(model, B, use_graph=True, per_row=True)
+    lens = None if lengths is None else torch.tensor(lengths, device=idx.device)
+    dec.sample_into(dec.prefill(idx, lens), 0.8, 200)
+    dec.run(1, 0.8, 200)  # capture outside the timed loop
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    dec.run(new, 0.8, 200)
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    dec.release()
+    return dt
+
+
+def run_samples(model, prompt, n, new, batched):
+    """sample.py's flow for n samples of one prompt, decoder construction and capture
+    included: one batch-1 decoder reused n times, or one generate_batch of n rows."""
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    if batched:
+        dec = Decoder(model, n, max_len=model.config.block_size, per_row=True)
+        model.generate_batch([prompt] * n, new, temperature=0.8, top_k=200, decoder=dec)
+    else:
+        dec = Decoder(model, 1, max_len=model.config.block_size)
+        for _ in range(n):
+            model.generate_cached(prompt[None], new, temperature=0.8, top_k=200, decoder=dec)
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    dec.release()
+    return dt
+
+
 def run_recompute(model, idx, new):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -57,8 +105,17 @@ def main():
     ap.add_argument("--prompt", type=int, default=128)
     ap.add_argument("--new", type=int, default=256)
     ap.add_argument("--recompute-new", type=int, default=32, help="tokens timed for the recompute loop (slow)")
-    ap.add_argument("--modes", default="recompute,cached,graph")
+    ap.add_argument("--modes", default="recompute,cached,graph", help="of recompute, cached, graph, rows")
+    ap.add_argument("--ragged", action="store_true", help="add mode 'ragged': unequal prompt lengths, per-row graph")
+    ap.add_argument("--repeat", type=int, default=1, help="run the mode list this many times (interleaved)")
+    ap.add_argument("--samples", type=int, default=0, help="also time N samples of one prompt: loop vs one batch")
+    ap.add_argument("--calibrate", action="store_true", help="first print the box calibration GEMM (utils/boxcal.py)")
     a = ap.parse_args()
+    if a.calibrate:
+        from nanosandbox_amd.utils.boxcal import calibration_gemm
+        print(json.dumps({"calibration_gemm": calibration_gemm()}), flush=True)
+    modes = a.modes.split(",") + (["ragged"] if a.ragged else [])
+    modes = [m for m in modes if m] * a.repeat
     for name in a.models.split(","):
         L, H, C = DIMS[name]
         torch.manual_seed(0)
@@ -67,8 +124,13 @@ def main():
         for B in [int(b) for b in a.batches.split(",")]:
             idx = torch.randint(0, 50257, (B, a.prompt), device="cuda")
             with torch.no_grad():
-                for mode in a.modes.split(","):
-                    if mode == "recompute":
+                for mode in modes:
+                    if mode in ("rows", "ragged"):
+                        n = a.new
+                        lens = ragged_lengths(B, a.prompt) if mode == "ragged" else None
+                        run_rows(model, idx, 4, lens)
+                        dt = run_rows(model, idx, n, lens)
+                    elif mode == "recompute":
                         run_recompute(model, idx, 2)  # warm-up (tuner, allocator)
                         n = a.recompute_new
                         dt = run_recompute(model, idx, n)
@@ -78,6 +140,16 @@ def main():
                         dt = run_cached(model, idx, n, mode == "graph")
                     print(json.dumps({"model": name, "batch": B, "mode": mode, "prompt": a.prompt, "new_tokens": n,
                                       "tokens_per_s": round(B * n / dt, 1), "ms_per_token": round(dt / n * 1e3, 3)}),
+                          flush=True)
+        if a.samples:
+            prompt = torch.randint(0, 50257, (a.prompt,), device="cuda")
+            with torch.no_grad():
+                for batched in [False, True] * a.repeat:
+                    run_samples(model, prompt, a.samples, 4, batched)  # warm-up (tuner, allocator)
+                    dt = run_samples(model, prompt, a.samples, a.new, batched)
+                    print(json.dumps({"model": name, "samples": a.samples, "new_tokens": a.new, "prompt": a.prompt,
+                                      "mode": "sample_batch" if batched else "sample_loop",
+                                      "tokens_per_s": round(a.samples * a.new / dt, 1), "seconds": round(dt, 3)}),
                           flush=True)
         del model
         torch.cuda.empty_cache()
