@@ -70,6 +70,16 @@ __device__ __forceinline__ void st8(bf16_t* p, const float (&f)[8]) {
   }
 }
 
+// Scalar tails: f32 product -> element.  hipcc folds (_Float16)(a * b) into
+// v_fma_mixlo_f16 a, b, 0, and that +0 addend turns a -0 product into +0; the vector bodies
+// convert pairs and keep the sign.  The empty asm keeps the product a value of its own, so
+// body and tail give the same bits.
+template <bool H>
+__device__ __forceinline__ uint16_t f2e_prod(float f) {
+  if constexpr (H) asm("" : "+v"(f));
+  return f2e<H>(f);
+}
+
 // H (every kernel below): the 16-bit tensors are fp16 instead of bf16
 template <bool NT = false, bool H = false>
 __global__ __launch_bounds__(kBlock) void gelu_fwd_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict__ y,
@@ -97,7 +107,7 @@ __global__ __launch_bounds__(kBlock) void gelu_fwd_kernel(const bf16_t* __restri
   }
   // scalar tail
   for (int64_t i = nv * 8 + (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock)
-    y[i] = f2e<H>(gelu_f(e2f<H>(x[i])));
+    y[i] = f2e_prod<H>(gelu_f(e2f<H>(x[i])));
 }
 
 template <bool NT = false, bool H = false>
@@ -127,7 +137,7 @@ __global__ __launch_bounds__(kBlock) void gelu_bwd_kernel(const bf16_t* __restri
     }
   }
   for (int64_t i = nv * 8 + (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock)
-    dx[i] = f2e<H>(e2f<H>(dy[i]) * gelu_grad(e2f<H>(x[i])));
+    dx[i] = f2e_prod<H>(e2f<H>(dy[i]) * gelu_grad(e2f<H>(x[i])));
 }
 
 template <bool H = false>
@@ -143,7 +153,7 @@ __global__ __launch_bounds__(kBlock) void dropout_kernel(const bf16_t* __restric
     store8e<H>(y + i * 8, f);
   }
   for (int64_t i = nv * 8 + (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock)
-    y[i] = f2e<H>(nsa_keep(seed, (uint64_t)i, thresh) ? e2f<H>(x[i]) * scale : 0.0f);
+    y[i] = f2e_prod<H>(nsa_keep(seed, (uint64_t)i, thresh) ? e2f<H>(x[i]) * scale : 0.0f);
 }
 
 template <bool H = false>
@@ -198,7 +208,9 @@ __global__ __launch_bounds__(256) void transpose_bf16_kernel(const bf16_t* __res
 // reduction of split-K weight-gradient partials (deterministic mode)
 __global__ __launch_bounds__(kBlock) void splitk_reduce_kernel(const float* __restrict__ ws, float* __restrict__ out,
                                                               int64_t n, int splits) {
-  const int64_t nv = n / 4;
+  // split s starts at ws + s * n: 16-byte aligned for every s only when n is a multiple of 4
+  // (every weight gradient is); any other n takes the scalar loop throughout
+  const int64_t nv = (n % 4 == 0 || splits == 1) ? n / 4 : 0;
   for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < nv; i += (int64_t)gridDim.x * kBlock) {
     float4 acc = reinterpret_cast<const float4*>(ws)[i];
     for (int sp = 1; sp < splits; ++sp) {
@@ -236,7 +248,7 @@ __global__ __launch_bounds__(kBlock) void scale_bf16_kernel(const bf16_t* __rest
     store8e<H>(y + i * 8, f);
   }
   for (int64_t i = nv * 8 + (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock)
-    y[i] = f2e<H>(e2f<H>(x[i]) * sc);
+    y[i] = f2e_prod<H>(e2f<H>(x[i]) * sc);
 }
 
 }  // namespace

@@ -80,3 +80,47 @@ def test_large_finite_scaled_gradients_are_not_skipped(kernels):
     opt.step()
     assert ls.found_inf and ls.skipped == 1 and ls.scale == 2.0 ** 15 and ls.good_steps == 1
     assert torch.equal(store.master, w1)
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
+def test_flat_store_padding_stays_zero(kernels, dtype):
+    """A vocabulary of 100 pads the tied wte / lm_head weight to 256 rows, and an embedding
+    width of 40 leaves a gap behind every vector (40, 120, 160 elements in 64-element
+    granules).  Three clipped steps with weight decay and random gradients on the real
+    elements: the row padding and every gap stay exactly zero in the master weights, the
+    compute shadow and both moments, every real element moves, and the shadow is the
+    rounded master weight."""
+    from nanosandbox_amd.models import GPT, GPTConfig
+    from nanosandbox_amd.optim import FlatParamStore
+
+    torch.manual_seed(1)
+    m = GPT(GPTConfig(n_layer=1, n_head=2, n_embd=40, block_size=24, vocab_size=100, bias=True))
+    store = FlatParamStore(m, "cuda", compute_dtype=dtype)
+    opt = m.configure_optimizers(0.1, 1e-2, (0.9, 0.95), "cuda", store=store)
+    real = torch.zeros(store.numel, dtype=torch.bool, device="cuda")
+    for s in store.slots:
+        assert s.offset % 64 == 0 and s.padded % 64 == 0
+        real[s.offset:s.offset + s.numel] = True
+    wte = store.slot_of(m.lm_head.weight)
+    assert wte.numel == 100 * 40 and wte.padded == 256 * 40  # the row padding
+    assert sum(1 for s in store.slots if s.numel < s.padded) > 5  # and the gaps behind the vectors
+    assert store.numel == sum(s.padded for s in store.slots) and (~real).sum().item() > 156 * 40
+    w0 = store.master.clone()
+    bufs = (store.master, store.compute, opt.exp_avg, opt.exp_avg_sq)
+    for b in bufs:
+        assert not b[~real].any()
+    for it in range(3):
+        store.grad.zero_()
+        for s in store.slots:
+            store.param_view(store.grad, s).copy_(torch.randn(s.param.shape, device="cuda") * (it + 1))
+        assert not store.grad[~real].any()
+        norm = opt.clip_grad_norm_(1.0)
+        opt.step()
+        assert norm.item() > 1.0  # clipping is active
+    torch.cuda.synchronize()
+    for b in bufs:
+        assert torch.isfinite(b).all()
+        assert not b[~real].any()
+    assert (store.master[real] != w0[real]).all()
+    assert (opt.exp_avg[real] != 0).all() and (opt.exp_avg_sq[real] > 0).all()
+    assert torch.equal(store.compute.view(torch.int16), store.master.to(dtype).view(torch.int16))
