@@ -357,39 +357,44 @@ class GPT(nn.Module):
         return flops_achieved / peak_flops
 
     @torch.no_grad()
-    def generate(self, idx, max_new_tokens, temperature=1.0, top_k=None):
+    def generate(self, idx, max_new_tokens, temperature=1.0, top_k=None, top_p=None, min_p=None):
         """Autoregressive sampling: crop context, last-token logits / temperature,
-        optional top-k, softmax, multinomial, append."""
+        optional top-k (None or 0: off), nucleus ``top_p`` and ``min_p``
+        (``ops.filter_logits``), softmax, multinomial, append."""
+        ops.check_sampling_filters(top_p, min_p)
         for _ in range(max_new_tokens):
             # if the sequence context is growing too long we must crop it at block_size
             idx_cond = idx if idx.size(1) <= self.config.block_size else idx[:, -self.config.block_size:]
             logits, _ = self(idx_cond)
             logits = logits[:, -1, :] / temperature
-            if top_k is not None:
+            if top_k:
                 v, _ = torch.topk(logits, min(top_k, logits.size(-1)))
                 logits[logits < v[:, [-1]]] = -float("Inf")
+            if (top_p is not None and top_p < 1.0) or (min_p is not None and min_p > 0.0):
+                logits = ops.filter_logits(logits.float(), None, top_p, min_p)
             probs = torch.softmax(logits, dim=-1)
             idx_next = torch.multinomial(probs, num_samples=1)
             idx = torch.cat((idx, idx_next), dim=1)
         return idx
 
     @torch.no_grad()
-    def generate_cached(self, idx, max_new_tokens, temperature=1.0, top_k=None, use_graph=None, decoder=None):
+    def generate_cached(self, idx, max_new_tokens, temperature=1.0, top_k=None, use_graph=None, decoder=None,
+                        top_p=None, min_p=None):
         """``generate`` with per-layer KV caches: the prompt is encoded once and every
         new token runs one position through the model (a replayed HIP graph on the GPU;
         ``runtime/decode.py``).  Same sampling; falls back to ``generate`` when prompt +
         new tokens exceed block_size."""
         from ..runtime.decode import generate_cached
         return generate_cached(self, idx, max_new_tokens, temperature=temperature, top_k=top_k, use_graph=use_graph,
-                               decoder=decoder)
+                               decoder=decoder, top_p=top_p, min_p=min_p)
 
     @torch.no_grad()
     def generate_batch(self, prompts, max_new_tokens, temperature=1.0, top_k=None, stop_token=None, use_graph=None,
-                       decoder=None):
+                       decoder=None, top_p=None, min_p=None):
         """``generate_cached`` for a list of 1-D prompts of unequal lengths, decoded as one
         batch with a position per row; returns a list of 1-D tensors (prompt + new tokens).
         A row that draws ``stop_token`` ends with it; the others get exactly
         ``max_new_tokens`` new tokens (``runtime/decode.py``)."""
         from ..runtime.decode import generate_batch
         return generate_batch(self, prompts, max_new_tokens, temperature=temperature, top_k=top_k,
-                              stop_token=stop_token, use_graph=use_graph, decoder=decoder)
+                              stop_token=stop_token, use_graph=use_graph, decoder=decoder, top_p=top_p, min_p=min_p)

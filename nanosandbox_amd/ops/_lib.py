@@ -80,6 +80,8 @@ _SIGNATURES = {
                              c_float, c_int, c_void_p],
     "nsa_sample_topk_rows": [c_void_p, c_int, c_int, c_int, c_float, c_int, c_uint64, c_void_p, c_void_p, c_int,
                              c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p],
+    "nsa_sample_filtered": [c_void_p, c_int, c_int, c_int, c_float, c_int, c_float, c_float, c_uint64, c_void_p,
+                            c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p],
     "nsa_pos_advance": [c_void_p, c_void_p, c_int, c_void_p],
     "nsa_gemv":[c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p],
     "nsa_skinny_gemm": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p],

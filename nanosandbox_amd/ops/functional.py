@@ -1117,8 +1117,46 @@ def decode_embed_linear_ln(tok, pos, wte, wpe, ln_w, ln_b, w, b=None, dtype=BF16
     return decode_linear_ln(x, None, ln_w, ln_b, w, b, out_dtype=out_dtype)
 
 
+def check_sampling_filters(top_p=None, min_p=None):
+    """Validate nucleus / min-p settings: ``top_p`` in (0, 1] and ``min_p`` in [0, 1), or None."""
+    if top_p is not None and not 0.0 < float(top_p) <= 1.0:
+        raise ValueError(f"top_p must be in (0, 1], got {top_p}")
+    if min_p is not None and not 0.0 <= float(min_p) < 1.0:
+        raise ValueError(f"min_p must be in [0, 1), got {min_p}")
+
+
+def filter_logits(z, top_k=None, top_p=None, min_p=None):
+    """The sampling filters on scaled logits ``z`` [B, V] (fp32), in torch: everything
+    outside the kept set becomes -inf.  top-k keeps ``z >=`` the k-th largest (ties kept);
+    with w = exp(z - max z) over that set and Z = sum w, ``top_p`` keeps a token iff the
+    mass of the strictly larger ones is ``< top_p * Z`` (the smallest descending prefix that
+    reaches top_p, ties at its edge kept) and ``min_p`` keeps it iff ``w >= min_p``.
+    None, ``top_k`` 0, ``top_p`` >= 1 and ``min_p`` 0 switch a filter off."""
+    V = z.size(-1)
+    if top_k is not None and 0 < int(top_k) < V:
+        v, _ = torch.topk(z, int(top_k))
+        z = z.masked_fill(z < v[:, -1:], -float("Inf"))
+    nucleus = top_p is not None and float(top_p) < 1.0
+    floor = min_p is not None and float(min_p) > 0.0
+    if not (nucleus or floor):
+        return z
+    w = torch.exp(z - z.max(dim=-1, keepdim=True).values)
+    keep = torch.ones_like(z, dtype=torch.bool)
+    if nucleus:
+        ws, order = torch.sort(w, dim=-1, descending=True)
+        cum = torch.cumsum(ws, dim=-1)
+        # mass of the strictly larger weights: the running sum before the first entry of a tie group
+        first = torch.ones_like(ws, dtype=torch.bool)
+        first[:, 1:] = ws[:, 1:] != ws[:, :-1]
+        s_gt = torch.cummax(torch.where(first, cum - ws, torch.zeros_like(ws)), dim=-1).values
+        keep = torch.zeros_like(keep).scatter(-1, order, s_gt < float(top_p) * cum[:, -1:])
+    if floor:
+        keep &= w >= float(min_p)
+    return z.masked_fill(~keep, -float("Inf"))
+
+
 def sample_topk_(logits, temperature: float, top_k, salt: int, pos, tok, gen, salt_dev=None, stop_token=None,
-                 done=None):
+                 done=None, top_p=None, min_p=None, stats=None):
     """Device-side nanoGPT sampling (logits / temperature, top-k, softmax, multinomial)
     of logits [B, V] fp32: the drawn ids go to ``tok`` [B, 1] and ``gen[:, pos]``
     (``pos``: int64 device tensor with one entry, or with B entries: row b writes
@@ -1128,8 +1166,18 @@ def sample_topk_(logits, temperature: float, top_k, salt: int, pos, tok, gen, sa
     scalar, optional) is read at run time: rewriting it
     gives a captured sampling graph a fresh stream.  ``done`` (int64 [B], optional): a row
     with ``done[b] != 0`` is skipped (``tok[b]``, ``gen`` and ``done[b]`` stay as they are); a
-    row that draws ``stop_token`` (None or < 0: no stop token) sets ``done[b]`` to 1."""
+    row that draws ``stop_token`` (None or < 0: no stop token) sets ``done[b]`` to 1.
+
+    ``top_p`` in (0, 1] (nucleus) and ``min_p`` in [0, 1) narrow the kept set further
+    (``filter_logits`` states the rule; ``top_k`` 0 or None keeps every id).  ``stats``
+    (int32 [B, 2], optional) receives every drawing row's kept count and the bits of its
+    smallest kept logit.  With all three left at None the call is the top-k sampler's,
+    launch for launch."""
     B, V = logits.shape
+    check_sampling_filters(top_p, min_p)
+    filtered = top_p is not None or min_p is not None or stats is not None
+    if stats is not None:
+        assert stats.shape == (B, 2) and stats.dtype == torch.int32 and stats.is_contiguous()
     k = 0 if top_k is None else min(int(top_k), V)
     per_row = pos.numel() > 1
     assert pos.numel() == (B if per_row else 1), "pos holds one position, or one per row"
@@ -1138,6 +1186,12 @@ def sample_topk_(logits, temperature: float, top_k, salt: int, pos, tok, gen, sa
         assert done.numel() == B and done.dtype == torch.int64 and done.is_contiguous()
     if logits.is_cuda:
         lg = logits if logits.dtype == F32 and logits.stride(1) == 1 else logits.float().contiguous()
+        if filtered:
+            _lib.call("nsa_sample_filtered", _lib.ptr(lg), B, V, lg.stride(0), float(temperature), k,
+                      1.0 if top_p is None else float(top_p), 0.0 if min_p is None else float(min_p),
+                      int(salt) & (2 ** 64 - 1), _lib.ptr(salt_dev), _lib.ptr(pos), 1 if per_row else 0, _lib.ptr(tok),
+                      _lib.ptr(gen), gen.stride(0), stop, _lib.ptr(done), _lib.ptr(stats), _lib.stream())
+            return
         if per_row or done is not None:
             _lib.call("nsa_sample_topk_rows", _lib.ptr(lg), B, V, lg.stride(0), float(temperature), k,
                       int(salt) & (2 ** 64 - 1), _lib.ptr(salt_dev), _lib.ptr(pos), 1 if per_row else 0, _lib.ptr(tok),
@@ -1146,11 +1200,13 @@ def sample_topk_(logits, temperature: float, top_k, salt: int, pos, tok, gen, sa
         _lib.call("nsa_sample_topk", _lib.ptr(lg), B, V, lg.stride(0), float(temperature), k, int(salt) & (2 ** 64 - 1),
                   _lib.ptr(salt_dev), _lib.ptr(pos), _lib.ptr(tok), _lib.ptr(gen), gen.stride(0), _lib.stream())
         return
-    lg = logits.float() / temperature
-    if k > 0:
-        v, _ = torch.topk(lg, k)
-        lg = lg.masked_fill(lg < v[:, -1:], -float("Inf"))
+    lg = filter_logits(logits.float() / temperature, k, top_p, min_p)
     nxt = torch.multinomial(torch.softmax(lg, dim=-1), num_samples=1)
+    if stats is not None:
+        kept = lg > -float("Inf")
+        low = logits.float().masked_fill(~kept, float("Inf")).min(dim=-1).values
+        rows = torch.ones(B, dtype=torch.bool, device=logits.device) if done is None else done.view(B) == 0
+        stats[rows] = torch.stack([kept.sum(-1).to(torch.int32), low.view(torch.int32)], dim=1)[rows]
     if not per_row and done is None:
         tok.copy_(nxt.view_as(tok))
         gen.index_copy_(1, pos, nxt)

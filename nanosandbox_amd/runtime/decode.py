@@ -23,7 +23,9 @@ Sampling (temperature, top-k, multinomial) is nanoGPT's distribution, drawn on t
 device by one kernel (``ops.sample_topk_``: radix-select threshold, softmax mass, scan,
 counter-hash uniform) that writes the id straight into the fed-token buffer and into
 ``gen`` at the device position.  ``run(n)`` captures step + sampling as one graph, so
-n tokens are n replays with no host round trip.
+n tokens are n replays with no host round trip.  ``top_p`` (nucleus) and ``min_p``
+narrow the kept set inside the same kernel launch (``ops.filter_logits`` states the
+rule); a captured graph is keyed by them only when one of them is on.
 ``Decoder(..., per_row=True)`` keeps one position and one finished flag per sequence
 (``pos`` and ``done``, int64 [B] on the device): prompts of unequal lengths share a
 batch (``prefill(idx, lengths)`` on a right-padded ``idx``), the attention and sampling
@@ -235,30 +237,33 @@ class Decoder:
         with torch.cuda.graph(self.graph):  # recorded, not executed: pos is unchanged
             self.logits = self._step_impl()
 
-    def sample_into(self, logits, temperature, top_k, stop_token=None):
+    def sample_into(self, logits, temperature, top_k, stop_token=None, top_p=None, min_p=None):
         """Draw the next token of every row from ``logits`` [B, V] into ``tok`` and
         ``gen[:, pos]`` (device kernel on the GPU: ``ops.sample_topk_``).  per_row: row b
         writes ``gen[b, pos[b]]``; a finished row draws nothing, and a row that draws
-        ``stop_token`` is finished from then on."""
+        ``stop_token`` is finished from then on.  ``top_p`` / ``min_p``: nucleus and min-p
+        filters on top of the top-k (off: the top-k sampler's own launch)."""
+        top_p, min_p = sampling_filters(top_p, min_p)
         if not self.per_row:
             assert stop_token is None, "a stop token needs Decoder(..., per_row=True)"
             ops.sample_topk_(logits, temperature, top_k, self.salt, self.pos, self.tok, self.gen,
-                             salt_dev=self.salt_dev)
+                             salt_dev=self.salt_dev, top_p=top_p, min_p=min_p)
             return
         ops.sample_topk_(logits, temperature, top_k, self.salt, self.pos, self.tok, self.gen, salt_dev=self.salt_dev,
-                         stop_token=stop_token, done=self.done)
+                         stop_token=stop_token, done=self.done, top_p=top_p, min_p=min_p)
 
     def reseed(self):
         """A fresh sampling stream for the next generate call (torch.manual_seed governs)."""
         self.salt_dev.fill_(int(torch.randint(0, 2 ** 62, (1,)).item()))
 
-    def _step_sample_impl(self, temperature, top_k, stop_token=None):
-        self.sample_into(self._step_impl(), temperature, top_k, stop_token)  # pos is now p + 1
+    def _step_sample_impl(self, temperature, top_k, stop_token=None, top_p=None, min_p=None):
+        self.sample_into(self._step_impl(), temperature, top_k, stop_token, top_p, min_p)  # pos is now p + 1
 
     DONE_POLL = 16  # run(): replays between two host looks at the finished flags
 
     @torch.no_grad()
-    def run(self, n: int, temperature: float = 1.0, top_k: int | None = None, stop_token: int | None = None):
+    def run(self, n: int, temperature: float = 1.0, top_k: int | None = None, stop_token: int | None = None,
+            top_p: float | None = None, min_p: float | None = None):
         """Decode n tokens starting from ``self.tok`` at ``self.pos``: each step feeds the
         token, samples the next one and feeds it back on the device (one graph replay per
         token on the GPU, no host round trip).  Results land in ``self.gen``.  With a
@@ -267,16 +272,19 @@ class Decoder:
         if stop_token is not None and stop_token < 0:
             stop_token = None
         assert stop_token is None or self.per_row, "a stop token needs Decoder(..., per_row=True)"
+        top_p, min_p = sampling_filters(top_p, min_p)
         if not self.use_graph:
-            step = lambda: self._step_sample_impl(temperature, top_k, stop_token)  # noqa: E731
+            step = lambda: self._step_sample_impl(temperature, top_k, stop_token, top_p, min_p)  # noqa: E731
         else:
             key = (float(temperature), top_k, stop_token) if self.per_row else (float(temperature), top_k)
+            if top_p is not None or min_p is not None:  # without them: the keys (and graphs) of the top-k sampler
+                key += (top_p, min_p)
             g = self.sgraphs.get(key)
             if g is None:
-                self._warmup(lambda: self._step_sample_impl(temperature, top_k, stop_token))
+                self._warmup(lambda: self._step_sample_impl(temperature, top_k, stop_token, top_p, min_p))
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g):
-                    self._step_sample_impl(temperature, top_k, stop_token)
+                    self._step_sample_impl(temperature, top_k, stop_token, top_p, min_p)
                 self.sgraphs[key] = g
             step = g.replay
         ran = 0
@@ -299,13 +307,25 @@ class Decoder:
         return p if self.per_row else p * self.B
 
 
+def sampling_filters(top_p=None, min_p=None):
+    """Validated (top_p, min_p) with a filter that is off (``top_p`` >= 1, ``min_p`` 0) as None."""
+    ops.check_sampling_filters(top_p, min_p)
+    return (None if top_p is None or float(top_p) >= 1.0 else float(top_p),
+            None if min_p is None or float(min_p) <= 0.0 else float(min_p))
+
+
 def sample_next(logits: torch.Tensor, temperature: float = 1.0, top_k: int | None = None,
-                generator: torch.Generator | None = None) -> torch.Tensor:
-    """nanoGPT's sampling: logits / temperature, optional top-k, softmax, multinomial -> [B, 1]."""
+                generator: torch.Generator | None = None, top_p: float | None = None,
+                min_p: float | None = None) -> torch.Tensor:
+    """nanoGPT's sampling: logits / temperature, optional top-k (None or 0: off), nucleus
+    ``top_p`` and ``min_p`` (``ops.filter_logits``), softmax, multinomial -> [B, 1]."""
+    top_p, min_p = sampling_filters(top_p, min_p)
     logits = logits.float() / temperature
-    if top_k is not None:
+    if top_k:
         v, _ = torch.topk(logits, min(top_k, logits.size(-1)))
         logits = logits.masked_fill(logits < v[:, -1:], -float("Inf"))  # basic slicing: capturable
+    if top_p is not None or min_p is not None:
+        logits = ops.filter_logits(logits, None, top_p, min_p)
     probs = torch.softmax(logits, dim=-1)
     return torch.multinomial(probs, num_samples=1, generator=generator)
 
@@ -313,24 +333,26 @@ def sample_next(logits: torch.Tensor, temperature: float = 1.0, top_k: int | Non
 @torch.no_grad()
 def generate_cached(model, idx: torch.Tensor, max_new_tokens: int, temperature: float = 1.0,
                     top_k: int | None = None, use_graph: bool | None = None,
-                    decoder: "Decoder | None" = None) -> torch.Tensor:
+                    decoder: "Decoder | None" = None, top_p: float | None = None,
+                    min_p: float | None = None) -> torch.Tensor:
     """``model.generate`` with KV caches: same sampling, one token's forward per new token.
 
     ``decoder``: a Decoder to reuse across calls (same batch size): its weight shadows and
     captured graphs survive, so ``sample.py``'s num_samples loop captures once.  The caller
     releases it; without one, a temporary decoder is built and released here."""
     B, T0 = idx.shape
+    top_p, min_p = sampling_filters(top_p, min_p)
     if max_new_tokens <= 0:
         return idx
     if T0 + max_new_tokens - 1 > model.config.block_size:
         # the caches hold block_size positions; nanoGPT crops the context beyond that
-        return model.generate(idx, max_new_tokens, temperature=temperature, top_k=top_k)
+        return model.generate(idx, max_new_tokens, temperature=temperature, top_k=top_k, top_p=top_p, min_p=min_p)
     own = decoder is None or decoder.B != B
     dec = Decoder(model, B, max_len=model.config.block_size, use_graph=use_graph) if own else decoder
     try:
         dec.reseed()  # every call draws its own samples, also on a reused decoder / graph
-        dec.sample_into(dec.prefill(idx), temperature, top_k)  # pos = T0: gen[:, T0]
-        dec.run(max_new_tokens - 1, temperature, top_k)
+        dec.sample_into(dec.prefill(idx), temperature, top_k, None, top_p, min_p)  # pos = T0: gen[:, T0]
+        dec.run(max_new_tokens - 1, temperature, top_k, None, top_p, min_p)
         return torch.cat([idx, dec.gen[:, T0:T0 + max_new_tokens]], dim=1)
     finally:
         if own:
@@ -348,7 +370,8 @@ def _cut_at_stop(new: torch.Tensor, stop_token: int | None) -> torch.Tensor:
 @torch.no_grad()
 def generate_batch(model, prompts, max_new_tokens: int, temperature: float = 1.0, top_k: int | None = None,
                    stop_token: int | None = None, use_graph: bool | None = None,
-                   decoder: "Decoder | None" = None) -> list[torch.Tensor]:
+                   decoder: "Decoder | None" = None, top_p: float | None = None,
+                   min_p: float | None = None) -> list[torch.Tensor]:
     """Generate for a list of prompts of unequal lengths as one batch.
 
     ``prompts``: 1-D token tensors, each of length >= 1.  Every result is its prompt followed
@@ -363,6 +386,7 @@ def generate_batch(model, prompts, max_new_tokens: int, temperature: float = 1.0
     shadows and captured graphs survive); the caller releases it."""
     if stop_token is not None and stop_token < 0:
         stop_token = None
+    top_p, min_p = sampling_filters(top_p, min_p)
     prompts = [p.view(-1) for p in prompts]
     assert all(p.numel() >= 1 for p in prompts), "every prompt needs at least one token"
     if max_new_tokens <= 0:
@@ -374,7 +398,7 @@ def generate_batch(model, prompts, max_new_tokens: int, temperature: float = 1.0
     for i, p in enumerate(prompts):
         if i not in rows:
             y = generate_cached(model, p.to(device)[None], max_new_tokens, temperature=temperature, top_k=top_k,
-                                use_graph=use_graph)[0]
+                                use_graph=use_graph, top_p=top_p, min_p=min_p)[0]
             outs[i] = torch.cat([y[:p.numel()], _cut_at_stop(y[p.numel():], stop_token)])
     if not rows:
         return outs
@@ -388,8 +412,8 @@ def generate_batch(model, prompts, max_new_tokens: int, temperature: float = 1.0
     try:
         dec.reseed()
         logits = dec.prefill(idx, torch.tensor(lens, dtype=torch.int64, device=device))
-        dec.sample_into(logits, temperature, top_k, stop_token)  # gen[b, lens[b]]
-        dec.run(max_new_tokens - 1, temperature, top_k, stop_token)
+        dec.sample_into(logits, temperature, top_k, stop_token, top_p, min_p)  # gen[b, lens[b]]
+        dec.run(max_new_tokens - 1, temperature, top_k, stop_token, top_p, min_p)
         for b, i in enumerate(rows):
             new = dec.gen[b, lens[b]:lens[b] + max_new_tokens]
             outs[i] = torch.cat([idx[b, :lens[b]], _cut_at_stop(new, stop_token)])

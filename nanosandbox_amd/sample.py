@@ -12,6 +12,8 @@ KV caches, replayed as a HIP graph (``runtime/decode.py``).  ``--sample_batch=N`
 samples of the prompt per decoder run, ``--prompts_file=FILE`` one prompt per line as a
 batch of unequal lengths, ``--stop_token=ID`` ends a sample at that token
 (``GPT.generate_batch``: one position and one finished flag per row on the device).
+``--top_p=0.9`` (nucleus) and ``--min_p=0.05`` narrow the sampled set on top of ``top_k``
+(``--top_k=0``: no top-k); on the GPU the selection runs inside the sampling kernel.
 """
 
 from __future__ import annotations
@@ -24,6 +26,7 @@ import torch
 from .config import parse_argv
 from .data import load_meta, resolve_data_dir
 from .models import GPT, GPTConfig
+from .ops import check_sampling_filters
 from .utils import load_checkpoint, load_model_state
 
 SAMPLE_DEFAULTS = dict(
@@ -33,7 +36,9 @@ SAMPLE_DEFAULTS = dict(
     num_samples=10,
     max_new_tokens=500,
     temperature=0.8,
-    top_k=200,
+    top_k=200,  # keep the k most likely tokens; 0: off
+    top_p=1.0,  # nucleus: the smallest set of most likely tokens whose mass reaches top_p; 1.0: off
+    min_p=0.0,  # drop tokens less likely than min_p times the most likely one; 0.0: off
     seed=1337,
     device="cuda",
     dtype="bfloat16",
@@ -67,10 +72,10 @@ def _generate_batches(model, c, encode, decode, start, device):
                 if B not in decs:
                     decs[B] = Decoder(model, B, max_len=model.config.block_size, per_row=True)
                 ys = model.generate_batch(prompts, c["max_new_tokens"], temperature=c["temperature"], top_k=c["top_k"],
-                                          stop_token=stop, decoder=decs[B])
+                                          stop_token=stop, decoder=decs[B], top_p=c["top_p"], min_p=c["min_p"])
             else:
-                ys = [model.generate(p[None], c["max_new_tokens"], temperature=c["temperature"], top_k=c["top_k"])[0]
-                      for p in prompts]
+                ys = [model.generate(p[None], c["max_new_tokens"], temperature=c["temperature"], top_k=c["top_k"],
+                                     top_p=c["top_p"], min_p=c["min_p"])[0] for p in prompts]
             for p, y in zip(prompts, ys):
                 new = y[p.numel():].tolist()
                 if stop is not None and stop in new:
@@ -111,6 +116,7 @@ def _codec(checkpoint, data_dir):
 
 def main(argv=None):
     c = parse_argv(SAMPLE_DEFAULTS, sys.argv[1:] if argv is None else argv)
+    check_sampling_filters(c["top_p"], c["min_p"])
     torch.manual_seed(c["seed"])
     device = c["device"]
     if device.startswith("cuda") and not torch.cuda.is_available():
@@ -148,9 +154,10 @@ def main(argv=None):
             for _ in range(c["num_samples"]):
                 if dec is not None:
                     y = model.generate_cached(x, c["max_new_tokens"], temperature=c["temperature"], top_k=c["top_k"],
-                                              decoder=dec)
+                                              decoder=dec, top_p=c["top_p"], min_p=c["min_p"])
                 else:
-                    y = model.generate(x, c["max_new_tokens"], temperature=c["temperature"], top_k=c["top_k"])
+                    y = model.generate(x, c["max_new_tokens"], temperature=c["temperature"], top_k=c["top_k"],
+                                       top_p=c["top_p"], min_p=c["min_p"])
                 text = decode(y[0].tolist())
                 outs.append(text)
                 print(text)

@@ -1,7 +1,8 @@
 """Generation throughput: nanoGPT's recompute loop vs KV-cache decoding (eager / HIP graph).
 
 Random-init GPT-2 weights of the named size, bf16, a random prompt of --prompt tokens,
---new tokens sampled per sequence (temperature 0.8, top-k 200 as in sample.py).  Prints
+--new tokens sampled per sequence (temperature 0.8, top-k 200 as in sample.py; --top_k,
+--top_p and --min_p choose other settings, e.g. ``--top_k 0 --top_p 0.9``).  Prints
 one JSON line per (model, batch, mode) with new tokens/s over the whole batch and the
 per-token latency.
 
@@ -28,22 +29,23 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from nanosandbox_amd.models import GPT, GPTConfig  # noqa: E402
 from nanosandbox_amd.runtime.decode import Decoder  # noqa: E402
 
+SMP = dict(top_k=200, top_p=None, min_p=None)  # the sampling settings of every mode (--top_k / --top_p / --min_p)
 DIMS = {"gpt2": (12, 12, 768), "gpt2-medium": (24, 16, 1024), "gpt2-large": (36, 20, 1280), "gpt2-xl": (48, 25, 1600)}
 
 
 def run_cached(model, idx, new, use_graph):
     B = idx.shape[0]
     dec = Decoder(model, B, use_graph=use_graph)
-    dec.sample_into(dec.prefill(idx), 0.8, 200)
+    dec.sample_into(dec.prefill(idx), 0.8, **SMP)
     if use_graph:
-        dec.run(1, 0.8, 200)  # capture outside the timed loop
+        dec.run(1, 0.8, **SMP)  # capture outside the timed loop
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     if use_graph:
-        dec.run(new, 0.8, 200)  # step + sampling + feedback: one graph replay per token
+        dec.run(new, 0.8, **SMP)  # step + sampling + feedback: one graph replay per token
     else:
         for _ in range(new):  # eager step + the same device sampling kernel
-            dec.sample_into(dec.step(dec.tok), 0.8, 200)
+            dec.sample_into(dec.step(dec.tok), 0.8, **SMP)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     dec.release()
@@ -61,11 +63,11 @@ def run_rows(model, idx, new, lengths=None):
     B = idx.shape[0]
     dec = Decoder(model, B, use_graph=True, per_row=True)
     lens = None if lengths is None else torch.tensor(lengths, device=idx.device)
-    dec.sample_into(dec.prefill(idx, lens), 0.8, 200)
-    dec.run(1, 0.8, 200)  # capture outside the timed loop
+    dec.sample_into(dec.prefill(idx, lens), 0.8, **SMP)
+    dec.run(1, 0.8, **SMP)  # capture outside the timed loop
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    dec.run(new, 0.8, 200)
+    dec.run(new, 0.8, **SMP)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     dec.release()
@@ -79,11 +81,11 @@ def run_samples(model, prompt, n, new, batched):
     t0 = time.perf_counter()
     if batched:
         dec = Decoder(model, n, max_len=model.config.block_size, per_row=True)
-        model.generate_batch([prompt] * n, new, temperature=0.8, top_k=200, decoder=dec)
+        model.generate_batch([prompt] * n, new, temperature=0.8, **SMP, decoder=dec)
     else:
         dec = Decoder(model, 1, max_len=model.config.block_size)
         for _ in range(n):
-            model.generate_cached(prompt[None], new, temperature=0.8, top_k=200, decoder=dec)
+            model.generate_cached(prompt[None], new, temperature=0.8, **SMP, decoder=dec)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     dec.release()
@@ -93,7 +95,7 @@ def run_samples(model, prompt, n, new, batched):
 def run_recompute(model, idx, new):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    model.generate(idx, new, temperature=0.8, top_k=200)
+    model.generate(idx, new, temperature=0.8, **SMP)
     torch.cuda.synchronize()
     return time.perf_counter() - t0
 
@@ -110,7 +112,13 @@ def main():
     ap.add_argument("--repeat", type=int, default=1, help="run the mode list this many times (interleaved)")
     ap.add_argument("--samples", type=int, default=0, help="also time N samples of one prompt: loop vs one batch")
     ap.add_argument("--calibrate", action="store_true", help="first print the box calibration GEMM (utils/boxcal.py)")
+    ap.add_argument("--top_k", type=int, default=200, help="0: no top-k")
+    ap.add_argument("--top_p", type=float, default=1.0, help="nucleus mass; 1.0: off")
+    ap.add_argument("--min_p", type=float, default=0.0, help="floor relative to the most likely token; 0.0: off")
     a = ap.parse_args()
+    SMP.update(top_k=a.top_k, top_p=a.top_p if a.top_p < 1.0 else None, min_p=a.min_p if a.min_p > 0.0 else None)
+    extra = {k: v for k, v in (("top_k", a.top_k), ("top_p", a.top_p), ("min_p", a.min_p))
+             if v != ap.get_default(k)}  # the default run prints what it always did
     if a.calibrate:
         from nanosandbox_amd.utils.boxcal import calibration_gemm
         print(json.dumps({"calibration_gemm": calibration_gemm()}), flush=True)
@@ -139,7 +147,8 @@ def main():
                         run_cached(model, idx, 4, mode == "graph")
                         dt = run_cached(model, idx, n, mode == "graph")
                     print(json.dumps({"model": name, "batch": B, "mode": mode, "prompt": a.prompt, "new_tokens": n,
-                                      "tokens_per_s": round(B * n / dt, 1), "ms_per_token": round(dt / n * 1e3, 3)}),
+                                      "tokens_per_s": round(B * n / dt, 1), "ms_per_token": round(dt / n * 1e3, 3),
+                                      **extra}),
                           flush=True)
         if a.samples:
             prompt = torch.randint(0, 50257, (a.prompt,), device="cuda")
@@ -149,7 +158,8 @@ def main():
                     dt = run_samples(model, prompt, a.samples, a.new, batched)
                     print(json.dumps({"model": name, "samples": a.samples, "new_tokens": a.new, "prompt": a.prompt,
                                       "mode": "sample_batch" if batched else "sample_loop",
-                                      "tokens_per_s": round(a.samples * a.new / dt, 1), "seconds": round(dt, 3)}),
+                                      "tokens_per_s": round(a.samples * a.new / dt, 1), "seconds": round(dt, 3),
+                                      **extra}),
                           flush=True)
         del model
         torch.cuda.empty_cache()
