@@ -1,0 +1,899 @@
+// Int8-weight forms of the weight-streaming decode kernels of decode.hip (the serving path
+// with Decoder(..., quantize="int8")): the weight of every linear is stored as one int8 per
+// element with one fp32 scale per output row (ops.quantize_rows_int8), so a decode step
+// streams half the bytes of the bf16 step.  All six compute
+//   y[m, n] = act((sum_k x[m, k] q[n, k]) scale[n] + bias[n])
+// with x the bf16-rounded activation row the bf16 kernel forms, fp32 accumulation and the
+// scale applied once per output in the epilogue.  int8 -> float is exact, so the results
+// differ from the bf16 kernels run on the dequantized weights by summation order alone.
+//
+// The prologues (residual add + LayerNorm, embedding + LayerNorm, flash-decoding combine)
+// are the bf16 kernels' own, statement for statement (the single-row ones store the row to
+// LDS in another order, hx() below).  They are repeated here rather than shared: moving
+// them out of decode.hip into a common header changed the compiled code of the bf16 kernels
+// (register allocation, scalar / vector address arithmetic), and this file leaves decode.hip
+// and its kernels byte-identical.
+#include "common.h"
+
+#include <math.h>
+#include <stdlib.h>
+
+#include <algorithm>
+
+namespace {
+
+constexpr int DA_D = 64;        // head dim of the decode-attention kernel
+constexpr int DA_PO = 4;          // o[] offset in a partial: 16-byte aligned for vector reads
+constexpr int DA_PART = DA_PO + DA_D;  // m, l, (pad), o[64]
+
+// The single-row prologues of decode.hip's gemv_row_kernel (see there):
+//   PRO_LN     s = res + branch (fp32; written to res_out by workgroup 0), x = LN(s)
+//   PRO_EMB_LN s = wte[*tok] + wpe[*pos] (written to res_out by workgroup 0), x = LN(s)
+//   PRO_ATTN   x = the flash-decoding combine of the attention partials (ws, H heads)
+enum { PRO_LN = 0, PRO_ATTN = 1, PRO_EMB_LN = 2 };
+
+struct RowPro {
+  const float* res;
+  const bf16_t* branch;
+  float* res_out;
+  const bf16_t* lw;
+  const bf16_t* lb;
+  float eps;
+  const float* ws;
+  int n_split;
+  const int64_t* tok;
+  const int64_t* pos;
+  const bf16_t* wte;
+  const bf16_t* wpe;
+  int64_t* pos_inc;  // PRO_LN: incremented by one thread after the row (the decode step's position)
+};
+
+// LDS position of x[k].  A lane multiplies one 16-byte weight piece (k = 16 g .. 16 g + 15)
+// with 16 values of x; k-contiguous rows would put lane g at a 64-byte stride, all 64 lanes
+// of a read on 4 of the 64 banks.  The 16 values sit as four float4 at [j][g] (j = (k / 4) % 4,
+// nck = K / 16 chunks), so the lanes of a wave read consecutive 16-byte vectors.
+__device__ __forceinline__ int hx(int k, int nck) { return (((k >> 2) & 3) * nck + (k >> 4)) * 4 + (k & 3); }
+
+// The row x[K] into hs[] at hx(k) (256 threads; stat: 2 x 4 floats of LDS; PRO_ATTN also uses
+// hs[K ..] for the chunk weights).  The caller's barrier after it publishes hs[].
+// K <= 2048 (every GPT-2 width): thread g owns x[8g .. 8g+7] and issues all of its loads
+// at once (16-byte vectors), so the row costs one memory round trip and two block
+// reductions; wider rows loop.
+template <int PRO>
+__device__ __forceinline__ void row_prologue(const RowPro& a, float* hs, float (*stat)[4], int K) {
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int nck = K / 16;
+  const bool vec = K <= 2048;
+  const int g8 = 8 * tid;
+  const bool own = vec && g8 < K;
+  if constexpr (PRO == PRO_ATTN) {
+    const int H = K / DA_D, ns = a.n_split;
+    float* fs = hs + K;  // [H][ns] chunk weights 2^(m_s - M) / L
+    for (int h = tid; h < H; h += 256) {
+      const float* part = a.ws + (int64_t)h * ns * DA_PART;
+      float M = -INFINITY;
+#pragma unroll 4
+      for (int sp = 0; sp < ns; ++sp) M = fmaxf(M, part[sp * DA_PART]);
+      float L = 0.0f;
+#pragma unroll 4
+      for (int sp = 0; sp < ns; ++sp) L = fmaf(exp2f(part[sp * DA_PART] - M), part[sp * DA_PART + 1], L);
+      const float inv = 1.0f / L;
+      for (int sp = 0; sp < ns; ++sp) fs[h * ns + sp] = exp2f(part[sp * DA_PART] - M) * inv;  // empty: 0
+    }
+    __syncthreads();
+    for (int k0 = g8; k0 < K; k0 += 8 * 256) {  // 8 dims of one head per thread and pass
+      const int h = k0 / DA_D;
+      const float* o = a.ws + (int64_t)h * ns * DA_PART + DA_PO + (k0 % DA_D);
+      float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll 4
+      for (int sp = 0; sp < ns; ++sp) {
+        const float f = fs[h * ns + sp];
+        const float4 u0 = *reinterpret_cast<const float4*>(o + sp * DA_PART);
+        const float4 u1 = *reinterpret_cast<const float4*>(o + sp * DA_PART + 4);
+        acc[0] = fmaf(f, u0.x, acc[0]);
+        acc[1] = fmaf(f, u0.y, acc[1]);
+        acc[2] = fmaf(f, u0.z, acc[2]);
+        acc[3] = fmaf(f, u0.w, acc[3]);
+        acc[4] = fmaf(f, u1.x, acc[4]);
+        acc[5] = fmaf(f, u1.y, acc[5]);
+        acc[6] = fmaf(f, u1.z, acc[6]);
+        acc[7] = fmaf(f, u1.w, acc[7]);
+      }
+#pragma unroll
+      for (int e = 0; e < 8; ++e) hs[hx(k0 + e, nck)] = bf2f(f2bf(acc[e]));  // the bf16 attention output
+    }
+  } else {
+    const bool write_s = PRO == PRO_EMB_LN || a.branch != nullptr;
+    int64_t te = 0, pe = 0;
+    if constexpr (PRO == PRO_EMB_LN) {
+      te = *a.tok;
+      pe = *a.pos;
+    }
+    float xv[8], lwv[8], lbv[8];
+    float sum = 0.0f;
+    if (vec) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) xv[e] = lwv[e] = lbv[e] = 0.0f;
+      if (own) {
+        if constexpr (PRO == PRO_EMB_LN) {
+          float e0[8], e1[8];
+          load8(a.wte + te * K + g8, e0);
+          load8(a.wpe + pe * K + g8, e1);
+#pragma unroll
+          for (int e = 0; e < 8; ++e) xv[e] = e0[e] + e1[e];
+        } else {
+          const float4 r0 = *reinterpret_cast<const float4*>(a.res + g8);
+          const float4 r1 = *reinterpret_cast<const float4*>(a.res + g8 + 4);
+          xv[0] = r0.x; xv[1] = r0.y; xv[2] = r0.z; xv[3] = r0.w;
+          xv[4] = r1.x; xv[5] = r1.y; xv[6] = r1.z; xv[7] = r1.w;
+          if (a.branch) {
+            float bv[8];
+            load8(a.branch + g8, bv);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) xv[e] += bv[e];
+          }
+        }
+        load8(a.lw + g8, lwv);
+        if (a.lb) load8(a.lb + g8, lbv);
+      }
+#pragma unroll
+      for (int e = 0; e < 8; ++e) sum += xv[e];
+    } else {
+      for (int k = tid; k < K; k += 256) {
+        float v;
+        if constexpr (PRO == PRO_EMB_LN) {
+          v = bf2f(a.wte[te * K + k]) + bf2f(a.wpe[pe * K + k]);
+        } else {
+          v = a.res[k];
+          if (a.branch) v += bf2f(a.branch[k]);
+        }
+        hs[hx(k, nck)] = v;
+        sum += v;
+      }
+    }
+    sum = wave_sum(sum);
+    if (lane == 0) stat[0][w] = sum;
+    __syncthreads();
+    const float mean = (stat[0][0] + stat[0][1] + stat[0][2] + stat[0][3]) / (float)K;
+    float sq = 0.0f;
+    if (vec) {
+      if (own)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) sq = fmaf(xv[e] - mean, xv[e] - mean, sq);
+    } else {
+      for (int k = tid; k < K; k += 256) {
+        const float d = hs[hx(k, nck)] - mean;
+        sq = fmaf(d, d, sq);
+      }
+    }
+    sq = wave_sum(sq);
+    if (lane == 0) stat[1][w] = sq;
+    __syncthreads();
+    const float rstd = rsqrtf((stat[1][0] + stat[1][1] + stat[1][2] + stat[1][3]) / (float)K + a.eps);
+    if (vec) {
+      if (own) {
+        if (blockIdx.x == 0 && write_s) {
+          *reinterpret_cast<float4*>(a.res_out + g8) = make_float4(xv[0], xv[1], xv[2], xv[3]);
+          *reinterpret_cast<float4*>(a.res_out + g8 + 4) = make_float4(xv[4], xv[5], xv[6], xv[7]);
+        }
+#pragma unroll
+        for (int e = 0; e < 8; ++e) hs[hx(g8 + e, nck)] = bf2f(f2bf((xv[e] - mean) * rstd * lwv[e] + lbv[e]));
+      }
+    } else {
+      for (int k = tid; k < K; k += 256) {
+        const float sv = hs[hx(k, nck)];
+        if (blockIdx.x == 0 && write_s) a.res_out[k] = sv;
+        float h = (sv - mean) * rstd * bf2f(a.lw[k]);
+        if (a.lb) h += bf2f(a.lb[k]);
+        hs[hx(k, nck)] = bf2f(f2bf(h));  // the bf16 activation the LayerNorm kernel would hand the GEMM
+      }
+    }
+  }
+}
+
+// NSA_GEMV_GRID: workgroup cap of the single-row GEMVs (default 1024: 4 per CU), as in decode.hip
+int gemv_row_grid() {
+  static const int g = [] {
+    const char* e = getenv("NSA_GEMV_GRID");
+    return e ? std::max(1, atoi(e)) : 1024;
+  }();
+  return g;
+}
+
+__device__ __forceinline__ float sk_wave_sum(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// Prologue of the skinny GEMMs with the residual add + LayerNorm in front (256 threads):
+// s = res + branch and x = LN(s) for the M batch rows (wave w: rows w, w + 4, ...; a row of
+// K <= 2048 lives in 32 registers per lane, two-pass mean / variance as nanoGPT's fp32
+// LayerNorm), x stored as bf16 in xs ([16][K + 8], padded rows); rows M..15 are zeroed
+// (they only feed output columns m >= M, which are never stored); workgroup 0 writes s
+// (fp32).  The caller's barrier after it publishes xs[].
+__device__ __forceinline__ void skinny_ln_prologue(const float* __restrict__ res, const bf16_t* __restrict__ branch,
+                                                   float* __restrict__ s_out, const bf16_t* __restrict__ lw,
+                                                   const bf16_t* __restrict__ lb, float eps, bf16_t* xs, int M,
+                                                   int K) {
+  const int KP = K + 8;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  for (int m = M + w; m < 16; m += 4)
+    for (int k = 8 * lane; k < K; k += 512) *reinterpret_cast<uint4*>(xs + m * KP + k) = uint4{0u, 0u, 0u, 0u};
+  for (int m = w; m < M; m += 4) {
+    const int mm = m;
+    float v[4][8];
+    float sum = 0.0f;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int k = (q * 64 + lane) * 8;
+      if (k < K) {
+        const float4 r0 = *reinterpret_cast<const float4*>(res + (int64_t)mm * K + k);
+        const float4 r1 = *reinterpret_cast<const float4*>(res + (int64_t)mm * K + k + 4);
+        v[q][0] = r0.x; v[q][1] = r0.y; v[q][2] = r0.z; v[q][3] = r0.w;
+        v[q][4] = r1.x; v[q][5] = r1.y; v[q][6] = r1.z; v[q][7] = r1.w;
+        if (branch) {
+          float bv[8];
+          load8(branch + (int64_t)mm * K + k, bv);
+#pragma unroll
+          for (int e = 0; e < 8; ++e) v[q][e] += bv[e];
+        }
+#pragma unroll
+        for (int e = 0; e < 8; ++e) sum += v[q][e];
+      }
+    }
+    const float mean = sk_wave_sum(sum) / (float)K;
+    float sq = 0.0f;
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+      if ((q * 64 + lane) * 8 < K)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) sq = fmaf(v[q][e] - mean, v[q][e] - mean, sq);
+    const float rstd = rsqrtf(sk_wave_sum(sq) / (float)K + eps);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int k = (q * 64 + lane) * 8;
+      if (k < K) {
+        float wv[8], bv[8], o[8];
+        load8(lw + k, wv);
+        if (lb) {
+          load8(lb + k, bv);
+        } else {
+#pragma unroll
+          for (int e = 0; e < 8; ++e) bv[e] = 0.0f;
+        }
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o[e] = (v[q][e] - mean) * rstd * wv[e] + bv[e];
+        store8(xs + m * KP + k, o);
+        if (blockIdx.x == 0 && s_out && m < M) {
+          float* sp = s_out + (int64_t)m * K + k;
+          *reinterpret_cast<float4*>(sp) = make_float4(v[q][0], v[q][1], v[q][2], v[q][3]);
+          *reinterpret_cast<float4*>(sp + 4) = make_float4(v[q][4], v[q][5], v[q][6], v[q][7]);
+        }
+      }
+    }
+  }
+}
+
+
+// ---------------------------------------------------------------------------
+// int8 -> fp32 / bf16 (two's-complement bytes, exact)
+// ---------------------------------------------------------------------------
+// byte j of a dword as a float
+__device__ __forceinline__ float q8f(uint32_t w, int j) { return (float)(int)(int8_t)(w >> (8 * j)); }
+
+// the 8 weights of two dwords (k order: byte 0 of lo first)
+__device__ __forceinline__ void unpack8q(uint32_t lo, uint32_t hi, float (&f)[8]) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    f[j] = q8f(lo, j);
+    f[4 + j] = q8f(hi, j);
+  }
+}
+
+// bytes j, j + 1 of a dword as a packed bf16 pair.  An int8 value has at most 7
+// significant bits, so the high half of its fp32 form is already its exact bf16: the two
+// high halves are packed by one byte permute, without a rounding convert.
+__device__ __forceinline__ uint32_t q8bf2(uint32_t w, int j) {
+  return __builtin_amdgcn_perm(__float_as_uint(q8f(w, j + 1)), __float_as_uint(q8f(w, j)), 0x07060302u);
+}
+// the 8 weights of two dwords as one MFMA fragment (8 bf16)
+__device__ __forceinline__ bf16x8 q8frag(uint32_t lo, uint32_t hi) {
+  const uint4 u = {q8bf2(lo, 0), q8bf2(lo, 2), q8bf2(hi, 0), q8bf2(hi, 2)};
+  return __builtin_bit_cast(bf16x8, u);
+}
+
+// V values per lane -> lane holds the wave-wide sum of value `index` (decode.hip's
+// wave_reduce_multi: halve-and-exchange butterfly)
+template <int V>
+__device__ __forceinline__ float wave_reduce_multi(float (&v)[V], int lane, int& index) {
+  int cnt = V;
+  index = 0;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    if (cnt > 1) {
+      const bool upper = (lane & off) != 0;
+      const int h = cnt / 2;
+#pragma unroll
+      for (int i = 0; i < V / 2; ++i) {
+        if (i < h) {
+          const float send = upper ? v[i] : v[i + h];
+          const float keep = upper ? v[i + h] : v[i];
+          v[i] = keep + __shfl_xor(send, off, 64);
+        }
+      }
+      if (upper) index += h;
+      cnt = h;
+    } else {
+      v[0] += __shfl_xor(v[0], off, 64);
+    }
+  }
+  return v[0];
+}
+
+// ---------------------------------------------------------------------------
+// Decode linear, int8 weights, M <= 8 rows on the vector ALU with a K loop (nsa_gemv's
+// counterpart for 2 .. NSA_GEMV_MAX_ROWS rows, and for one row wider than 8192).
+// A lane's 16-byte load carries 16 weights of one row: chunk g covers k = 16g .. 16g+15.
+// KW of the workgroup's 4 waves split K and the other 4 / KW wave sets take further
+// columns: a workgroup covers (4 / KW) * NC output columns.
+// ---------------------------------------------------------------------------
+template <int M, int ACT, bool OUTF, int NC, int KW>
+__global__ __launch_bounds__(256) void gemv_q8_kernel(const bf16_t* __restrict__ x, const int8_t* __restrict__ Wq,
+                                                      const float* __restrict__ scale,
+                                                      const bf16_t* __restrict__ bias, void* __restrict__ y, int rows,
+                                                      int N, int K) {
+  constexpr int V = NC * M, CG = 4 / KW;
+  __shared__ float red[4][V];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int kw = w % KW, cg = w / KW;
+  const int n0 = (blockIdx.x * CG + cg) * NC;
+  float acc[V];
+#pragma unroll
+  for (int i = 0; i < V; ++i) acc[i] = 0.0f;
+  const int nchunk = K / 16;
+#pragma unroll 2
+  for (int g = kw * 64 + lane; g < nchunk; g += 64 * KW) {
+    const int k = 16 * g;
+    uint4 q[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) q[c] = *reinterpret_cast<const uint4*>(Wq + (int64_t)min(n0 + c, N - 1) * K + k);
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      float xf[M][8];
+#pragma unroll
+      for (int m = 0; m < M; ++m) {
+        if (m < rows) load8(x + (int64_t)m * K + k + 8 * h, xf[m]);
+        else
+#pragma unroll
+          for (int j = 0; j < 8; ++j) xf[m][j] = 0.0f;
+      }
+#pragma unroll
+      for (int c = 0; c < NC; ++c) {
+        float wf[8];
+        unpack8q(h ? q[c].z : q[c].x, h ? q[c].w : q[c].y, wf);
+#pragma unroll
+        for (int m = 0; m < M; ++m)
+#pragma unroll
+          for (int j = 0; j < 8; ++j) acc[c * M + m] = fmaf(xf[m][j], wf[j], acc[c * M + m]);
+      }
+    }
+  }
+  int idx;
+  const float v = wave_reduce_multi<V>(acc, lane, idx);
+  // lanes below the last split's offset hold duplicates: the first of each group writes
+  constexpr int DUP = 64 / V;  // lanes per value
+  if ((lane & (DUP - 1)) == 0) red[w][idx] = v;
+  __syncthreads();
+  if (tid < CG * V) {
+    const int g = tid / V, i = tid % V;
+    const int c = i / M, m = i % M, n = (blockIdx.x * CG + g) * NC + c;
+    if (m < rows && n < N) {
+      float o = 0.0f;
+#pragma unroll
+      for (int q = 0; q < KW; ++q) o += red[g * KW + q][i];
+      o *= scale[n];
+      if (bias) o += bf2f(bias[n]);
+      if (ACT == 1) o = nsa_gelu(o);
+      if constexpr (OUTF)
+        reinterpret_cast<float*>(y)[(int64_t)m * N + n] = o;
+      else
+        reinterpret_cast<bf16_t*>(y)[(int64_t)m * N + n] = f2bf(o);
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
+// One decode row, int8 weights: the single-row kernels.  KW of the workgroup's 4 waves split
+// K and the other 4 / KW wave sets take further columns (BN = (4 / KW) * NC columns per
+// block); a lane owns chunks g = kw * 64 + lane + p * 64 * KW, p < P, so KW * P * 64 >= K / 16
+// covers the row (q8_cfg: every K <= 8192 with P <= 2) and all weight loads of a block issue
+// together, with no K loop: chunks past the end re-read the last chunk against a zeroed x
+// (branch-free), rows past N re-read row N - 1 and are not stored.
+// ---------------------------------------------------------------------------
+struct Q8Cfg {
+  int kw, p;
+};
+// the fewest waves along K that cover the row in one pass; two passes beyond 4096
+Q8Cfg q8_cfg(int K) {
+  const int nck = K / 16;
+  if (nck <= 64) return {1, 1};
+  if (nck <= 128) return {2, 1};
+  if (nck <= 256) return {4, 1};
+  return {4, 2};  // nck <= 512 (callers check)
+}
+// the weights of block row set n0 into wp (all P * NC loads in flight together)
+template <int NC, int P>
+__device__ __forceinline__ void q8_load_block(const int8_t* __restrict__ Wq, int n0, int N, int K, const int (&gc)[P],
+                                              uint4 (&wp)[P][NC]) {
+#pragma unroll
+  for (int p = 0; p < P; ++p)
+#pragma unroll
+    for (int c = 0; c < NC; ++c)
+      wp[p][c] = *reinterpret_cast<const uint4*>(Wq + (int64_t)min(n0 + c, N - 1) * K + 16 * gc[p]);
+}
+// acc[c] = sum over the lane's chunks of x . w
+template <int NC, int P>
+__device__ __forceinline__ void q8_dot_block(const float (&xr)[P][16], const uint4 (&wp)[P][NC], float (&acc)[NC]) {
+#pragma unroll
+  for (int c = 0; c < NC; ++c) acc[c] = 0.0f;
+#pragma unroll
+  for (int p = 0; p < P; ++p)
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      float wf[8];
+      unpack8q(wp[p][c].x, wp[p][c].y, wf);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) acc[c] = fmaf(xr[p][j], wf[j], acc[c]);
+      unpack8q(wp[p][c].z, wp[p][c].w, wf);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) acc[c] = fmaf(xr[p][8 + j], wf[j], acc[c]);
+    }
+}
+
+// y[n] = act((x . Wq[n]) scale[n] + bias[n]) with the producer of x in the prologue
+// (gemv_row_kernel's counterpart).  Each workgroup loops over column blocks cb, cb +
+// gridDim.x, ...; the first block's weights are issued before the prologue and the next
+// block's before the reduction; x stays in registers across the blocks.
+template <int PRO, int ACT, bool OUTF, int NC, int KW, int P>
+__global__ __launch_bounds__(256) void gemv_row_q8_kernel(const RowPro a, const int8_t* __restrict__ Wq,
+                                                          const float* __restrict__ scale,
+                                                          const bf16_t* __restrict__ bias, void* __restrict__ y,
+                                                          int N, int K) {
+  extern __shared__ __attribute__((aligned(16))) float hs[];  // [K] input row at hx(k)
+  constexpr int CG = 4 / KW, BN = CG * NC;  // wave sets / columns per block
+  __shared__ float red[4][NC];
+  __shared__ float stat[2][4];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int kw = w % KW, cg = w / KW;
+  const int nchunk = K / 16;
+  const int nblk = (N + BN - 1) / BN;
+  int gc[P];
+  bool live[P];
+#pragma unroll
+  for (int p = 0; p < P; ++p) {
+    const int g = kw * 64 + lane + p * 64 * KW;
+    live[p] = g < nchunk;
+    gc[p] = live[p] ? g : nchunk - 1;
+  }
+  int cb = blockIdx.x;
+  uint4 wp[P][NC];
+  q8_load_block<NC, P>(Wq, cb * BN + cg * NC, N, K, gc, wp);
+  row_prologue<PRO>(a, hs, stat, K);
+  __syncthreads();
+  float xr[P][16];
+#pragma unroll
+  for (int p = 0; p < P; ++p)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float4 v = reinterpret_cast<const float4*>(hs)[j * nchunk + gc[p]];
+      if (!live[p]) v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+      xr[p][4 * j] = v.x;
+      xr[p][4 * j + 1] = v.y;
+      xr[p][4 * j + 2] = v.z;
+      xr[p][4 * j + 3] = v.w;
+    }
+  for (; cb < nblk; cb += gridDim.x) {
+    float acc[NC];
+    q8_dot_block<NC, P>(xr, wp, acc);
+    const int nb = cb + gridDim.x;
+    if (nb < nblk) q8_load_block<NC, P>(Wq, nb * BN + cg * NC, N, K, gc, wp);  // in flight during the reduction
+    int idx;
+    const float v = wave_reduce_multi<NC>(acc, lane, idx);
+    if ((lane & (64 / NC - 1)) == 0) red[w][idx] = v;
+    __syncthreads();
+    if (tid < BN) {
+      const int g = tid / NC, c = tid % NC;
+      const int n = cb * BN + tid;
+      if (n < N) {
+        float o = 0.0f;
+#pragma unroll
+        for (int q = 0; q < KW; ++q) o += red[g * KW + q][c];
+        o *= scale[n];
+        if (bias) o += bf2f(bias[n]);
+        if (ACT == 1) o = nsa_gelu(o);
+        if constexpr (OUTF)
+          reinterpret_cast<float*>(y)[n] = o;
+        else
+          reinterpret_cast<bf16_t*>(y)[n] = f2bf(o);
+      }
+    }
+    __syncthreads();  // red[] is rewritten by the next block
+  }
+  if constexpr (PRO == PRO_LN)
+    if (a.pos_inc && blockIdx.x == 0 && tid == 0) *a.pos_inc += 1;
+}
+
+// The same for a row x that is already in memory (nsa_gemv_q8 at one row): one block per
+// workgroup, x read with the weights.
+template <int ACT, bool OUTF, int NC, int KW, int P>
+__global__ __launch_bounds__(256) void gemv1_q8_kernel(const bf16_t* __restrict__ x, const int8_t* __restrict__ Wq,
+                                                       const float* __restrict__ scale,
+                                                       const bf16_t* __restrict__ bias, void* __restrict__ y, int N,
+                                                       int K) {
+  constexpr int CG = 4 / KW, BN = CG * NC;
+  __shared__ float red[4][NC];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int kw = w % KW, cg = w / KW;
+  const int nchunk = K / 16;
+  int gc[P];
+  bool live[P];
+#pragma unroll
+  for (int p = 0; p < P; ++p) {
+    const int g = kw * 64 + lane + p * 64 * KW;
+    live[p] = g < nchunk;
+    gc[p] = live[p] ? g : nchunk - 1;
+  }
+  uint4 wp[P][NC];
+  q8_load_block<NC, P>(Wq, blockIdx.x * BN + cg * NC, N, K, gc, wp);
+  float xr[P][16];
+#pragma unroll
+  for (int p = 0; p < P; ++p) {
+    float lo[8], hi[8];
+    load8(x + 16 * gc[p], lo);
+    load8(x + 16 * gc[p] + 8, hi);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      xr[p][j] = live[p] ? lo[j] : 0.0f;
+      xr[p][8 + j] = live[p] ? hi[j] : 0.0f;
+    }
+  }
+  float acc[NC];
+  q8_dot_block<NC, P>(xr, wp, acc);
+  int idx;
+  const float v = wave_reduce_multi<NC>(acc, lane, idx);
+  if ((lane & (64 / NC - 1)) == 0) red[w][idx] = v;
+  __syncthreads();
+  if (tid < BN) {
+    const int g = tid / NC, c = tid % NC;
+    const int n = blockIdx.x * BN + tid;
+    if (n < N) {
+      float o = 0.0f;
+#pragma unroll
+      for (int q = 0; q < KW; ++q) o += red[g * KW + q][c];
+      o *= scale[n];
+      if (bias) o += bf2f(bias[n]);
+      if (ACT == 1) o = nsa_gelu(o);
+      if constexpr (OUTF)
+        reinterpret_cast<float*>(y)[n] = o;
+      else
+        reinterpret_cast<bf16_t*>(y)[n] = f2bf(o);
+    }
+  }
+}
+
+template <int PRO>
+hipError_t launch_gemv_row_q8(const RowPro& a, const void* Wq, const void* scale, const void* bias, void* y, int N,
+                              int K, int act, int out_f32, hipStream_t s) {
+  // the row, plus the chunk weights of the attention combine
+  const size_t lds = (size_t)(K + (PRO == PRO_ATTN ? (K / DA_D) * a.n_split : 0)) * sizeof(float);
+  const int8_t* w = (const int8_t*)Wq;
+  const float* sc = (const float*)scale;
+  const bf16_t* b = (const bf16_t*)bias;
+  const Q8Cfg cfg = q8_cfg(K);
+  // columns per wave set: 4 as the bf16 kernel, 2 where one wave covers K (K <= 1024: 8 columns per
+  // block; measured per token at batch 1, GPT-2 124M: 0.309 ms with 2, 0.319 with 4; bf16 0.336)
+  const int nc = cfg.kw == 1 ? 2 : 4;
+  // at most gemv_row_grid() workgroups, each looping over column blocks
+  const int bn = (4 / cfg.kw) * nc;
+  const int nblk = (N + bn - 1) / bn;
+  const unsigned grid = (unsigned)std::min(nblk, gemv_row_grid());
+#define NSA_ROWQ(NC_, KW_, P_)                                                                       \
+  do {                                                                                               \
+    if (act)                                                                                         \
+      gemv_row_q8_kernel<PRO, 1, false, NC_, KW_, P_><<<grid, 256, lds, s>>>(a, w, sc, b, y, N, K); \
+    else if (out_f32)                                                                                \
+      gemv_row_q8_kernel<PRO, 0, true, NC_, KW_, P_><<<grid, 256, lds, s>>>(a, w, sc, b, y, N, K);  \
+    else                                                                                             \
+      gemv_row_q8_kernel<PRO, 0, false, NC_, KW_, P_><<<grid, 256, lds, s>>>(a, w, sc, b, y, N, K); \
+  } while (0)
+  if (cfg.kw == 1)
+    NSA_ROWQ(2, 1, 1);
+  else if (cfg.kw == 2)
+    NSA_ROWQ(4, 2, 1);
+  else if (cfg.p == 1)
+    NSA_ROWQ(4, 4, 1);
+  else
+    NSA_ROWQ(4, 4, 2);
+#undef NSA_ROWQ
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// Skinny GEMM (2..16 decode rows on the matrix cores), int8 weights.  As in
+// skinny_gemm_kernel the weight is the A operand of v_mfma_f32_16x16x32_bf16 (lane l: row
+// n0 + (l & 15)) and X^T the B operand (lane l: batch row l & 15).  A lane's 16-byte weight
+// load holds 16 consecutive k of its row, the k of a 64-wide unit u being
+//   64 u + 16 (l >> 4) + 8 h + i,   h = 0, 1 (the MFMA), i = 0 .. 7 (the fragment element),
+// so one load feeds two MFMAs, and the X fragment of MFMA h is the 16 bytes of the batch
+// row at the same k: the two fragments permute k alike, which a dot product does not see.
+// The 8 bytes of a fragment become bf16 in registers (q8frag).  Any N: weight rows past
+// the end read row N - 1 and their outputs are not stored.
+// ---------------------------------------------------------------------------
+template <int ACT, bool OUTF>
+__device__ __forceinline__ void skinny_q8_epilogue(const f32x4& acc, float (*red)[4][64],
+                                                   const float* __restrict__ scale, const bf16_t* __restrict__ bias,
+                                                   void* __restrict__ yv, int M, int N, int n0) {
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  // C layout: lane l holds column m = l & 15 of the 16-row group, rows n = 4 (l >> 4) + i
+#pragma unroll
+  for (int i = 0; i < 4; ++i) red[w][i][lane] = acc[i];
+  __syncthreads();
+  const int n = tid & 15, m = tid >> 4;  // n fastest: coalesced stores
+  if (m < M && n0 + n < N) {
+    const int i = n & 3, ln = 16 * (n >> 2) + m;
+    float o = red[0][i][ln] + red[1][i][ln] + red[2][i][ln] + red[3][i][ln];
+    o *= scale[n0 + n];
+    if (bias) o += bf2f(bias[n0 + n]);
+    if constexpr (ACT == 1) o = nsa_gelu(o);
+    if constexpr (OUTF)
+      reinterpret_cast<float*>(yv)[(int64_t)m * N + n0 + n] = o;
+    else
+      reinterpret_cast<bf16_t*>(yv)[(int64_t)m * N + n0 + n] = f2bf(o);
+  }
+}
+
+// UN 64-wide units per wave in flight; units past the end re-read the last unit with a zero
+// weight fragment (branch-free, so every load of a round issues before any wait)
+template <int ACT, bool OUTF, int UN>
+__global__ __launch_bounds__(256) void skinny_gemm_q8_kernel(const bf16_t* __restrict__ x,
+                                                             const int8_t* __restrict__ Wq,
+                                                             const float* __restrict__ scale,
+                                                             const bf16_t* __restrict__ bias, void* __restrict__ yv,
+                                                             int M, int N, int K) {
+  __shared__ float red[4][4][64];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int n0 = blockIdx.x * 16;
+  const int g = lane >> 4, c = lane & 15;
+  const int8_t* wrow = Wq + (int64_t)min(n0 + c, N - 1) * K + 16 * g;
+  const bf16_t* xrow = x + (int64_t)min(c, M - 1) * K + 16 * g;
+  f32x4 acc = f32x4{};
+  const int U = K / 64;  // wave w takes units w, w + 4, w + 8, ...
+  for (int u0 = w; u0 < U; u0 += 4 * UN) {
+    uint4 a[UN], b[UN][2];
+#pragma unroll
+    for (int j = 0; j < UN; ++j) {
+      const int uu = u0 + 4 * j;
+      const int uc = uu < U ? uu : U - 1;
+      a[j] = *reinterpret_cast<const uint4*>(wrow + 64 * uc);
+      if (uu >= U) a[j] = uint4{0u, 0u, 0u, 0u};
+      b[j][0] = *reinterpret_cast<const uint4*>(xrow + 64 * uc);
+      b[j][1] = *reinterpret_cast<const uint4*>(xrow + 64 * uc + 8);
+    }
+#pragma unroll
+    for (int j = 0; j < UN; ++j) {
+      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(q8frag(a[j].x, a[j].y), __builtin_bit_cast(bf16x8, b[j][0]), acc,
+                                                    0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(q8frag(a[j].z, a[j].w), __builtin_bit_cast(bf16x8, b[j][1]), acc,
+                                                    0, 0, 0);
+    }
+  }
+  skinny_q8_epilogue<ACT, OUTF>(acc, red, scale, bias, yv, M, N, n0);
+}
+
+// The same with the residual add + LayerNorm in the prologue (skinny_ln_gemm_kernel's
+// counterpart): the first round of weight loads is issued before the prologue and each
+// round prefetches the next, so the weight stream overlaps the LayerNorm.
+template <int ACT, bool OUTF>
+__global__ __launch_bounds__(256) void skinny_ln_gemm_q8_kernel(const float* __restrict__ res,
+                                                                const bf16_t* __restrict__ branch,
+                                                                float* __restrict__ s_out,
+                                                                const bf16_t* __restrict__ lw,
+                                                                const bf16_t* __restrict__ lb, float eps,
+                                                                const int8_t* __restrict__ Wq,
+                                                                const float* __restrict__ scale,
+                                                                const bf16_t* __restrict__ bias,
+                                                                void* __restrict__ yv, int M, int N, int K) {
+  extern __shared__ __attribute__((aligned(16))) bf16_t xs[];  // [16][K + 8]
+  __shared__ float red[4][4][64];
+  const int KP = K + 8;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int n0 = blockIdx.x * 16;
+  const int g = lane >> 4, c = lane & 15;
+  const int8_t* wrow = Wq + (int64_t)min(n0 + c, N - 1) * K + 16 * g;
+  const int U = K / 64;
+  constexpr int UN = 4;
+  uint4 a[UN];
+  auto load_a = [&](int u0, uint4 (&dst)[UN]) {
+#pragma unroll
+    for (int j = 0; j < UN; ++j) {
+      const int uu = u0 + 4 * j;
+      dst[j] = *reinterpret_cast<const uint4*>(wrow + 64 * (uu < U ? uu : U - 1));
+      if (uu >= U) dst[j] = uint4{0u, 0u, 0u, 0u};
+    }
+  };
+  load_a(w, a);
+  skinny_ln_prologue(res, branch, s_out, lw, lb, eps, xs, M, K);
+  __syncthreads();
+  f32x4 acc = f32x4{};
+  for (int u0 = w; u0 < U; u0 += 4 * UN) {
+    uint4 b[UN][2];
+#pragma unroll
+    for (int j = 0; j < UN; ++j) {
+      const int uu = u0 + 4 * j;
+      const bf16_t* xp = xs + c * KP + 64 * (uu < U ? uu : U - 1) + 16 * g;
+      b[j][0] = *reinterpret_cast<const uint4*>(xp);
+      b[j][1] = *reinterpret_cast<const uint4*>(xp + 8);
+    }
+    uint4 an[UN];
+    const bool more = u0 + 4 * UN < U;  // wave-uniform
+    if (more) load_a(u0 + 4 * UN, an);
+#pragma unroll
+    for (int j = 0; j < UN; ++j) {
+      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(q8frag(a[j].x, a[j].y), __builtin_bit_cast(bf16x8, b[j][0]), acc,
+                                                    0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(q8frag(a[j].z, a[j].w), __builtin_bit_cast(bf16x8, b[j][1]), acc,
+                                                    0, 0, 0);
+    }
+    if (more) {
+#pragma unroll
+      for (int j = 0; j < UN; ++j) a[j] = an[j];
+    }
+  }
+  skinny_q8_epilogue<ACT, OUTF>(acc, red, scale, bias, yv, M, N, n0);
+}
+
+}  // namespace
+
+// y[rows, N] = act((x[rows, K] Wq[N, K]^T) * scale[N] + b), rows <= 8, any N, K % 16 == 0;
+// Wq int8, scale fp32, x / b bf16; act: 0 none, 1 exact-erf GELU; out_f32: y is fp32.
+NSA_API hipError_t nsa_gemv_q8(const void* x, const void* Wq, const void* scale, const void* bias, void* y, int rows,
+                               int N, int K, int act, int out_f32, hipStream_t s) {
+  if (rows < 1 || rows > 8 || K % 16 || K < 16 || N < 1 || (act && out_f32)) return hipErrorInvalidValue;
+#define NSA_GEMVQ(MR)                                                                                         \
+  do {                                                                                                        \
+    const unsigned grid = (unsigned)((N + 7) / 8);                                                            \
+    if (act)                                                                                                  \
+      gemv_q8_kernel<MR, 1, false, 8, 4><<<grid, 256, 0, s>>>((const bf16_t*)x, (const int8_t*)Wq,             \
+                                                              (const float*)scale, (const bf16_t*)bias, y,    \
+                                                              rows, N, K);                                    \
+    else if (out_f32)                                                                                         \
+      gemv_q8_kernel<MR, 0, true, 8, 4><<<grid, 256, 0, s>>>((const bf16_t*)x, (const int8_t*)Wq,              \
+                                                             (const float*)scale, (const bf16_t*)bias, y,     \
+                                                             rows, N, K);                                     \
+    else                                                                                                      \
+      gemv_q8_kernel<MR, 0, false, 8, 4><<<grid, 256, 0, s>>>((const bf16_t*)x, (const int8_t*)Wq,             \
+                                                              (const float*)scale, (const bf16_t*)bias, y,    \
+                                                              rows, N, K);                                    \
+  } while (0)
+  if (rows == 1 && K <= 8192) {
+    // one row: 2 columns per wave set (narrow outputs need many small workgroups to keep
+    // enough weight bytes in flight), as the bf16 kernel's NSA_GEMV1_NC default
+    const Q8Cfg cfg = q8_cfg(K);
+    const unsigned g1 = (unsigned)((N + (4 / cfg.kw) * 2 - 1) / ((4 / cfg.kw) * 2));
+#define NSA_GEMV1Q(KW_, P_)                                                                                   \
+  do {                                                                                                        \
+    if (act)                                                                                                  \
+      gemv1_q8_kernel<1, false, 2, KW_, P_><<<g1, 256, 0, s>>>((const bf16_t*)x, (const int8_t*)Wq,            \
+                                                               (const float*)scale, (const bf16_t*)bias, y, N, \
+                                                               K);                                            \
+    else if (out_f32)                                                                                         \
+      gemv1_q8_kernel<0, true, 2, KW_, P_><<<g1, 256, 0, s>>>((const bf16_t*)x, (const int8_t*)Wq,             \
+                                                              (const float*)scale, (const bf16_t*)bias, y, N, \
+                                                              K);                                             \
+    else                                                                                                      \
+      gemv1_q8_kernel<0, false, 2, KW_, P_><<<g1, 256, 0, s>>>((const bf16_t*)x, (const int8_t*)Wq,            \
+                                                               (const float*)scale, (const bf16_t*)bias, y, N, \
+                                                               K);                                            \
+  } while (0)
+    if (cfg.kw == 1) NSA_GEMV1Q(1, 1);
+    else if (cfg.kw == 2) NSA_GEMV1Q(2, 1);
+    else if (cfg.p == 1) NSA_GEMV1Q(4, 1);
+    else NSA_GEMV1Q(4, 2);
+#undef NSA_GEMV1Q
+  } else if (rows == 1) NSA_GEMVQ(1);  // K > 8192: the K loop of the multi-row kernel
+  else if (rows == 2) NSA_GEMVQ(2);
+  else if (rows <= 4) NSA_GEMVQ(4);
+  else NSA_GEMVQ(8);
+#undef NSA_GEMVQ
+  return hipGetLastError();
+}
+
+// nsa_gemv_ln with int8 weights: K % 16 == 0, K <= 8192, any N
+NSA_API hipError_t nsa_gemv_ln_q8(const void* res, const void* branch, void* res_out, const void* lw, const void* lb,
+                                  const void* Wq, const void* scale, const void* bias, void* y, int N, int K,
+                                  float eps, int act, int out_f32, void* pos_inc, hipStream_t s) {
+  if (K % 16 || K < 16 || K > 8192 || N < 1 || (act && out_f32) || (branch && (!res_out || res_out == res)))
+    return hipErrorInvalidValue;
+  RowPro a{};
+  a.res = (const float*)res;
+  a.branch = (const bf16_t*)branch;
+  a.res_out = (float*)res_out;
+  a.lw = (const bf16_t*)lw;
+  a.lb = (const bf16_t*)lb;
+  a.eps = eps;
+  a.pos_inc = (int64_t*)pos_inc;
+  return launch_gemv_row_q8<PRO_LN>(a, Wq, scale, bias, y, N, K, act, out_f32, s);
+}
+
+// nsa_gemv_emb_ln with an int8 linear (the wte / wpe rows stay bf16)
+NSA_API hipError_t nsa_gemv_emb_ln_q8(const void* tok, const void* pos, const void* wte, const void* wpe,
+                                      void* res_out, const void* lw, const void* lb, const void* Wq, const void* scale,
+                                      const void* bias, void* y, int N, int K, float eps, int act, int out_f32,
+                                      hipStream_t s) {
+  if (K % 16 || K < 16 || K > 8192 || N < 1 || (act && out_f32) || !res_out) return hipErrorInvalidValue;
+  RowPro a{};
+  a.res_out = (float*)res_out;
+  a.lw = (const bf16_t*)lw;
+  a.lb = (const bf16_t*)lb;
+  a.eps = eps;
+  a.tok = (const int64_t*)tok;
+  a.pos = (const int64_t*)pos;
+  a.wte = (const bf16_t*)wte;
+  a.wpe = (const bf16_t*)wpe;
+  return launch_gemv_row_q8<PRO_EMB_LN>(a, Wq, scale, bias, y, N, K, act, out_f32, s);
+}
+
+// nsa_gemv_attn with int8 weights (K = H * 64: a multiple of 16)
+NSA_API hipError_t nsa_gemv_attn_q8(const void* ws, int n_split, const void* Wq, const void* scale, const void* bias,
+                                    void* y, int N, int K, int act, int out_f32, hipStream_t s) {
+  if (K % DA_D || K < DA_D || K > 8192 || N < 1 || n_split < 1 || (K / DA_D) * n_split > 16384 || (act && out_f32))
+    return hipErrorInvalidValue;
+  RowPro a{};
+  a.ws = (const float*)ws;
+  a.n_split = n_split;
+  return launch_gemv_row_q8<PRO_ATTN>(a, Wq, scale, bias, y, N, K, act, out_f32, s);
+}
+
+// y[rows, N] = act((x[rows, K] Wq[N, K]^T) * scale[N] + b) for 2 <= rows <= 16, any N, K % 64 == 0
+NSA_API hipError_t nsa_skinny_gemm_q8(const void* x, const void* Wq, const void* scale, const void* bias, void* y,
+                                      int rows, int N, int K, int act, int out_f32, hipStream_t s) {
+  if (rows < 1 || rows > 16 || K % 64 || K < 64 || N < 1 || (act && out_f32)) return hipErrorInvalidValue;
+  const unsigned grid = (unsigned)((N + 15) / 16);
+#define NSA_SKQ(A, F, UN_)                                                                                   \
+  skinny_gemm_q8_kernel<A, F, UN_><<<grid, 256, 0, s>>>((const bf16_t*)x, (const int8_t*)Wq, (const float*)scale, \
+                                                        (const bf16_t*)bias, y, rows, N, K)
+  // 4 units (1024 k over the workgroup) in flight per round up to K = 1024, 8 beyond
+  if (K <= 1024) {
+    if (act) NSA_SKQ(1, false, 4);
+    else if (out_f32) NSA_SKQ(0, true, 4);
+    else NSA_SKQ(0, false, 4);
+  } else {
+    if (act) NSA_SKQ(1, false, 8);
+    else if (out_f32) NSA_SKQ(0, true, 8);
+    else NSA_SKQ(0, false, 8);
+  }
+#undef NSA_SKQ
+  return hipGetLastError();
+}
+
+// nsa_skinny_ln_gemm with int8 weights: any N, K % 64 == 0, K <= 1920
+NSA_API hipError_t nsa_skinny_ln_gemm_q8(const void* res, const void* branch, void* s_out, const void* lw,
+                                         const void* lb, float eps, const void* Wq, const void* scale,
+                                         const void* bias, void* y, int rows, int N, int K, int act, int out_f32,
+                                         hipStream_t s) {
+  if (rows < 1 || rows > 16 || K % 64 || K < 64 || K > 1920 || N < 1 || (act && out_f32) || (branch && !s_out))
+    return hipErrorInvalidValue;
+  const unsigned grid = (unsigned)((N + 15) / 16);
+  const size_t lds = (size_t)16 * (K + 8) * sizeof(bf16_t);
+#define NSA_SKLNQ(A, F)                                                                                         \
+  skinny_ln_gemm_q8_kernel<A, F><<<grid, 256, lds, s>>>((const float*)res, (const bf16_t*)branch, (float*)s_out,   \
+                                                        (const bf16_t*)lw, (const bf16_t*)lb, eps,                 \
+                                                        (const int8_t*)Wq, (const float*)scale,                    \
+                                                        (const bf16_t*)bias, y, rows, N, K)
+  if (act) NSA_SKLNQ(1, false);
+  else if (out_f32) NSA_SKLNQ(0, true);
+  else NSA_SKLNQ(0, false);
+#undef NSA_SKLNQ
+  return hipGetLastError();
+}

@@ -258,8 +258,9 @@ class EmbeddingFn(torch.autograd.Function):
             _lib.call(name, _lib.ptr(idx),
                       _lib.ptr(wte_c), _lib.ptr(wpe_c), _lib.ptr(out), B * T, T, C, p, seed, _lib.stream())
             return out
-        # fp32 master weights, as nanoGPT's autocast leaves nn.Embedding in fp32
-        x = wte.detach().float()[idx] + wpe.detach().float()[:T].unsqueeze(0)
+        # fp32 master weights, as nanoGPT's autocast leaves nn.Embedding in fp32 (or an fp32
+        # ``compute`` shadow: a quantized Decoder's dequantized table)
+        x = compute_weight(wte, F32)[idx] + compute_weight(wpe, F32)[:T].unsqueeze(0)
         if p > 0:
             x = x * _cpu_keep_mask(x.shape, p, seed, x.device) / (1.0 - p)
         return x.to(dtype)
@@ -980,6 +981,42 @@ def decode_attention(qkv, kc, vc, pos, n_head: int, append: bool = False, combin
     return y.reshape(B, 1, C).to(qkv.dtype)
 
 
+class QuantWeight(NamedTuple):
+    """An int8 weight-only form of a linear's weight [N, K]: ``q`` int8 [N, K] (contiguous,
+    plain two's complement) and ``scale`` fp32 [N], one per output row; it stands for
+    ``dequantize(qw)``.  ``decode_linear``, ``decode_linear_ln`` and
+    ``decode_embed_linear_ln`` take one wherever they take ``w``."""
+    q: torch.Tensor
+    scale: torch.Tensor
+
+    @property
+    def shape(self):
+        return self.q.shape
+
+
+def quantize_rows_int8(w) -> QuantWeight:
+    """Per-output-row symmetric int8 of ``w`` [N, K], in fp32: scale[n] = absmax_n / 127 (1 for
+    an all-zero row), q[n, k] = clamp(round(w[n, k] / scale[n]), -127, 127).  Plain torch (CPU
+    or GPU); runs once per decoder."""
+    wf = w.detach().float()
+    absmax = wf.abs().amax(dim=1)
+    scale = torch.where(absmax > 0, absmax / 127, torch.ones_like(absmax))
+    q = torch.clamp(torch.round(wf / scale[:, None]), -127, 127).to(torch.int8).contiguous()
+    return QuantWeight(q, scale.contiguous())
+
+
+def dequantize(qw: QuantWeight) -> torch.Tensor:
+    """The fp32 weight a ``QuantWeight`` stands for: q * scale[:, None]."""
+    return qw.q.float() * qw.scale[:, None]
+
+
+def _stream_weight(w):
+    """(entry-point suffix, the tensors passed where the bf16 entry point takes W)."""
+    if isinstance(w, QuantWeight):
+        return "_q8", (w.q, w.scale)
+    return "", (compute_weight(w, BF16),)
+
+
 GEMV_MAX_ROWS = int(os.environ.get("NSA_GEMV_MAX_ROWS", "1"))
 # decode batches of 2..SKINNY_MAX_ROWS rows: the MFMA weight-streaming kernel (nsa_skinny_gemm).
 # HIP-graph decode, ms/token (GPT-2 124M / 1.5B): batch 8 0.685 / 4.24 with the library GEMM,
@@ -1003,33 +1040,42 @@ def decode_linear(x, w, b=None, gelu: bool = False, out_f32: bool = False):
     per token at 124M in round 2), so the default cap is 1 row (``NSA_GEMV_MAX_ROWS``) and
     batches of 2 .. ``NSA_SKINNY_MAX_ROWS`` (16) rows run on ``nsa_skinny_gemm`` (MFMA
     weight stream, bias / GELU epilogue) when N % 16 == 0 and K % 32 == 0; larger batches go
-    to ``linear`` (our small-tile / NT kernels: no library GEMM on this path)."""
+    to ``linear`` (our small-tile / NT kernels: no library GEMM on this path).
+
+    ``w`` may be a ``QuantWeight``: the same rules pick the ``_q8`` form of the same kernel
+    (K % 16 == 0 at one row, K % 64 == 0 and any N on the skinny kernel); whatever those do
+    not cover (CPU, fp32, other K, more rows) runs the rest of this function on
+    ``dequantize(w)`` in x's dtype: the reference semantics, and a slow path on the GPU."""
+    q8 = isinstance(w, QuantWeight)
     N = w.shape[0]
     if isinstance(x, AttnPartials):  # one row; the attention combine runs in the GEMV prologue
         y = torch.empty(N, device=x.ws.device, dtype=F32 if out_f32 else BF16)
-        _lib.call("nsa_gemv_attn", _lib.ptr(x.ws), x.n_split, _lib.ptr(compute_weight(w, BF16)),
+        sfx, wt = _stream_weight(w)
+        _lib.call("nsa_gemv_attn" + sfx, _lib.ptr(x.ws), x.n_split, *map(_lib.ptr, wt),
                   _lib.ptr(compute_weight(b, BF16) if b is not None else None), _lib.ptr(y), N, x.C,
                   1 if gelu else 0, 1 if out_f32 else 0, _lib.stream())
         return y.view(1, 1, N)
     K = x.shape[-1]
     rows = x.numel() // K
-    if x.is_cuda and x.dtype == BF16 and rows <= GEMV_MAX_ROWS and K % 8 == 0:
+    if x.is_cuda and x.dtype == BF16 and rows <= GEMV_MAX_ROWS and K % (16 if q8 else 8) == 0:
         x2 = x.reshape(rows, K).contiguous()
-        wc = compute_weight(w, BF16)
+        sfx, wt = _stream_weight(w)
         bc = compute_weight(b, BF16) if b is not None else None
         y = torch.empty(rows, N, device=x.device, dtype=F32 if out_f32 else BF16)
-        _lib.call("nsa_gemv", _lib.ptr(x2), _lib.ptr(wc), _lib.ptr(bc), _lib.ptr(y), rows, N, K, 1 if gelu else 0,
-                  1 if out_f32 else 0, _lib.stream())
-        return y.view(*x.shape[:-1], N)
-    if (x.is_cuda and x.dtype == BF16 and 2 <= rows <= SKINNY_MAX_ROWS and K % 32 == 0 and N % 16 == 0
-            and not (gelu and out_f32)):
-        x2 = x.reshape(rows, K).contiguous()
-        wc = compute_weight(w, BF16)
-        bc = compute_weight(b, BF16) if b is not None else None
-        y = torch.empty(rows, N, device=x.device, dtype=F32 if out_f32 else BF16)
-        _lib.call("nsa_skinny_gemm", _lib.ptr(x2), _lib.ptr(wc), _lib.ptr(bc), _lib.ptr(y), rows, N, K,
+        _lib.call("nsa_gemv" + sfx, _lib.ptr(x2), *map(_lib.ptr, wt), _lib.ptr(bc), _lib.ptr(y), rows, N, K,
                   1 if gelu else 0, 1 if out_f32 else 0, _lib.stream())
         return y.view(*x.shape[:-1], N)
+    if (x.is_cuda and x.dtype == BF16 and 2 <= rows <= SKINNY_MAX_ROWS and K % (64 if q8 else 32) == 0
+            and (q8 or N % 16 == 0) and not (gelu and out_f32)):
+        x2 = x.reshape(rows, K).contiguous()
+        sfx, wt = _stream_weight(w)
+        bc = compute_weight(b, BF16) if b is not None else None
+        y = torch.empty(rows, N, device=x.device, dtype=F32 if out_f32 else BF16)
+        _lib.call("nsa_skinny_gemm" + sfx, _lib.ptr(x2), *map(_lib.ptr, wt), _lib.ptr(bc), _lib.ptr(y), rows, N, K,
+                  1 if gelu else 0, 1 if out_f32 else 0, _lib.stream())
+        return y.view(*x.shape[:-1], N)
+    if q8:
+        w = dequantize(w).to(x.dtype)
     y = linear(x, w, b)
     if gelu:
         y = GeluFn.apply(y)
@@ -1045,38 +1091,39 @@ def decode_linear_ln(res, branch, ln_w, ln_b, w, b=None, gelu: bool = False, out
     + ``decode_linear`` (``out_dtype``: the LayerNorm output dtype there).  ``pos_inc``: an
     int64 device tensor incremented by one after the row (inside the kernel on the fused
     path: the decode step's position update without its own launch).  Inference only."""
+    q8 = isinstance(w, QuantWeight)  # the _q8 form of the same kernel; else decode_linear's fallback
     C = res.shape[-1]
     rows = res.numel() // C
-    if (res.is_cuda and res.dtype == F32 and rows == 1 and GEMV_MAX_ROWS >= 1 and C % 8 == 0 and C <= 8192
-            and (branch is None or branch.dtype == BF16)):
+    if (res.is_cuda and res.dtype == F32 and rows == 1 and GEMV_MAX_ROWS >= 1 and C % (16 if q8 else 8) == 0
+            and C <= 8192 and (branch is None or branch.dtype == BF16)):
         N = w.shape[0]
         r2 = res.reshape(C).contiguous()
         br = branch.reshape(C).contiguous() if branch is not None else None
         s_out = torch.empty_like(r2) if branch is not None else None
         lw, lb = compute_weight(ln_w, BF16), compute_weight(ln_b, BF16) if ln_b is not None else None
-        wc = compute_weight(w, BF16)
+        sfx, wt = _stream_weight(w)
         bc = compute_weight(b, BF16) if b is not None else None
         y = torch.empty(N, device=res.device, dtype=F32 if out_f32 else BF16)
-        _lib.call("nsa_gemv_ln", _lib.ptr(r2), _lib.ptr(br), _lib.ptr(s_out), _lib.ptr(lw), _lib.ptr(lb), _lib.ptr(wc),
-                  _lib.ptr(bc), _lib.ptr(y), N, C, LN_EPS, 1 if gelu else 0, 1 if out_f32 else 0, _lib.ptr(pos_inc),
-                  _lib.stream())
+        _lib.call("nsa_gemv_ln" + sfx, _lib.ptr(r2), _lib.ptr(br), _lib.ptr(s_out), _lib.ptr(lw), _lib.ptr(lb),
+                  *map(_lib.ptr, wt), _lib.ptr(bc), _lib.ptr(y), N, C, LN_EPS, 1 if gelu else 0,
+                  1 if out_f32 else 0, _lib.ptr(pos_inc), _lib.stream())
         s_new = s_out.view(res.shape) if branch is not None else res
         return s_new, y.view(*res.shape[:-1], N)
     N = w.shape[0]
-    if (res.is_cuda and res.dtype == F32 and 2 <= rows <= min(SKINNY_MAX_ROWS, SKINNY_LN_MAX_ROWS) and C % 32 == 0
-            and C <= 1920
-            and N % 16 == 0 and not (gelu and out_f32) and (branch is None or branch.dtype == BF16)
+    if (res.is_cuda and res.dtype == F32 and 2 <= rows <= min(SKINNY_MAX_ROWS, SKINNY_LN_MAX_ROWS)
+            and C % (64 if q8 else 32) == 0 and C <= 1920
+            and (q8 or N % 16 == 0) and not (gelu and out_f32) and (branch is None or branch.dtype == BF16)
             and out_dtype in (None, BF16)):
         # 2..16 rows: residual add + LayerNorm recomputed per workgroup in the skinny GEMM's prologue
         r2 = res.reshape(rows, C).contiguous()
         br = branch.reshape(rows, C).contiguous() if branch is not None else None
         s_out = torch.empty_like(r2) if branch is not None else None
         lw, lb = compute_weight(ln_w, BF16), compute_weight(ln_b, BF16) if ln_b is not None else None
-        wc = compute_weight(w, BF16)
+        sfx, wt = _stream_weight(w)
         bc = compute_weight(b, BF16) if b is not None else None
         y = torch.empty(rows, N, device=res.device, dtype=F32 if out_f32 else BF16)
-        _lib.call("nsa_skinny_ln_gemm", _lib.ptr(r2), _lib.ptr(br), _lib.ptr(s_out), _lib.ptr(lw), _lib.ptr(lb),
-                  LN_EPS, _lib.ptr(wc), _lib.ptr(bc), _lib.ptr(y), rows, N, C, 1 if gelu else 0,
+        _lib.call("nsa_skinny_ln_gemm" + sfx, _lib.ptr(r2), _lib.ptr(br), _lib.ptr(s_out), _lib.ptr(lw), _lib.ptr(lb),
+                  LN_EPS, *map(_lib.ptr, wt), _lib.ptr(bc), _lib.ptr(y), rows, N, C, 1 if gelu else 0,
                   1 if out_f32 else 0, _lib.stream())
         if pos_inc is not None:
             pos_inc.add_(1)
@@ -1100,16 +1147,17 @@ def decode_embed_linear_ln(tok, pos, wte, wpe, ln_w, ln_b, w, b=None, dtype=BF16
     B = tok.numel()
     C = wte.shape[1]
     wte_c, wpe_c = compute_weight(wte, dtype), compute_weight(wpe, dtype)
-    if (tok.is_cuda and B == 1 and dtype == BF16 and res_dtype == F32 and GEMV_MAX_ROWS >= 1 and C % 8 == 0
-            and C <= 8192):
+    q8 = isinstance(w, QuantWeight)
+    if (tok.is_cuda and B == 1 and dtype == BF16 and res_dtype == F32 and GEMV_MAX_ROWS >= 1
+            and C % (16 if q8 else 8) == 0 and C <= 8192):
         N = w.shape[0]
         x = torch.empty(1, 1, C, device=tok.device, dtype=F32)
         y = torch.empty(N, device=tok.device, dtype=BF16)
         lw, lb = compute_weight(ln_w, BF16), compute_weight(ln_b, BF16) if ln_b is not None else None
-        wc = compute_weight(w, BF16)
+        sfx, wt = _stream_weight(w)
         bc = compute_weight(b, BF16) if b is not None else None
-        _lib.call("nsa_gemv_emb_ln", _lib.ptr(tok), _lib.ptr(pos), _lib.ptr(wte_c), _lib.ptr(wpe_c), _lib.ptr(x),
-                  _lib.ptr(lw), _lib.ptr(lb), _lib.ptr(wc), _lib.ptr(bc), _lib.ptr(y), N, C, LN_EPS, 0, 0,
+        _lib.call("nsa_gemv_emb_ln" + sfx, _lib.ptr(tok), _lib.ptr(pos), _lib.ptr(wte_c), _lib.ptr(wpe_c), _lib.ptr(x),
+                  _lib.ptr(lw), _lib.ptr(lb), *map(_lib.ptr, wt), _lib.ptr(bc), _lib.ptr(y), N, C, LN_EPS, 0, 0,
                   _lib.stream())
         return x, y.view(1, 1, N)
     x = wte_c.index_select(0, tok.view(-1)).float() + wpe_c.index_select(0, pos.view(-1)).float()

@@ -33,6 +33,12 @@ kernels read ``pos[b]``, and a row that draws the stop token is frozen inside th
 captured step: its position stops, it is fed the same token again (rewriting the same
 cache row with the same values) and it draws nothing.  ``generate_batch`` is the
 list-of-prompts front end.
+``Decoder(..., quantize="int8")`` decodes the model whose linear weights (c_attn, both
+c_proj, c_fc and the tied lm_head / wte) are the per-row int8 quantization of the
+model's (``ops.quantize_rows_int8``): every step streams int8 weights through the
+``_q8`` forms of the same kernels (half the bytes, the same launches, the same captured
+graph), and prefill and the embedding read the dequantized weights through the
+``compute`` shadows, so prompt and steps see one model.
 The caches hold at most ``block_size`` positions; ``GPT.generate_cached`` falls
 back to the recompute loop when prompt + new tokens exceed that (nanoGPT crops the
 context there, which a cache cannot do without re-encoding).
@@ -47,10 +53,22 @@ from .. import ops
 
 class Decoder:
     def __init__(self, model, batch_size: int, max_len: int | None = None, use_graph: bool | None = None,
-                 per_row: bool = False):
+                 per_row: bool = False, quantize: str | None = None):
+        if quantize not in (None, "int8"):
+            raise ValueError(f"quantize must be None or 'int8', got {quantize!r}")
         self.model = model
         self.per_row = per_row
+        self.quantize = quantize
         cfg = model.config
+        if quantize and model.lm_head.weight.is_cuda:
+            # the int8 kernels are the single-row and skinny ones; there is no int8 form of the
+            # larger-batch GEMMs or of the fallback ops, and no silent bf16 step instead
+            if batch_size > ops.functional.SKINNY_MAX_ROWS:
+                raise ValueError(f"quantize='int8' decodes at most {ops.functional.SKINNY_MAX_ROWS} rows on the GPU "
+                                 f"(the skinny int8 kernels), got batch size {batch_size}")
+            if not self.graph_capable(model):
+                raise ValueError("quantize='int8' needs the fused decode kernels on the GPU: head_dim 64, "
+                                 "bfloat16 compute and a vocabulary of at most 53248")
         self.B = batch_size
         self.T = max_len or cfg.block_size
         assert self.T <= cfg.block_size, "caches cannot exceed the position-embedding table"
@@ -90,6 +108,10 @@ class Decoder:
         # fp32 weight on every use (124M: ~750 MB of conversion traffic per token, and
         # inside the captured graph too).  Created here, dropped by ``release()``.
         self._shadowed = []
+        self.qweights = {}   # int8 mode: id(parameter) -> ops.QuantWeight
+        self._qsaved = []    # (parameter, attribute, had it, value) to put back in release()
+        if quantize:
+            self._quantize_weights()
         if self.dtype != torch.float32:
             for prm in model.parameters():
                 c = getattr(prm, "compute", None)
@@ -103,6 +125,35 @@ class Decoder:
         return (cfg.n_embd // cfg.n_head == 64 and model.compute_dtype == torch.bfloat16
                 and cfg.vocab_size <= 53248)
 
+    def _quantize_weights(self):
+        """int8 mode: quantize every linear weight and the tied lm_head / wte table, and point
+        their ``compute`` shadows (what prefill and the embedding gather read) at the
+        dequantized weights in the compute dtype (fp32 on the CPU included), so the prompt
+        runs through the same model as the int8 steps.  Whatever ``compute`` a parameter had
+        (a trained model's optimizer shadow) is kept for ``release()``."""
+        model = self.model
+        params = []
+        for block in model.transformer.h:
+            params += [block.attn.c_attn.weight, block.attn.c_proj.weight, block.mlp.c_fc.weight,
+                       block.mlp.c_proj.weight]
+        head = model.lm_head.weight  # tied to wte: the token embeddings are the dequantized rows too
+        params.append(head)
+        for prm in params:
+            qw = ops.quantize_rows_int8(prm)
+            self.qweights[id(prm)] = qw
+            self._qsaved.append((prm, "compute", hasattr(prm, "compute"), getattr(prm, "compute", None)))
+            prm.compute = ops.dequantize(qw).to(self.dtype)
+        # the padded lm_head operand of a flat parameter store holds the unquantized weights
+        if hasattr(head, "compute_padded"):
+            self._qsaved.append((head, "compute_padded", True, head.compute_padded))
+            del head.compute_padded
+        # copies derived from the earlier shadows (the padded lm_head operand) are stale
+        ops.gemm_dispatch.weights_changed()
+
+    def _w(self, prm):
+        """The weight a decode op streams: the parameter, or its QuantWeight in int8 mode."""
+        return self.qweights.get(id(prm), prm)
+
     def release(self):
         """Drop the weight shadows this decoder created and its captured graph."""
         for prm in self._shadowed:
@@ -111,6 +162,15 @@ class Decoder:
             except AttributeError:
                 pass
         self._shadowed = []
+        for prm, name, had, old in self._qsaved:  # int8 mode: the shadows that were there before
+            if had:
+                setattr(prm, name, old)
+            elif hasattr(prm, name):
+                delattr(prm, name)
+        if self._qsaved:
+            ops.gemm_dispatch.weights_changed()
+        self._qsaved = []
+        self.qweights = {}
         self.graph = None
         self.sgraphs = {}
 
@@ -143,24 +203,25 @@ class Decoder:
         rides in the attention kernel and bias / GELU in the GEMV epilogues: 5 launches
         per layer."""
         tr = self.model.transformer
+        W = self._w  # int8 mode: the QuantWeight of a linear's weight
         branch = None  # the previous sublayer's output, not yet added to the residual x
         for i, block in enumerate(tr.h):
             attn, mlp = block.attn, block.mlp
             ln1, ln2 = block.ln_1, block.ln_2
             if i == 0:
                 x, qkv = ops.decode_embed_linear_ln(self.tok, self.pos, tr.wte.weight, tr.wpe.weight, ln1.weight,
-                                                    ln1.bias, attn.c_attn.weight, attn.c_attn.bias, dtype=self.dtype,
+                                                    ln1.bias, W(attn.c_attn.weight), attn.c_attn.bias, dtype=self.dtype,
                                                     res_dtype=self.rdtype, out_dtype=ln1.out_dtype)
             else:
-                x, qkv = ops.decode_linear_ln(x, branch, ln1.weight, ln1.bias, attn.c_attn.weight, attn.c_attn.bias,
+                x, qkv = ops.decode_linear_ln(x, branch, ln1.weight, ln1.bias, W(attn.c_attn.weight), attn.c_attn.bias,
                                               out_dtype=ln1.out_dtype)
             y = ops.decode_attention(qkv, self.kc[i], self.vc[i], self.pos, attn.n_head, append=True, combine=False)
-            y = ops.decode_linear(y, attn.c_proj.weight, attn.c_proj.bias)
-            x, u = ops.decode_linear_ln(x, y, ln2.weight, ln2.bias, mlp.c_fc.weight, mlp.c_fc.bias, gelu=True,
+            y = ops.decode_linear(y, W(attn.c_proj.weight), attn.c_proj.bias)
+            x, u = ops.decode_linear_ln(x, y, ln2.weight, ln2.bias, W(mlp.c_fc.weight), mlp.c_fc.bias, gelu=True,
                                         out_dtype=ln2.out_dtype)
-            branch = ops.decode_linear(u, mlp.c_proj.weight, mlp.c_proj.bias)
+            branch = ops.decode_linear(u, W(mlp.c_proj.weight), mlp.c_proj.bias)
         lnf = tr.ln_f
-        _, logits = ops.decode_linear_ln(x, branch, lnf.weight, lnf.bias, self.model.lm_head.weight, None,
+        _, logits = ops.decode_linear_ln(x, branch, lnf.weight, lnf.bias, W(self.model.lm_head.weight), None,
                                          out_f32=True, out_dtype=lnf.out_dtype,
                                          pos_inc=None if self.per_row else self.pos)
         if self.per_row:
@@ -334,8 +395,11 @@ def sample_next(logits: torch.Tensor, temperature: float = 1.0, top_k: int | Non
 def generate_cached(model, idx: torch.Tensor, max_new_tokens: int, temperature: float = 1.0,
                     top_k: int | None = None, use_graph: bool | None = None,
                     decoder: "Decoder | None" = None, top_p: float | None = None,
-                    min_p: float | None = None) -> torch.Tensor:
+                    min_p: float | None = None, quantize: str | None = None) -> torch.Tensor:
     """``model.generate`` with KV caches: same sampling, one token's forward per new token.
+
+    ``quantize="int8"``: decode with int8 weights (``Decoder(..., quantize="int8")``); the
+    recompute fallback cannot, so a prompt + new tokens past block_size raises ValueError.
 
     ``decoder``: a Decoder to reuse across calls (same batch size): its weight shadows and
     captured graphs survive, so ``sample.py``'s num_samples loop captures once.  The caller
@@ -344,11 +408,17 @@ def generate_cached(model, idx: torch.Tensor, max_new_tokens: int, temperature: 
     top_p, min_p = sampling_filters(top_p, min_p)
     if max_new_tokens <= 0:
         return idx
+    if quantize not in (None, "int8"):
+        raise ValueError(f"quantize must be None or 'int8', got {quantize!r}")
     if T0 + max_new_tokens - 1 > model.config.block_size:
+        if quantize:
+            raise ValueError("quantize needs the KV-cache path: prompt + new tokens exceed block_size, and the "
+                             "recompute loop runs the unquantized model")
         # the caches hold block_size positions; nanoGPT crops the context beyond that
         return model.generate(idx, max_new_tokens, temperature=temperature, top_k=top_k, top_p=top_p, min_p=min_p)
-    own = decoder is None or decoder.B != B
-    dec = Decoder(model, B, max_len=model.config.block_size, use_graph=use_graph) if own else decoder
+    own = decoder is None or decoder.B != B or decoder.quantize != quantize
+    dec = (Decoder(model, B, max_len=model.config.block_size, use_graph=use_graph, quantize=quantize) if own
+           else decoder)
     try:
         dec.reseed()  # every call draws its own samples, also on a reused decoder / graph
         dec.sample_into(dec.prefill(idx), temperature, top_k, None, top_p, min_p)  # pos = T0: gen[:, T0]
@@ -371,7 +441,7 @@ def _cut_at_stop(new: torch.Tensor, stop_token: int | None) -> torch.Tensor:
 def generate_batch(model, prompts, max_new_tokens: int, temperature: float = 1.0, top_k: int | None = None,
                    stop_token: int | None = None, use_graph: bool | None = None,
                    decoder: "Decoder | None" = None, top_p: float | None = None,
-                   min_p: float | None = None) -> list[torch.Tensor]:
+                   min_p: float | None = None, quantize: str | None = None) -> list[torch.Tensor]:
     """Generate for a list of prompts of unequal lengths as one batch.
 
     ``prompts``: 1-D token tensors, each of length >= 1.  Every result is its prompt followed
@@ -383,7 +453,10 @@ def generate_batch(model, prompts, max_new_tokens: int, temperature: float = 1.0
     ``generate_cached`` on its own (the recompute loop) and is cut at the stop token.
 
     ``decoder``: a per_row Decoder of the right batch size to reuse across calls (weight
-    shadows and captured graphs survive); the caller releases it."""
+    shadows and captured graphs survive); the caller releases it.  ``quantize="int8"``:
+    int8 weights; a row that needs the recompute loop then raises ValueError."""
+    if quantize not in (None, "int8"):
+        raise ValueError(f"quantize must be None or 'int8', got {quantize!r}")
     if stop_token is not None and stop_token < 0:
         stop_token = None
     top_p, min_p = sampling_filters(top_p, min_p)
@@ -398,7 +471,7 @@ def generate_batch(model, prompts, max_new_tokens: int, temperature: float = 1.0
     for i, p in enumerate(prompts):
         if i not in rows:
             y = generate_cached(model, p.to(device)[None], max_new_tokens, temperature=temperature, top_k=top_k,
-                                use_graph=use_graph, top_p=top_p, min_p=min_p)[0]
+                                use_graph=use_graph, top_p=top_p, min_p=min_p, quantize=quantize)[0]
             outs[i] = torch.cat([y[:p.numel()], _cut_at_stop(y[p.numel():], stop_token)])
     if not rows:
         return outs
@@ -407,8 +480,8 @@ def generate_batch(model, prompts, max_new_tokens: int, temperature: float = 1.0
     idx = torch.zeros(B, max(lens), dtype=torch.int64, device=device)  # right-padded (any valid id)
     for b, i in enumerate(rows):
         idx[b, :lens[b]] = prompts[i]
-    own = decoder is None or decoder.B != B or not decoder.per_row
-    dec = Decoder(model, B, max_len=T, use_graph=use_graph, per_row=True) if own else decoder
+    own = decoder is None or decoder.B != B or not decoder.per_row or decoder.quantize != quantize
+    dec = Decoder(model, B, max_len=T, use_graph=use_graph, per_row=True, quantize=quantize) if own else decoder
     try:
         dec.reseed()
         logits = dec.prefill(idx, torch.tensor(lens, dtype=torch.int64, device=device))

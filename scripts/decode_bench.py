@@ -15,6 +15,8 @@ position per sequence at equal prompt lengths (what the per-row step costs besid
 the whole mode list N times, interleaved, for the run-to-run spread.  ``--samples N``
 times sample.py's flow for N samples of one prompt: a reused batch-1 decoder N times over
 (``sample_loop``) against one ``generate_batch`` of N rows (``sample_batch``).
+``--quantize int8`` adds ``graph_int8`` / ``rows_int8``, the ``graph`` / ``rows`` modes on a
+``Decoder(quantize="int8")``, next to their bf16 twins in the interleaved mode list.
 """
 
 import argparse
@@ -33,9 +35,9 @@ SMP = dict(top_k=200, top_p=None, min_p=None)  # the sampling settings of every 
 DIMS = {"gpt2": (12, 12, 768), "gpt2-medium": (24, 16, 1024), "gpt2-large": (36, 20, 1280), "gpt2-xl": (48, 25, 1600)}
 
 
-def run_cached(model, idx, new, use_graph):
+def run_cached(model, idx, new, use_graph, quantize=None):
     B = idx.shape[0]
-    dec = Decoder(model, B, use_graph=use_graph)
+    dec = Decoder(model, B, use_graph=use_graph, quantize=quantize)
     dec.sample_into(dec.prefill(idx), 0.8, **SMP)
     if use_graph:
         dec.run(1, 0.8, **SMP)  # capture outside the timed loop
@@ -58,10 +60,10 @@ def ragged_lengths(B, prompt):
     return [prompt if B == 1 else lo + (prompt - lo) * b // (B - 1) for b in range(B)]
 
 
-def run_rows(model, idx, new, lengths=None):
+def run_rows(model, idx, new, lengths=None, quantize=None):
     """The graph mode on a per_row decoder: equal lengths, or (lengths) a ragged batch."""
     B = idx.shape[0]
-    dec = Decoder(model, B, use_graph=True, per_row=True)
+    dec = Decoder(model, B, use_graph=True, per_row=True, quantize=quantize)
     lens = None if lengths is None else torch.tensor(lengths, device=idx.device)
     dec.sample_into(dec.prefill(idx, lens), 0.8, **SMP)
     dec.run(1, 0.8, **SMP)  # capture outside the timed loop
@@ -112,6 +114,8 @@ def main():
     ap.add_argument("--repeat", type=int, default=1, help="run the mode list this many times (interleaved)")
     ap.add_argument("--samples", type=int, default=0, help="also time N samples of one prompt: loop vs one batch")
     ap.add_argument("--calibrate", action="store_true", help="first print the box calibration GEMM (utils/boxcal.py)")
+    ap.add_argument("--quantize", default="", choices=["", "int8"],
+                    help="int8: add int8 weight-only twins of the graph and rows modes (graph_int8, rows_int8)")
     ap.add_argument("--top_k", type=int, default=200, help="0: no top-k")
     ap.add_argument("--top_p", type=float, default=1.0, help="nucleus mass; 1.0: off")
     ap.add_argument("--min_p", type=float, default=0.0, help="floor relative to the most likely token; 0.0: off")
@@ -123,7 +127,10 @@ def main():
         from nanosandbox_amd.utils.boxcal import calibration_gemm
         print(json.dumps({"calibration_gemm": calibration_gemm()}), flush=True)
     modes = a.modes.split(",") + (["ragged"] if a.ragged else [])
-    modes = [m for m in modes if m] * a.repeat
+    modes = [m for m in modes if m]
+    if a.quantize:  # each int8 twin right after its bf16 mode
+        modes = [t for m in modes for t in ([m, f"{m}_{a.quantize}"] if m in ("graph", "rows") else [m])]
+    modes = modes * a.repeat
     for name in a.models.split(","):
         L, H, C = DIMS[name]
         torch.manual_seed(0)
@@ -133,19 +140,21 @@ def main():
             idx = torch.randint(0, 50257, (B, a.prompt), device="cuda")
             with torch.no_grad():
                 for mode in modes:
-                    if mode in ("rows", "ragged"):
+                    base, _, qz = mode.partition("_")  # graph_int8 -> (graph, int8)
+                    qz = qz or None
+                    if base in ("rows", "ragged"):
                         n = a.new
-                        lens = ragged_lengths(B, a.prompt) if mode == "ragged" else None
-                        run_rows(model, idx, 4, lens)
-                        dt = run_rows(model, idx, n, lens)
+                        lens = ragged_lengths(B, a.prompt) if base == "ragged" else None
+                        run_rows(model, idx, 4, lens, qz)
+                        dt = run_rows(model, idx, n, lens, qz)
                     elif mode == "recompute":
                         run_recompute(model, idx, 2)  # warm-up (tuner, allocator)
                         n = a.recompute_new
                         dt = run_recompute(model, idx, n)
                     else:
                         n = a.new
-                        run_cached(model, idx, 4, mode == "graph")
-                        dt = run_cached(model, idx, n, mode == "graph")
+                        run_cached(model, idx, 4, base == "graph", qz)
+                        dt = run_cached(model, idx, n, base == "graph", qz)
                     print(json.dumps({"model": name, "batch": B, "mode": mode, "prompt": a.prompt, "new_tokens": n,
                                       "tokens_per_s": round(B * n / dt, 1), "ms_per_token": round(dt / n * 1e3, 3),
                                       **extra}),
