@@ -16,7 +16,7 @@
 // (m, l, o[64]) to a workspace; a combine kernel rescales the chunks to the global
 // max.  Chunks past `pos` write an empty partial (m = -inf) and exit, so the grid is
 // fixed by Tmax (graph-safe) while the work follows the live context length.
-#include "common.h"
+#include "decode_rows.h"
 
 #include <math.h>
 #include <stdlib.h>
@@ -25,10 +25,7 @@
 
 namespace {
 
-constexpr int DA_D = 64;        // head dim of the decode-attention kernel
 constexpr int DA_CHUNK = 256;   // keys per workgroup (one per thread)
-constexpr int DA_PO = 4;          // o[] offset in a partial: 16-byte aligned for vector reads
-constexpr int DA_PART = DA_PO + DA_D;  // m, l, (pad), o[64]
 
 __global__ __launch_bounds__(256) void kv_append_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ kc,
                                                         bf16_t* __restrict__ vc, const int64_t* __restrict__ pos_dev,
@@ -52,17 +49,6 @@ __global__ __launch_bounds__(256) void kv_append_kernel(const bf16_t* __restrict
   const bf16_t* src = qkv + ((int64_t)b * S + s) * 3 * C + (1 + kv) * C + hh * D + c * 8;
   bf16_t* dst = (kv ? vc : kc) + (((int64_t)b * H + hh) * Tmax + p) * D + c * 8;
   *reinterpret_cast<uint4*>(dst) = *reinterpret_cast<const uint4*>(src);
-}
-
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-  return v;
-}
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
 }
 
 // grid (B*H, n_split), 256 threads; pos_dev[b * pos_stride] is row b's position
@@ -1001,33 +987,6 @@ __global__ void pos_advance_kernel(int64_t* __restrict__ pos, const int64_t* __r
 // dot products, a butterfly (halve-and-exchange) shuffle reduction leaves each lane
 // with one (column, row) total over the wave, and the 4 waves meet in LDS.
 // ---------------------------------------------------------------------------
-template <int M, int V>
-__device__ __forceinline__ float wave_reduce_multi(float (&v)[V], int lane, int& index) {
-  // V values per lane -> lane holds the wave-wide sum of value `index`
-  int cnt = V;
-  index = 0;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    if (cnt > 1) {
-      const bool upper = (lane & off) != 0;
-      const int h = cnt / 2;
-#pragma unroll
-      for (int i = 0; i < V / 2; ++i) {
-        if (i < h) {
-          const float send = upper ? v[i] : v[i + h];
-          const float keep = upper ? v[i + h] : v[i];
-          v[i] = keep + __shfl_xor(send, off, 64);
-        }
-      }
-      if (upper) index += h;
-      cnt = h;
-    } else {
-      v[0] += __shfl_xor(v[0], off, 64);
-    }
-  }
-  return v[0];
-}
-
 template <int M, int ACT, bool OUTF, int NC = 8>
 __global__ __launch_bounds__(256) void gemv_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ W,
                                                    const bf16_t* __restrict__ bias, void* __restrict__ y, int rows,
@@ -1062,7 +1021,7 @@ __global__ __launch_bounds__(256) void gemv_kernel(const bf16_t* __restrict__ x,
     }
   }
   int idx;
-  const float v = wave_reduce_multi<M, V>(acc, lane, idx);
+  const float v = wave_reduce_multi<V>(acc, lane, idx);
   // lanes below the last split's offset hold duplicates: the first of each group writes
   constexpr int DUP = 64 / V;  // lanes per value
   if ((lane & (DUP - 1)) == 0) red[w][idx] = v;
@@ -1081,35 +1040,8 @@ __global__ __launch_bounds__(256) void gemv_kernel(const bf16_t* __restrict__ x,
   }
 }
 
-// Single-row decode linear with its input's producer in the prologue: every workgroup
-// builds the row x[K] (bf16-rounded, in LDS) itself, then streams its NC weight rows:
-//   PRO_LN     s = res + branch (fp32; written to res_out by workgroup 0), x = LN(s)
-//   PRO_EMB_LN s = wte[*tok] + wpe[*pos] (written to res_out by workgroup 0), x = LN(s)
-//   PRO_ATTN   x = the flash-decoding combine of the attention partials (ws, H heads)
-//   y = act(x W^T + bias)
-// The recomputation is cheap (K <= 8192 values, L2-resident) and removes the separate
-// add+LayerNorm / combine / embedding launch per linear: at batch 1 each launch costs a
-// few microseconds of fixed overhead against ~1-10 us of weight streaming.  The first
-// K piece of the weights is loaded before the prologue, so its latency overlaps it.
-// res_out must not alias res.
-enum { PRO_LN = 0, PRO_ATTN = 1, PRO_EMB_LN = 2 };
-
-struct RowPro {
-  const float* res;
-  const bf16_t* branch;
-  float* res_out;
-  const bf16_t* lw;
-  const bf16_t* lb;
-  float eps;
-  const float* ws;
-  int n_split;
-  const int64_t* tok;
-  const int64_t* pos;
-  const bf16_t* wte;
-  const bf16_t* wpe;
-  int64_t* pos_inc;  // PRO_LN: incremented by one thread after the row (the decode step's position)
-};
-
+// Single-row decode linear with its input's producer in the prologue (decode_rows.h: PRO_*,
+// RowPro): the row x[K] is built in LDS by decode_row_prologue.h, k-contiguous.
 template <int PRO, int ACT, bool OUTF, int NC>
 __global__ __launch_bounds__(256) void gemv_row_kernel(const RowPro a, const bf16_t* __restrict__ W,
                                                        const bf16_t* __restrict__ bias, void* __restrict__ y, int N,
@@ -1127,135 +1059,10 @@ __global__ __launch_bounds__(256) void gemv_row_kernel(const RowPro a, const bf1
     for (int c = 0; c < NC; ++c)
       wp[c] = *reinterpret_cast<const uint4*>(W + (int64_t)min(cb * NC + c, N - 1) * K + 8 * g0);
   }
-  // Prologue.  K <= 2048 (every GPT-2 width): thread g owns x[8g .. 8g+7] and issues all
-  // of its loads at once (16-byte vectors), so the row costs one memory round trip and
-  // two block reductions; wider rows loop.
-  const bool vec = K <= 2048;
-  const int g8 = 8 * tid;
-  const bool own = vec && g8 < K;
-  if constexpr (PRO == PRO_ATTN) {
-    const int H = K / DA_D, ns = a.n_split;
-    float* fs = hs + K;  // [H][ns] chunk weights 2^(m_s - M) / L
-    for (int h = tid; h < H; h += 256) {
-      const float* part = a.ws + (int64_t)h * ns * DA_PART;
-      float M = -INFINITY;
-#pragma unroll 4
-      for (int sp = 0; sp < ns; ++sp) M = fmaxf(M, part[sp * DA_PART]);
-      float L = 0.0f;
-#pragma unroll 4
-      for (int sp = 0; sp < ns; ++sp) L = fmaf(exp2f(part[sp * DA_PART] - M), part[sp * DA_PART + 1], L);
-      const float inv = 1.0f / L;
-      for (int sp = 0; sp < ns; ++sp) fs[h * ns + sp] = exp2f(part[sp * DA_PART] - M) * inv;  // empty: 0
-    }
-    __syncthreads();
-    for (int k0 = g8; k0 < K; k0 += 8 * 256) {  // 8 dims of one head per thread and pass
-      const int h = k0 / DA_D;
-      const float* o = a.ws + (int64_t)h * ns * DA_PART + DA_PO + (k0 % DA_D);
-      float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll 4
-      for (int sp = 0; sp < ns; ++sp) {
-        const float f = fs[h * ns + sp];
-        const float4 u0 = *reinterpret_cast<const float4*>(o + sp * DA_PART);
-        const float4 u1 = *reinterpret_cast<const float4*>(o + sp * DA_PART + 4);
-        acc[0] = fmaf(f, u0.x, acc[0]);
-        acc[1] = fmaf(f, u0.y, acc[1]);
-        acc[2] = fmaf(f, u0.z, acc[2]);
-        acc[3] = fmaf(f, u0.w, acc[3]);
-        acc[4] = fmaf(f, u1.x, acc[4]);
-        acc[5] = fmaf(f, u1.y, acc[5]);
-        acc[6] = fmaf(f, u1.z, acc[6]);
-        acc[7] = fmaf(f, u1.w, acc[7]);
-      }
-#pragma unroll
-      for (int e = 0; e < 8; ++e) hs[k0 + e] = bf2f(f2bf(acc[e]));  // the bf16 attention output
-    }
-  } else {
-    const bool write_s = PRO == PRO_EMB_LN || a.branch != nullptr;
-    int64_t te = 0, pe = 0;
-    if constexpr (PRO == PRO_EMB_LN) {
-      te = *a.tok;
-      pe = *a.pos;
-    }
-    float xv[8], lwv[8], lbv[8];
-    float sum = 0.0f;
-    if (vec) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) xv[e] = lwv[e] = lbv[e] = 0.0f;
-      if (own) {
-        if constexpr (PRO == PRO_EMB_LN) {
-          float e0[8], e1[8];
-          load8(a.wte + te * K + g8, e0);
-          load8(a.wpe + pe * K + g8, e1);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) xv[e] = e0[e] + e1[e];
-        } else {
-          const float4 r0 = *reinterpret_cast<const float4*>(a.res + g8);
-          const float4 r1 = *reinterpret_cast<const float4*>(a.res + g8 + 4);
-          xv[0] = r0.x; xv[1] = r0.y; xv[2] = r0.z; xv[3] = r0.w;
-          xv[4] = r1.x; xv[5] = r1.y; xv[6] = r1.z; xv[7] = r1.w;
-          if (a.branch) {
-            float bv[8];
-            load8(a.branch + g8, bv);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) xv[e] += bv[e];
-          }
-        }
-        load8(a.lw + g8, lwv);
-        if (a.lb) load8(a.lb + g8, lbv);
-      }
-#pragma unroll
-      for (int e = 0; e < 8; ++e) sum += xv[e];
-    } else {
-      for (int k = tid; k < K; k += 256) {
-        float v;
-        if constexpr (PRO == PRO_EMB_LN) {
-          v = bf2f(a.wte[te * K + k]) + bf2f(a.wpe[pe * K + k]);
-        } else {
-          v = a.res[k];
-          if (a.branch) v += bf2f(a.branch[k]);
-        }
-        hs[k] = v;
-        sum += v;
-      }
-    }
-    sum = wave_sum(sum);
-    if (lane == 0) stat[0][w] = sum;
-    __syncthreads();
-    const float mean = (stat[0][0] + stat[0][1] + stat[0][2] + stat[0][3]) / (float)K;
-    float sq = 0.0f;
-    if (vec) {
-      if (own)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) sq = fmaf(xv[e] - mean, xv[e] - mean, sq);
-    } else {
-      for (int k = tid; k < K; k += 256) {
-        const float d = hs[k] - mean;
-        sq = fmaf(d, d, sq);
-      }
-    }
-    sq = wave_sum(sq);
-    if (lane == 0) stat[1][w] = sq;
-    __syncthreads();
-    const float rstd = rsqrtf((stat[1][0] + stat[1][1] + stat[1][2] + stat[1][3]) / (float)K + a.eps);
-    if (vec) {
-      if (own) {
-        if (blockIdx.x == 0 && write_s) {
-          *reinterpret_cast<float4*>(a.res_out + g8) = make_float4(xv[0], xv[1], xv[2], xv[3]);
-          *reinterpret_cast<float4*>(a.res_out + g8 + 4) = make_float4(xv[4], xv[5], xv[6], xv[7]);
-        }
-#pragma unroll
-        for (int e = 0; e < 8; ++e) hs[g8 + e] = bf2f(f2bf((xv[e] - mean) * rstd * lwv[e] + lbv[e]));
-      }
-    } else {
-      for (int k = tid; k < K; k += 256) {
-        const float sv = hs[k];
-        if (blockIdx.x == 0 && write_s) a.res_out[k] = sv;
-        float h = (sv - mean) * rstd * bf2f(a.lw[k]);
-        if (a.lb) h += bf2f(a.lb[k]);
-        hs[k] = bf2f(f2bf(h));  // the bf16 activation the LayerNorm kernel would hand the GEMM
-      }
-    }
-  }
+  // prologue: the row x[K] into hs[k]
+#define NSA_HS(k) (k)
+#include "decode_row_prologue.h"
+#undef NSA_HS
   __syncthreads();
   for (; cb < nblk; cb += gridDim.x) {
     const int n0 = cb * NC;
@@ -1294,7 +1101,7 @@ __global__ __launch_bounds__(256) void gemv_row_kernel(const RowPro a, const bf1
         wp[c] = *reinterpret_cast<const uint4*>(W + (int64_t)min(nb * NC + c, N - 1) * K + 8 * g0);
     }
     int idx;
-    const float v = wave_reduce_multi<1, NC>(acc, lane, idx);
+    const float v = wave_reduce_multi<NC>(acc, lane, idx);
     if ((lane & (64 / NC - 1)) == 0) red[w][idx] = v;
     __syncthreads();
     if (tid < NC) {
@@ -1315,15 +1122,7 @@ __global__ __launch_bounds__(256) void gemv_row_kernel(const RowPro a, const bf1
     if (a.pos_inc && blockIdx.x == 0 && tid == 0) *a.pos_inc += 1;
 }
 
-// NSA_GEMV_GRID: workgroup cap of the single-row GEMVs (default 1024: 4 per CU);
 // NSA_GEMV_NC: output columns per workgroup block (2, 4, 8 or 16)
-int gemv_row_grid() {
-  static const int g = [] {
-    const char* e = getenv("NSA_GEMV_GRID");
-    return e ? std::max(1, atoi(e)) : 1024;
-  }();
-  return g;
-}
 int env_nc(const char* name) {  // 0: unset
   const char* e = getenv(name);
   const int v = e ? atoi(e) : 0;
@@ -1602,12 +1401,6 @@ NSA_API hipError_t nsa_skinny_gemm(const void* x, const void* W, const void* bia
 // fragments from there; workgroup 0 writes s (fp32).  The first round of weight loads is
 // issued before the prologue and each round prefetches the next, so the weight stream
 // overlaps the LayerNorm.  Removes the separate add+LayerNorm launch per linear.
-__device__ __forceinline__ float sk_wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 template <int ACT, bool OUTF>
 __global__ __launch_bounds__(256) void skinny_ln_gemm_kernel(const float* __restrict__ res,
                                                              const bf16_t* __restrict__ branch,
@@ -1635,63 +1428,8 @@ __global__ __launch_bounds__(256) void skinny_ln_gemm_kernel(const float* __rest
     }
   };
   load_a(w, a);
-  // prologue: LayerNorm of the M batch rows into LDS; rows M..15 are zeroed (they only feed
-  // output columns m >= M, which are never stored)
-  for (int m = M + w; m < 16; m += 4)
-    for (int k = 8 * lane; k < K; k += 512) *reinterpret_cast<uint4*>(xs + m * KP + k) = uint4{0u, 0u, 0u, 0u};
-  for (int m = w; m < M; m += 4) {
-    const int mm = m;
-    float v[4][8];
-    float sum = 0.0f;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int k = (q * 64 + lane) * 8;
-      if (k < K) {
-        const float4 r0 = *reinterpret_cast<const float4*>(res + (int64_t)mm * K + k);
-        const float4 r1 = *reinterpret_cast<const float4*>(res + (int64_t)mm * K + k + 4);
-        v[q][0] = r0.x; v[q][1] = r0.y; v[q][2] = r0.z; v[q][3] = r0.w;
-        v[q][4] = r1.x; v[q][5] = r1.y; v[q][6] = r1.z; v[q][7] = r1.w;
-        if (branch) {
-          float bv[8];
-          load8(branch + (int64_t)mm * K + k, bv);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) v[q][e] += bv[e];
-        }
-#pragma unroll
-        for (int e = 0; e < 8; ++e) sum += v[q][e];
-      }
-    }
-    const float mean = sk_wave_sum(sum) / (float)K;
-    float sq = 0.0f;
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-      if ((q * 64 + lane) * 8 < K)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) sq = fmaf(v[q][e] - mean, v[q][e] - mean, sq);
-    const float rstd = rsqrtf(sk_wave_sum(sq) / (float)K + eps);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int k = (q * 64 + lane) * 8;
-      if (k < K) {
-        float wv[8], bv[8], o[8];
-        load8(lw + k, wv);
-        if (lb) {
-          load8(lb + k, bv);
-        } else {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) bv[e] = 0.0f;
-        }
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] = (v[q][e] - mean) * rstd * wv[e] + bv[e];
-        store8(xs + m * KP + k, o);
-        if (blockIdx.x == 0 && s_out && m < M) {
-          float* sp = s_out + (int64_t)m * K + k;
-          *reinterpret_cast<float4*>(sp) = make_float4(v[q][0], v[q][1], v[q][2], v[q][3]);
-          *reinterpret_cast<float4*>(sp + 4) = make_float4(v[q][4], v[q][5], v[q][6], v[q][7]);
-        }
-      }
-    }
-  }
+  // prologue: LayerNorm of the M batch rows into LDS
+#include "decode_skinny_ln_prologue.h"
   __syncthreads();
   f32x4 acc = f32x4{};
   for (int u0 = w; u0 < U; u0 += 4 * UN) {

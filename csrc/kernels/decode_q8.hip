@@ -8,45 +8,22 @@
 // differ from the bf16 kernels run on the dequantized weights by summation order alone.
 //
 // The prologues (residual add + LayerNorm, embedding + LayerNorm, flash-decoding combine)
-// are the bf16 kernels' own, statement for statement (the single-row ones store the row to
-// LDS in another order, hx() below).  They are repeated here rather than shared: moving
-// them out of decode.hip into a common header changed the compiled code of the bf16 kernels
-// (register allocation, scalar / vector address arithmetic), and this file leaves decode.hip
-// and its kernels byte-identical.
-#include "common.h"
+// are the bf16 kernels' own: one source, the function-body fragments decode_row_prologue.h
+// and decode_skinny_ln_prologue.h, which decode.hip includes inline in its kernels and this
+// file as the bodies of row_prologue() and skinny_ln_prologue().  The single-row ones store
+// the row to LDS in another order here (hx() below, through the fragment's NSA_HS macro).
+// They are shared as text, not as a function: calling a function from decode.hip's
+// gemv_row_kernel changes the compiled code of the bf16 kernels (register allocation,
+// occupancy), while textual inclusion leaves the kernels of both files as they were.  The
+// declarations both files use (RowPro, PRO_*, the partial layout, wave_reduce_multi,
+// gemv_row_grid) are in decode_rows.h.
+#include "decode_rows.h"
 
 #include <math.h>
-#include <stdlib.h>
 
 #include <algorithm>
 
 namespace {
-
-constexpr int DA_D = 64;        // head dim of the decode-attention kernel
-constexpr int DA_PO = 4;          // o[] offset in a partial: 16-byte aligned for vector reads
-constexpr int DA_PART = DA_PO + DA_D;  // m, l, (pad), o[64]
-
-// The single-row prologues of decode.hip's gemv_row_kernel (see there):
-//   PRO_LN     s = res + branch (fp32; written to res_out by workgroup 0), x = LN(s)
-//   PRO_EMB_LN s = wte[*tok] + wpe[*pos] (written to res_out by workgroup 0), x = LN(s)
-//   PRO_ATTN   x = the flash-decoding combine of the attention partials (ws, H heads)
-enum { PRO_LN = 0, PRO_ATTN = 1, PRO_EMB_LN = 2 };
-
-struct RowPro {
-  const float* res;
-  const bf16_t* branch;
-  float* res_out;
-  const bf16_t* lw;
-  const bf16_t* lb;
-  float eps;
-  const float* ws;
-  int n_split;
-  const int64_t* tok;
-  const int64_t* pos;
-  const bf16_t* wte;
-  const bf16_t* wpe;
-  int64_t* pos_inc;  // PRO_LN: incremented by one thread after the row (the decode step's position)
-};
 
 // LDS position of x[k].  A lane multiplies one 16-byte weight piece (k = 16 g .. 16 g + 15)
 // with 16 values of x; k-contiguous rows would put lane g at a 64-byte stride, all 64 lanes
@@ -56,225 +33,26 @@ __device__ __forceinline__ int hx(int k, int nck) { return (((k >> 2) & 3) * nck
 
 // The row x[K] into hs[] at hx(k) (256 threads; stat: 2 x 4 floats of LDS; PRO_ATTN also uses
 // hs[K ..] for the chunk weights).  The caller's barrier after it publishes hs[].
-// K <= 2048 (every GPT-2 width): thread g owns x[8g .. 8g+7] and issues all of its loads
-// at once (16-byte vectors), so the row costs one memory round trip and two block
-// reductions; wider rows loop.
 template <int PRO>
 __device__ __forceinline__ void row_prologue(const RowPro& a, float* hs, float (*stat)[4], int K) {
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int nck = K / 16;
-  const bool vec = K <= 2048;
-  const int g8 = 8 * tid;
-  const bool own = vec && g8 < K;
-  if constexpr (PRO == PRO_ATTN) {
-    const int H = K / DA_D, ns = a.n_split;
-    float* fs = hs + K;  // [H][ns] chunk weights 2^(m_s - M) / L
-    for (int h = tid; h < H; h += 256) {
-      const float* part = a.ws + (int64_t)h * ns * DA_PART;
-      float M = -INFINITY;
-#pragma unroll 4
-      for (int sp = 0; sp < ns; ++sp) M = fmaxf(M, part[sp * DA_PART]);
-      float L = 0.0f;
-#pragma unroll 4
-      for (int sp = 0; sp < ns; ++sp) L = fmaf(exp2f(part[sp * DA_PART] - M), part[sp * DA_PART + 1], L);
-      const float inv = 1.0f / L;
-      for (int sp = 0; sp < ns; ++sp) fs[h * ns + sp] = exp2f(part[sp * DA_PART] - M) * inv;  // empty: 0
-    }
-    __syncthreads();
-    for (int k0 = g8; k0 < K; k0 += 8 * 256) {  // 8 dims of one head per thread and pass
-      const int h = k0 / DA_D;
-      const float* o = a.ws + (int64_t)h * ns * DA_PART + DA_PO + (k0 % DA_D);
-      float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll 4
-      for (int sp = 0; sp < ns; ++sp) {
-        const float f = fs[h * ns + sp];
-        const float4 u0 = *reinterpret_cast<const float4*>(o + sp * DA_PART);
-        const float4 u1 = *reinterpret_cast<const float4*>(o + sp * DA_PART + 4);
-        acc[0] = fmaf(f, u0.x, acc[0]);
-        acc[1] = fmaf(f, u0.y, acc[1]);
-        acc[2] = fmaf(f, u0.z, acc[2]);
-        acc[3] = fmaf(f, u0.w, acc[3]);
-        acc[4] = fmaf(f, u1.x, acc[4]);
-        acc[5] = fmaf(f, u1.y, acc[5]);
-        acc[6] = fmaf(f, u1.z, acc[6]);
-        acc[7] = fmaf(f, u1.w, acc[7]);
-      }
-#pragma unroll
-      for (int e = 0; e < 8; ++e) hs[hx(k0 + e, nck)] = bf2f(f2bf(acc[e]));  // the bf16 attention output
-    }
-  } else {
-    const bool write_s = PRO == PRO_EMB_LN || a.branch != nullptr;
-    int64_t te = 0, pe = 0;
-    if constexpr (PRO == PRO_EMB_LN) {
-      te = *a.tok;
-      pe = *a.pos;
-    }
-    float xv[8], lwv[8], lbv[8];
-    float sum = 0.0f;
-    if (vec) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) xv[e] = lwv[e] = lbv[e] = 0.0f;
-      if (own) {
-        if constexpr (PRO == PRO_EMB_LN) {
-          float e0[8], e1[8];
-          load8(a.wte + te * K + g8, e0);
-          load8(a.wpe + pe * K + g8, e1);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) xv[e] = e0[e] + e1[e];
-        } else {
-          const float4 r0 = *reinterpret_cast<const float4*>(a.res + g8);
-          const float4 r1 = *reinterpret_cast<const float4*>(a.res + g8 + 4);
-          xv[0] = r0.x; xv[1] = r0.y; xv[2] = r0.z; xv[3] = r0.w;
-          xv[4] = r1.x; xv[5] = r1.y; xv[6] = r1.z; xv[7] = r1.w;
-          if (a.branch) {
-            float bv[8];
-            load8(a.branch + g8, bv);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) xv[e] += bv[e];
-          }
-        }
-        load8(a.lw + g8, lwv);
-        if (a.lb) load8(a.lb + g8, lbv);
-      }
-#pragma unroll
-      for (int e = 0; e < 8; ++e) sum += xv[e];
-    } else {
-      for (int k = tid; k < K; k += 256) {
-        float v;
-        if constexpr (PRO == PRO_EMB_LN) {
-          v = bf2f(a.wte[te * K + k]) + bf2f(a.wpe[pe * K + k]);
-        } else {
-          v = a.res[k];
-          if (a.branch) v += bf2f(a.branch[k]);
-        }
-        hs[hx(k, nck)] = v;
-        sum += v;
-      }
-    }
-    sum = wave_sum(sum);
-    if (lane == 0) stat[0][w] = sum;
-    __syncthreads();
-    const float mean = (stat[0][0] + stat[0][1] + stat[0][2] + stat[0][3]) / (float)K;
-    float sq = 0.0f;
-    if (vec) {
-      if (own)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) sq = fmaf(xv[e] - mean, xv[e] - mean, sq);
-    } else {
-      for (int k = tid; k < K; k += 256) {
-        const float d = hs[hx(k, nck)] - mean;
-        sq = fmaf(d, d, sq);
-      }
-    }
-    sq = wave_sum(sq);
-    if (lane == 0) stat[1][w] = sq;
-    __syncthreads();
-    const float rstd = rsqrtf((stat[1][0] + stat[1][1] + stat[1][2] + stat[1][3]) / (float)K + a.eps);
-    if (vec) {
-      if (own) {
-        if (blockIdx.x == 0 && write_s) {
-          *reinterpret_cast<float4*>(a.res_out + g8) = make_float4(xv[0], xv[1], xv[2], xv[3]);
-          *reinterpret_cast<float4*>(a.res_out + g8 + 4) = make_float4(xv[4], xv[5], xv[6], xv[7]);
-        }
-#pragma unroll
-        for (int e = 0; e < 8; ++e) hs[hx(g8 + e, nck)] = bf2f(f2bf((xv[e] - mean) * rstd * lwv[e] + lbv[e]));
-      }
-    } else {
-      for (int k = tid; k < K; k += 256) {
-        const float sv = hs[hx(k, nck)];
-        if (blockIdx.x == 0 && write_s) a.res_out[k] = sv;
-        float h = (sv - mean) * rstd * bf2f(a.lw[k]);
-        if (a.lb) h += bf2f(a.lb[k]);
-        hs[hx(k, nck)] = bf2f(f2bf(h));  // the bf16 activation the LayerNorm kernel would hand the GEMM
-      }
-    }
-  }
-}
-
-// NSA_GEMV_GRID: workgroup cap of the single-row GEMVs (default 1024: 4 per CU), as in decode.hip
-int gemv_row_grid() {
-  static const int g = [] {
-    const char* e = getenv("NSA_GEMV_GRID");
-    return e ? std::max(1, atoi(e)) : 1024;
-  }();
-  return g;
-}
-
-__device__ __forceinline__ float sk_wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
+#define NSA_HS(k) hx(k, nck)
+#include "decode_row_prologue.h"
+#undef NSA_HS
 }
 
 // Prologue of the skinny GEMMs with the residual add + LayerNorm in front (256 threads):
-// s = res + branch and x = LN(s) for the M batch rows (wave w: rows w, w + 4, ...; a row of
-// K <= 2048 lives in 32 registers per lane, two-pass mean / variance as nanoGPT's fp32
-// LayerNorm), x stored as bf16 in xs ([16][K + 8], padded rows); rows M..15 are zeroed
-// (they only feed output columns m >= M, which are never stored); workgroup 0 writes s
-// (fp32).  The caller's barrier after it publishes xs[].
+// x = LN(res + branch) of the M batch rows as bf16 in xs ([16][K + 8], padded rows).  The
+// caller's barrier after it publishes xs[].
 __device__ __forceinline__ void skinny_ln_prologue(const float* __restrict__ res, const bf16_t* __restrict__ branch,
                                                    float* __restrict__ s_out, const bf16_t* __restrict__ lw,
                                                    const bf16_t* __restrict__ lb, float eps, bf16_t* xs, int M,
                                                    int K) {
   const int KP = K + 8;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  for (int m = M + w; m < 16; m += 4)
-    for (int k = 8 * lane; k < K; k += 512) *reinterpret_cast<uint4*>(xs + m * KP + k) = uint4{0u, 0u, 0u, 0u};
-  for (int m = w; m < M; m += 4) {
-    const int mm = m;
-    float v[4][8];
-    float sum = 0.0f;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int k = (q * 64 + lane) * 8;
-      if (k < K) {
-        const float4 r0 = *reinterpret_cast<const float4*>(res + (int64_t)mm * K + k);
-        const float4 r1 = *reinterpret_cast<const float4*>(res + (int64_t)mm * K + k + 4);
-        v[q][0] = r0.x; v[q][1] = r0.y; v[q][2] = r0.z; v[q][3] = r0.w;
-        v[q][4] = r1.x; v[q][5] = r1.y; v[q][6] = r1.z; v[q][7] = r1.w;
-        if (branch) {
-          float bv[8];
-          load8(branch + (int64_t)mm * K + k, bv);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) v[q][e] += bv[e];
-        }
-#pragma unroll
-        for (int e = 0; e < 8; ++e) sum += v[q][e];
-      }
-    }
-    const float mean = sk_wave_sum(sum) / (float)K;
-    float sq = 0.0f;
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-      if ((q * 64 + lane) * 8 < K)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) sq = fmaf(v[q][e] - mean, v[q][e] - mean, sq);
-    const float rstd = rsqrtf(sk_wave_sum(sq) / (float)K + eps);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int k = (q * 64 + lane) * 8;
-      if (k < K) {
-        float wv[8], bv[8], o[8];
-        load8(lw + k, wv);
-        if (lb) {
-          load8(lb + k, bv);
-        } else {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) bv[e] = 0.0f;
-        }
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] = (v[q][e] - mean) * rstd * wv[e] + bv[e];
-        store8(xs + m * KP + k, o);
-        if (blockIdx.x == 0 && s_out && m < M) {
-          float* sp = s_out + (int64_t)m * K + k;
-          *reinterpret_cast<float4*>(sp) = make_float4(v[q][0], v[q][1], v[q][2], v[q][3]);
-          *reinterpret_cast<float4*>(sp + 4) = make_float4(v[q][4], v[q][5], v[q][6], v[q][7]);
-        }
-      }
-    }
-  }
+#include "decode_skinny_ln_prologue.h"
 }
-
 
 // ---------------------------------------------------------------------------
 // int8 -> fp32 / bf16 (two's-complement bytes, exact)
@@ -301,34 +79,6 @@ __device__ __forceinline__ uint32_t q8bf2(uint32_t w, int j) {
 __device__ __forceinline__ bf16x8 q8frag(uint32_t lo, uint32_t hi) {
   const uint4 u = {q8bf2(lo, 0), q8bf2(lo, 2), q8bf2(hi, 0), q8bf2(hi, 2)};
   return __builtin_bit_cast(bf16x8, u);
-}
-
-// V values per lane -> lane holds the wave-wide sum of value `index` (decode.hip's
-// wave_reduce_multi: halve-and-exchange butterfly)
-template <int V>
-__device__ __forceinline__ float wave_reduce_multi(float (&v)[V], int lane, int& index) {
-  int cnt = V;
-  index = 0;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    if (cnt > 1) {
-      const bool upper = (lane & off) != 0;
-      const int h = cnt / 2;
-#pragma unroll
-      for (int i = 0; i < V / 2; ++i) {
-        if (i < h) {
-          const float send = upper ? v[i] : v[i + h];
-          const float keep = upper ? v[i + h] : v[i];
-          v[i] = keep + __shfl_xor(send, off, 64);
-        }
-      }
-      if (upper) index += h;
-      cnt = h;
-    } else {
-      v[0] += __shfl_xor(v[0], off, 64);
-    }
-  }
-  return v[0];
 }
 
 // ---------------------------------------------------------------------------

@@ -278,7 +278,8 @@ def test_decode_skinny_ln_kernel(kernels, monkeypatch, rows, branch, N, K, bias,
 @pytest.mark.parametrize("branch", [False, True])
 @pytest.mark.parametrize("N,K,bias,gelu,f32", [(2304, 768, True, False, False), (3072, 768, True, True, False),
                                               (50304, 768, False, False, True), (6400, 1600, True, True, False),
-                                              (100, 64, False, False, False)])
+                                              (100, 64, False, False, False),
+                                              (100, 2560, False, False, False)])  # K > 2048: the scalar loop
 def test_decode_linear_ln_kernel(kernels, branch, N, K, bias, gelu, f32):
     """Fused residual add + LayerNorm + GEMV (one decode row) against fp32 torch on the
     same bf16-rounded LayerNorm output."""
@@ -346,12 +347,13 @@ def test_device_sampling_all_ties(kernels):
     assert len(set(tok[:, 0].tolist())) > 200
 
 
-def test_decode_embed_linear_ln_kernel(kernels):
+@pytest.mark.parametrize("C", [768, 2560])  # the vector prologue, and the scalar loop of K > 2048
+def test_decode_embed_linear_ln_kernel(kernels, C):
     from nanosandbox_amd import ops
     import torch.nn.functional as F
 
     torch.manual_seed(1)
-    V, T, C, N = 512, 128, 768, 2304
+    V, T, N = 512, 128, 2304
     wte = (torch.randn(V, C, device=DEV) * 0.5).to(BF)
     wpe = (torch.randn(T, C, device=DEV) * 0.5).to(BF)
     lw = (1 + 0.1 * torch.randn(C, device=DEV)).to(BF)
@@ -369,14 +371,16 @@ def test_decode_embed_linear_ln_kernel(kernels):
     assert err < 1e-2, err
 
 
-@pytest.mark.parametrize("pos", [0, 300, 1023])
-def test_attention_partials_into_linear(kernels, pos):
+# H = 12 (C = 768), and 40 (C = 2560): the second pass of the combine (K > 2048)
+@pytest.mark.parametrize("pos,H", [pytest.param(p, h, id=str(p) if h == 12 else "%d-H%d" % (p, h))
+                                   for h in (12, 40) for p in (0, 300, 1023)])
+def test_attention_partials_into_linear(kernels, pos, H):
     """decode_attention(combine=False) -> decode_linear (combine in the GEMV prologue)
     equals the combine kernel's output through the plain GEMV."""
     from nanosandbox_amd import ops
 
     torch.manual_seed(pos)
-    H, D, T = 12, 64, 1024
+    D, T = 64, 1024
     C = H * D
     kc = torch.randn(1, H, T, D, device=DEV).to(BF)
     vc = torch.randn(1, H, T, D, device=DEV).to(BF)

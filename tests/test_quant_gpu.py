@@ -129,11 +129,12 @@ def test_q8_gemv_wide_row(kernels, monkeypatch):
     assert torch.equal(y.view(1, N), ref.float())
 
 
-def test_q8_embed_linear_ln_kernel(kernels, monkeypatch):
+@pytest.mark.parametrize("C", [768, 2560])  # the vector prologue, and the scalar loop of K > 2048
+def test_q8_embed_linear_ln_kernel(kernels, monkeypatch, C):
     from nanosandbox_amd import ops
 
     calls = _record(monkeypatch)
-    V, T, C, N = 512, 128, 768, 2304
+    V, T, N = 512, 128, 2304
     qw, dq, b = _weights(N, C, True, 1)
     wte = (torch.randn(V, C, device=DEV) * 0.5).to(BF)
     wpe = (torch.randn(T, C, device=DEV) * 0.5).to(BF)
@@ -150,14 +151,16 @@ def test_q8_embed_linear_ln_kernel(kernels, monkeypatch):
     assert y.shape == (1, 1, N) and err < 1e-2, err
 
 
-@pytest.mark.parametrize("pos", [0, 300, 1023])
-def test_q8_attention_partials_into_linear(kernels, monkeypatch, pos):
+# H = 12 (C = 768), and 40 (C = 2560): the second pass of the combine (K > 2048)
+@pytest.mark.parametrize("pos,H", [pytest.param(p, h, id=str(p) if h == 12 else "%d-H%d" % (p, h))
+                                   for h in (12, 40) for p in (0, 300, 1023)])
+def test_q8_attention_partials_into_linear(kernels, monkeypatch, pos, H):
     """decode_attention(combine=False) -> decode_linear(QuantWeight): the combine in the
     nsa_gemv_attn_q8 prologue, against the combine kernel's bf16 output through the reference."""
     from nanosandbox_amd import ops
 
     torch.manual_seed(pos)
-    H, D, T = 12, 64, 1024
+    D, T = 64, 1024
     C = H * D
     kc = torch.randn(1, H, T, D, device=DEV).to(BF)
     vc = torch.randn(1, H, T, D, device=DEV).to(BF)
