@@ -1,4 +1,4 @@
-"""Nucleus (top-p) and min-p sampling on MI355X: the kept set of ``sample_filtered_kernel``
+"""Nucleus (top-p) and min-p sampling on MI355X: the kept set of ``nsa_sample_filtered``
 (reported through ``stats``), its draws and the graph-replayed decode step, against the
 float64 reference and fixtures of tests/test_nucleus_refs.py."""
 
