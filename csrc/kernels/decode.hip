@@ -17,6 +17,13 @@
 // max.  Chunks past `pos` write an empty partial (m = -inf) and exit, so the grid is
 // fixed by Tmax (graph-safe) while the work follows the live context length.
 //
+// Int8 caches (Decoder(..., kv_quantize="int8")): K and V as int8 [B, H, Tmax, 64], one
+// 64-byte row per key, with one fp32 scale per row ([B, H, Tmax], one tensor each for K and
+// V); a row stands for q * scale (ops.quantize_cache_rows: scale = absmax / 127, q =
+// rint(x / scale)).  The partial kernel is the bf16 one instantiated on the cache's element
+// type: same grid, chunks and workspace, so the combine kernel and the nsa_gemv_attn
+// prologues read its partials unchanged.
+//
 // Also here: the weight-streaming decode linears (GEMV / skinny GEMM with their prologues)
 // and the per-row position advance.  The step's sampler is sample.hip.
 #include "decode_rows.h"
@@ -27,8 +34,6 @@
 #include <algorithm>
 
 namespace {
-
-constexpr int DA_CHUNK = 256;   // keys per workgroup (one per thread)
 
 __global__ __launch_bounds__(256) void kv_append_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ kc,
                                                         bf16_t* __restrict__ vc, const int64_t* __restrict__ pos_dev,
@@ -54,19 +59,96 @@ __global__ __launch_bounds__(256) void kv_append_kernel(const bf16_t* __restrict
   *reinterpret_cast<uint4*>(dst) = *reinterpret_cast<const uint4*>(src);
 }
 
+// One cache row's int8 form: scale = absmax / 127 (1 for an all-zero row), q = rint(x / scale)
+// with a correctly rounded fp32 division (the build uses no fast-math), round-half-to-even and
+// a clamp to +-127: ops.quantize_cache_rows bit for bit.
+__device__ __forceinline__ float kv8_scale(float absmax) { return absmax > 0.0f ? absmax / 127.0f : 1.0f; }
+__device__ __forceinline__ float kv8_quant(float x, float scale) {
+  return fminf(fmaxf(rintf(x / scale), -127.0f), 127.0f);
+}
+// four integer-valued floats as the bytes of one dword (byte 0 first)
+__device__ __forceinline__ uint32_t kv8_pack4(float a, float b, float c, float d) {
+  return ((uint32_t)(int)a & 0xffu) | (((uint32_t)(int)b & 0xffu) << 8) | (((uint32_t)(int)c & 0xffu) << 16) |
+         ((uint32_t)(int)d << 24);
+}
+
+// kv_append_kernel for int8 caches (D = 64): an 8-lane group per K or V row, lane c holds the
+// row's values 8c .. 8c+7; index = (((b*S + s)*2 + kv)*H + h)*8 + c.  The row's absmax meets in
+// three shuffles inside the group (groups never straddle the early exits: 256 and the total are
+// multiples of 8, and the position is the group's).
+__global__ __launch_bounds__(256) void kv_append_kv8_kernel(const bf16_t* __restrict__ qkv, int8_t* __restrict__ kq,
+                                                            float* __restrict__ ksc, int8_t* __restrict__ vq,
+                                                            float* __restrict__ vsc,
+                                                            const int64_t* __restrict__ pos_dev, int pos0, int B,
+                                                            int S, int H, int Tmax) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t total = (int64_t)B * S * 2 * H * 8;
+  if (i >= total) return;
+  const int c = (int)(i & 7);
+  int64_t r = i >> 3;
+  const int hh = (int)(r % H);
+  r /= H;
+  const int kv = (int)(r & 1);
+  r >>= 1;
+  const int s = (int)(r % S);
+  const int b = (int)(r / S);
+  const int p = (pos_dev ? (int)*pos_dev : pos0) + s;
+  if (p < 0 || p >= Tmax) return;
+  const int C = H * DA_D;
+  float x[8];
+  load8(qkv + ((int64_t)b * S + s) * 3 * C + (1 + kv) * C + hh * DA_D + c * 8, x);
+  float am = 0.0f;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) am = fmaxf(am, fabsf(x[j]));
+#pragma unroll
+  for (int off = 1; off < 8; off <<= 1) am = fmaxf(am, __shfl_xor(am, off, 64));
+  const float sc = kv8_scale(am);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) x[j] = kv8_quant(x[j], sc);
+  const int64_t row = ((int64_t)b * H + hh) * Tmax + p;
+  *reinterpret_cast<uint2*>((kv ? vq : kq) + row * DA_D + c * 8) =
+      uint2{kv8_pack4(x[0], x[1], x[2], x[3]), kv8_pack4(x[4], x[5], x[6], x[7])};
+  if (c == 0) (kv ? vsc : ksc)[row] = sc;
+}
+
+// per-row scales of an int8 cache (fp32 [B, H, Tmax] each); nothing for a bf16 cache
+template <typename CT>
+struct CacheScales {};
+template <>
+struct CacheScales<int8_t> {
+  float* k;
+  float* v;
+};
+
 // grid (B*H, n_split), 256 threads; pos_dev[b * pos_stride] is row b's position
 // append: also store the new token's K / V rows at position pos (kc_w / vc_w alias
 // kc / vc; separate non-restrict pointers for the one write)
+//
+// CT: the cache's element type.  bf16_t: the rows hold the values.  int8_t: 64-byte rows with
+// one fp32 scale per row in cs.k / cs.v (CacheScales, the last argument: empty in the bf16
+// form, whose other arguments sit where they always did).  A thread scores its key on the raw bytes (int8 -> float
+// is exact) and multiplies by the key's scale once; ps[] holds p * vscale[key], so the V loop
+// works on raw bytes too, while l sums the un-scaled p.  Appending, the workgroup whose chunk
+// holds pos quantizes the new K and V rows itself (wave 0: K, wave 1: V; one value per lane),
+// stores bytes and scale for later steps and leaves the quantized values in LDS (nq / nsc):
+// the threads that meet position pos take the row from there in the same arithmetic as from
+// the cache, never from the global row this launch writes.  So the output is a function of
+// the cache contents only: append gives what kv_append followed by a plain call gives.
+template <typename CT>
 __global__ __launch_bounds__(256) void decode_attn_partial_kernel(const bf16_t* __restrict__ qkv,
-                                                                  const bf16_t* __restrict__ kc,
-                                                                  const bf16_t* __restrict__ vc, bf16_t* kc_w,
-                                                                  bf16_t* vc_w, const int64_t* __restrict__ pos_dev,
+                                                                  const CT* __restrict__ kc,
+                                                                  const CT* __restrict__ vc, CT* kc_w, CT* vc_w,
+                                                                  const int64_t* __restrict__ pos_dev,
                                                                   int pos_stride, float* __restrict__ ws, int H,
-                                                                  int Tmax, float scale_log2, int append) {
+                                                                  int Tmax, float scale_log2, int append,
+                                                                  const CacheScales<CT> cs) {
+  constexpr bool KV8 = sizeof(CT) == 1;
   __shared__ float qs[DA_D];
   __shared__ float ps[DA_CHUNK];
   __shared__ float red[2][4];
   __shared__ float os[4][DA_D];
+  __shared__ float nq[KV8 ? 2 : 1][DA_D];  // int8 caches, append: the new K / V rows, quantized (integers)
+  __shared__ float nsc[2];                 // and their scales
   const int bh = blockIdx.x, s = blockIdx.y, n_split = gridDim.y;
   const int b = bh / H, hh = bh % H;
   const int C = H * DA_D;
@@ -82,26 +164,80 @@ __global__ __launch_bounds__(256) void decode_attn_partial_kernel(const bf16_t* 
   }
   const bf16_t* qrow = qkv + (int64_t)b * 3 * C + hh * DA_D;  // q | k | v of the new token
   if (tid < DA_D) qs[tid] = bf2f(qrow[tid]);
-  if (append && pos < k0 + DA_CHUNK && tid < 2 * (DA_D / 8)) {
-    // this chunk holds position pos: store the new token's K / V rows for later steps
-    // (this kernel itself takes them straight from qkv, so no write->read ordering)
-    const int c = tid & 7, kv = tid >> 3;
-    *reinterpret_cast<uint4*>((kv ? vc_w : kc_w) + ((int64_t)bh * Tmax + pos) * DA_D + 8 * c) =
-        *reinterpret_cast<const uint4*>(qrow + (1 + kv) * C + 8 * c);
-  }
-  __syncthreads();
   const int key = k0 + tid;
   const bool live = key <= pos;
+  // int8 caches: this thread's key row (raw bytes) and its K / V scales; the row this launch
+  // appends comes from LDS instead (fresh), and its loads go to the (valid, unused) q row, not
+  // to the cache row being written
+  [[maybe_unused]] const bool fresh = KV8 && append && key == pos;
+  [[maybe_unused]] uint4 ku[DA_D / 16];
+  [[maybe_unused]] float ks = 0.0f, vs = 0.0f;
+  if constexpr (KV8) {
+    if (live) {  // issued before the quantizer below, so their latency overlaps it
+      const int64_t row = (int64_t)bh * Tmax + key;
+      const uint4* krow = reinterpret_cast<const uint4*>(fresh ? (const int8_t*)qrow : kc + row * DA_D);
+#pragma unroll
+      for (int c = 0; c < DA_D / 16; ++c) ku[c] = krow[c];
+      if (!fresh) {
+        ks = cs.k[row];
+        vs = cs.v[row];
+      }
+    }
+    if (append && pos < k0 + DA_CHUNK && w < 2) {  // wave-uniform: all 64 lanes of waves 0 and 1
+      const float x = bf2f(qrow[(1 + w) * C + lane]);
+      const float s1 = kv8_scale(wave_max(fabsf(x)));
+      const float qv = kv8_quant(x, s1);
+      nq[w][lane] = qv;
+      // lane l < 16 stores bytes 4l .. 4l+3 as one dword
+      const float q0 = __shfl(qv, (4 * lane) & 63, 64), q1 = __shfl(qv, (4 * lane + 1) & 63, 64);
+      const float q2 = __shfl(qv, (4 * lane + 2) & 63, 64), q3 = __shfl(qv, (4 * lane + 3) & 63, 64);
+      const int64_t row = (int64_t)bh * Tmax + pos;
+      if (lane < DA_D / 4)
+        reinterpret_cast<uint32_t*>((w ? vc_w : kc_w) + row * DA_D)[lane] = kv8_pack4(q0, q1, q2, q3);
+      if (lane == 0) {
+        nsc[w] = s1;
+        (w ? cs.v : cs.k)[row] = s1;
+      }
+    }
+  } else {
+    if (append && pos < k0 + DA_CHUNK && tid < 2 * (DA_D / 8)) {
+      // this chunk holds position pos: store the new token's K / V rows for later steps
+      // (this kernel itself takes them straight from qkv, so no write->read ordering)
+      const int c = tid & 7, kv = tid >> 3;
+      *reinterpret_cast<uint4*>((kv ? vc_w : kc_w) + ((int64_t)bh * Tmax + pos) * DA_D + 8 * c) =
+          *reinterpret_cast<const uint4*>(qrow + (1 + kv) * C + 8 * c);
+    }
+  }
+  __syncthreads();
   float sc = -INFINITY;
   if (live) {
-    const bf16_t* krow = key == pos ? qrow + C : kc + ((int64_t)bh * Tmax + key) * DA_D;
     float acc = 0.0f;
+    if constexpr (KV8) {
+      if (fresh) {
+        ks = nsc[0];
+        vs = nsc[1];
+      }
 #pragma unroll
-    for (int c = 0; c < DA_D / 8; ++c) {
-      float kf[8];
-      load8(krow + 8 * c, kf);
+      for (int c = 0; c < DA_D / 16; ++c) {
+        float kf[2][8];
+        unpack8q(ku[c].x, ku[c].y, kf[0]);
+        unpack8q(ku[c].z, ku[c].w, kf[1]);
+        if (fresh)
 #pragma unroll
-      for (int j = 0; j < 8; ++j) acc = fmaf(qs[8 * c + j], kf[j], acc);
+          for (int j = 0; j < 16; ++j) kf[j >> 3][j & 7] = nq[0][16 * c + j];
+#pragma unroll
+        for (int j = 0; j < 16; ++j) acc = fmaf(qs[16 * c + j], kf[j >> 3][j & 7], acc);
+      }
+      acc *= ks;
+    } else {
+      const bf16_t* krow = key == pos ? qrow + C : kc + ((int64_t)bh * Tmax + key) * DA_D;
+#pragma unroll
+      for (int c = 0; c < DA_D / 8; ++c) {
+        float kf[8];
+        load8(krow + 8 * c, kf);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) acc = fmaf(qs[8 * c + j], kf[j], acc);
+      }
     }
     sc = acc * scale_log2;
   }
@@ -112,7 +248,8 @@ __global__ __launch_bounds__(256) void decode_attn_partial_kernel(const bf16_t* 
   const float p = live ? exp2f(sc - m) : 0.0f;
   const float lw = wave_sum(p);
   if (lane == 0) red[1][w] = lw;
-  ps[tid] = p;
+  if constexpr (KV8) ps[tid] = live ? p * vs : 0.0f;  // a dead key has no scale to read
+  else ps[tid] = p;
   __syncthreads();
   // weighted V sum: thread (key group kg = tid / 8: keys k0 + 8 kg .. +7; dims 8 dg .. +7)
   // issues its 8 16-byte row loads together (one 2-byte load per key and lane in a
@@ -126,9 +263,19 @@ __global__ __launch_bounds__(256) void decode_attn_partial_kernel(const bf16_t* 
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
     const int kk = min(k0 + 8 * kg + j, pos);
-    const bf16_t* vr = (append && kk == pos) ? qrow + 2 * C : vc + ((int64_t)bh * Tmax + kk) * DA_D;
     float vf[8];
-    load8(vr + 8 * dg, vf);
+    if constexpr (KV8) {  // 8-byte loads; the appended row from LDS as for K
+      const bool vfresh = append && kk == pos;
+      const int8_t* vr = vfresh ? (const int8_t*)qrow : vc + ((int64_t)bh * Tmax + kk) * DA_D;
+      const uint2 u = *reinterpret_cast<const uint2*>(vr + 8 * dg);
+      unpack8q(u.x, u.y, vf);
+      if (vfresh)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) vf[e] = nq[1][8 * dg + e];
+    } else {
+      const bf16_t* vr = (append && kk == pos) ? qrow + 2 * C : vc + ((int64_t)bh * Tmax + kk) * DA_D;
+      load8(vr + 8 * dg, vf);
+    }
     const float pj = ps[8 * kg + j];
 #pragma unroll
     for (int e = 0; e < 8; ++e) o[e] = fmaf(pj, vf[e], o[e]);
@@ -382,19 +529,38 @@ NSA_API hipError_t nsa_kv_append(const void* qkv, void* kc, void* vc, const void
   return hipGetLastError();
 }
 
+// nsa_kv_append for int8 caches (D = 64): every K / V row of qkv is quantized (one fp32 scale
+// per row into ksc / vsc [B, H, Tmax]) and stored at its position.
+NSA_API hipError_t nsa_kv_append_kv8(const void* qkv, void* kq, void* ksc, void* vq, void* vsc, const void* pos,
+                                     int pos0, int B, int S, int H, int D, int Tmax, hipStream_t s) {
+  if (D != DA_D || B < 1 || S < 1 || H < 1 || Tmax < 1) return hipErrorInvalidValue;
+  const int64_t total = (int64_t)B * S * 2 * H * 8;
+  kv_append_kv8_kernel<<<(unsigned)((total + 255) / 256), 256, 0, s>>>(
+      (const bf16_t*)qkv, (int8_t*)kq, (float*)ksc, (int8_t*)vq, (float*)vsc, (const int64_t*)pos, pos0, B, S, H, Tmax);
+  return hipGetLastError();
+}
+
 // Single-query causal attention of the newest token (position *pos) over the caches.
 // qkv: [B, 1, 3C] (q | k | v); out: [B, C] bf16; ws: B*H*ceil(Tmax/256)*68 fp32.
 // append != 0: the new token's K / V are taken from qkv and stored at *pos (fused
 // kv_append); otherwise the caches must already hold position *pos.  out == NULL leaves
 // the partials in ws for nsa_gemv_attn.
-static hipError_t decode_attn_launch(const void* qkv, void* kc, void* vc, const void* pos, int pos_stride, void* ws,
-                                     void* out, int B, int H, int D, int Tmax, float scale, int append,
-                                     hipStream_t s) {
+// CT = int8_t: int8 caches with their per-row scales ksc / vsc (fp32 [B, H, Tmax])
+template <typename CT>
+static hipError_t decode_attn_launch(const void* qkv, void* kc, void* vc, void* ksc, void* vsc, const void* pos,
+                                     int pos_stride, void* ws, void* out, int B, int H, int D, int Tmax, float scale,
+                                     int append, hipStream_t s) {
   if (D != DA_D || B < 1 || H < 1 || Tmax < 1) return hipErrorInvalidValue;
+  CacheScales<CT> cs;
+  if constexpr (sizeof(CT) == 1) {
+    if (!ksc || !vsc) return hipErrorInvalidValue;
+    cs.k = (float*)ksc;
+    cs.v = (float*)vsc;
+  }
   const int n_split = (Tmax + DA_CHUNK - 1) / DA_CHUNK;
-  decode_attn_partial_kernel<<<dim3(B * H, n_split), 256, 0, s>>>(
-      (const bf16_t*)qkv, (const bf16_t*)kc, (const bf16_t*)vc, (bf16_t*)kc, (bf16_t*)vc, (const int64_t*)pos,
-      pos_stride, (float*)ws, H, Tmax, scale * 1.4426950408889634f, append);
+  decode_attn_partial_kernel<CT><<<dim3(B * H, n_split), 256, 0, s>>>(
+      (const bf16_t*)qkv, (const CT*)kc, (const CT*)vc, (CT*)kc, (CT*)vc, (const int64_t*)pos, pos_stride, (float*)ws,
+      H, Tmax, scale * 1.4426950408889634f, append, cs);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess || !out) return e;  // out == NULL: the consumer combines (nsa_gemv_attn)
   decode_attn_combine_kernel<<<B * H, 64, 0, s>>>((const float*)ws, (bf16_t*)out, H, n_split);
@@ -403,14 +569,29 @@ static hipError_t decode_attn_launch(const void* qkv, void* kc, void* vc, const 
 
 NSA_API hipError_t nsa_decode_attn(const void* qkv, void* kc, void* vc, const void* pos, void* ws, void* out, int B,
                                    int H, int D, int Tmax, float scale, int append, hipStream_t s) {
-  return decode_attn_launch(qkv, kc, vc, pos, 0, ws, out, B, H, D, Tmax, scale, append, s);
+  return decode_attn_launch<bf16_t>(qkv, kc, vc, nullptr, nullptr, pos, 0, ws, out, B, H, D, Tmax, scale, append, s);
 }
 
 // The same with one position per row: pos is int64[B], row b attends over keys
 // 0 .. pos[b] and (append) stores its K / V at pos[b].  Same kernels, same partials.
 NSA_API hipError_t nsa_decode_attn_rows(const void* qkv, void* kc, void* vc, const void* pos, void* ws, void* out,
                                         int B, int H, int D, int Tmax, float scale, int append, hipStream_t s) {
-  return decode_attn_launch(qkv, kc, vc, pos, 1, ws, out, B, H, D, Tmax, scale, append, s);
+  return decode_attn_launch<bf16_t>(qkv, kc, vc, nullptr, nullptr, pos, 1, ws, out, B, H, D, Tmax, scale, append, s);
+}
+
+// The same two over int8 caches: kq / vq int8 [B, H, Tmax, 64], ksc / vsc fp32 [B, H, Tmax], a
+// row standing for q * scale.  append quantizes the new token's K / V rows into them.  Same
+// grid, same partials in ws, same combine.
+NSA_API hipError_t nsa_decode_attn_kv8(const void* qkv, void* kq, void* ksc, void* vq, void* vsc, const void* pos,
+                                       void* ws, void* out, int B, int H, int D, int Tmax, float scale, int append,
+                                       hipStream_t s) {
+  return decode_attn_launch<int8_t>(qkv, kq, vq, ksc, vsc, pos, 0, ws, out, B, H, D, Tmax, scale, append, s);
+}
+
+NSA_API hipError_t nsa_decode_attn_rows_kv8(const void* qkv, void* kq, void* ksc, void* vq, void* vsc,
+                                            const void* pos, void* ws, void* out, int B, int H, int D, int Tmax,
+                                            float scale, int append, hipStream_t s) {
+  return decode_attn_launch<int8_t>(qkv, kq, vq, ksc, vsc, pos, 1, ws, out, B, H, D, Tmax, scale, append, s);
 }
 
 // pos[b] += 1 for every row with done[b] == 0 (int64[B] each): the per-row step's advance.

@@ -55,20 +55,9 @@ __device__ __forceinline__ void skinny_ln_prologue(const float* __restrict__ res
 }
 
 // ---------------------------------------------------------------------------
-// int8 -> fp32 / bf16 (two's-complement bytes, exact)
+// int8 -> bf16 (two's-complement bytes, exact; q8f / unpack8q, the fp32 forms, are in
+// decode_rows.h)
 // ---------------------------------------------------------------------------
-// byte j of a dword as a float
-__device__ __forceinline__ float q8f(uint32_t w, int j) { return (float)(int)(int8_t)(w >> (8 * j)); }
-
-// the 8 weights of two dwords (k order: byte 0 of lo first)
-__device__ __forceinline__ void unpack8q(uint32_t lo, uint32_t hi, float (&f)[8]) {
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    f[j] = q8f(lo, j);
-    f[4 + j] = q8f(hi, j);
-  }
-}
-
 // bytes j, j + 1 of a dword as a packed bf16 pair.  An int8 value has at most 7
 // significant bits, so the high half of its fp32 form is already its exact bf16: the two
 // high halves are packed by one byte permute, without a rounding convert.

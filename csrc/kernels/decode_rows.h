@@ -15,6 +15,21 @@ namespace {
 constexpr int DA_D = 64;        // head dim of the decode-attention kernel
 constexpr int DA_PO = 4;          // o[] offset in a partial: 16-byte aligned for vector reads
 constexpr int DA_PART = DA_PO + DA_D;  // m, l, (pad), o[64]
+constexpr int DA_CHUNK = 256;   // keys per workgroup of the attention partial kernel (one per thread)
+
+// int8 -> fp32 (two's-complement bytes, exact): the int8 weights of decode_q8.hip and the
+// int8 KV-cache rows of decode.hip
+// byte j of a dword as a float
+__device__ __forceinline__ float q8f(uint32_t w, int j) { return (float)(int)(int8_t)(w >> (8 * j)); }
+
+// the 8 values of two dwords (k order: byte 0 of lo first)
+__device__ __forceinline__ void unpack8q(uint32_t lo, uint32_t hi, float (&f)[8]) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    f[j] = q8f(lo, j);
+    f[4 + j] = q8f(hi, j);
+  }
+}
 
 // Single-row decode linear with its input's producer in the prologue: every workgroup
 // builds the row x[K] (bf16-rounded, in LDS) itself, then streams its NC weight rows:

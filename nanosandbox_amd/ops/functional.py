@@ -906,28 +906,91 @@ def attention(qkv, n_head: int, p: float, training: bool):
 # (runtime/decode.py; csrc/kernels/decode.hip).  Inference only (no autograd).
 # ----------------------------------------------------------------------------
 
+class QuantCache(NamedTuple):
+    """An int8 K or V cache: ``q`` int8 [B, H, Tmax, D] and ``scale`` fp32 [B, H, Tmax], one
+    scale per cache row; row (b, h, t) stands for ``q[b, h, t] * scale[b, h, t]``
+    (``dequantize_cache``).  ``kv_append`` and ``decode_attention`` take one wherever they take
+    a bf16 cache."""
+    q: torch.Tensor
+    scale: torch.Tensor
+
+    @property
+    def shape(self):
+        return self.q.shape
+
+
+def quantize_cache_rows(x) -> QuantCache:
+    """Per-row symmetric int8 over the last dimension, in fp32: scale = absmax / 127 (1 for an
+    all-zero row), q = clamp(rint(x / scale), -127, 127) with a true division and
+    round-half-to-even: ``quantize_rows_int8``'s rule per cache row.  Plain torch; on the CPU
+    it is the reference the int8-cache kernels match bit for bit."""
+    xf = x.detach().float()
+    absmax = xf.abs().amax(dim=-1)
+    # a tensor divisor: a Python scalar may be turned into a multiplication by its reciprocal
+    scale = torch.where(absmax > 0, absmax / torch.full_like(absmax, 127), torch.ones_like(absmax))
+    q = torch.clamp(torch.round(xf / scale[..., None]), -127, 127).to(torch.int8).contiguous()
+    return QuantCache(q, scale.contiguous())
+
+
+def dequantize_cache(qc: QuantCache) -> torch.Tensor:
+    """The fp32 rows a ``QuantCache`` stands for: q * scale[..., None]."""
+    return qc.q.float() * qc.scale[..., None]
+
+
+def _cache_store(c, index, rows):
+    """cache[index] = rows ([..., S, D]); a ``QuantCache`` stores them quantized."""
+    if isinstance(c, QuantCache):
+        qc = quantize_cache_rows(rows)
+        c.q[index] = qc.q
+        c.scale[index] = qc.scale
+    else:
+        c[index] = rows.to(c.dtype)
+
+
+def _cache_rows(c, index):
+    """cache[index] as fp32 rows (a ``QuantCache``: dequantized)."""
+    if isinstance(c, QuantCache):
+        return dequantize_cache(QuantCache(c.q[index], c.scale[index]))
+    return c[index].float()
+
+
 def kv_append(qkv, kc, vc, pos=None, pos0: int = 0):
     """Write the K / V rows of ``qkv`` [B, S, 3C] into the caches [B, H, Tmax, D] at
     positions p0 .. p0+S-1, p0 = ``pos`` (int64 device tensor, graph-safe) or ``pos0``.
-    ``pos`` with one entry per row (B > 1) places every row at its own p0 (eager torch)."""
+    ``pos`` with one entry per row (B > 1) places every row at its own p0 (eager torch).
+    ``kc`` / ``vc`` may be ``QuantCache``s: every row is stored quantized
+    (``quantize_cache_rows``; GPU, bf16, D = 64: ``nsa_kv_append_kv8``)."""
     B, S, C3 = qkv.shape
     _, H, Tmax, D = kc.shape
+    kv8 = isinstance(kc, QuantCache)
+    assert kv8 == isinstance(vc, QuantCache), "K and V caches of one form"
     if pos is not None and pos.numel() > 1:
         assert pos.numel() == B
+        if kv8 and qkv.is_cuda and qkv.dtype == BF16 and D == 64:  # the kernel, row by row
+            qkv = qkv.contiguous()
+            for b, p0 in enumerate(pos.tolist()):
+                _lib.call("nsa_kv_append_kv8", _lib.ptr(qkv[b]), _lib.ptr(kc.q[b]), _lib.ptr(kc.scale[b]),
+                          _lib.ptr(vc.q[b]), _lib.ptr(vc.scale[b]), None, int(p0), 1, S, H, D, Tmax, _lib.stream())
+            return
         k, v = qkv.view(B, S, 3, H, D)[:, :, 1:].permute(2, 0, 3, 1, 4)
         for b, p0 in enumerate(pos.tolist()):
-            kc[b, :, p0:p0 + S] = k[b].to(kc.dtype)
-            vc[b, :, p0:p0 + S] = v[b].to(vc.dtype)
+            _cache_store(kc, (b, slice(None), slice(p0, p0 + S)), k[b])
+            _cache_store(vc, (b, slice(None), slice(p0, p0 + S)), v[b])
         return
-    if qkv.is_cuda and qkv.dtype == BF16 and D % 8 == 0:
+    if kv8 and qkv.is_cuda and qkv.dtype == BF16 and D == 64:
+        qkv = qkv.contiguous()
+        _lib.call("nsa_kv_append_kv8", _lib.ptr(qkv), _lib.ptr(kc.q), _lib.ptr(kc.scale), _lib.ptr(vc.q),
+                  _lib.ptr(vc.scale), _lib.ptr(pos), int(pos0), B, S, H, D, Tmax, _lib.stream())
+        return
+    if not kv8 and qkv.is_cuda and qkv.dtype == BF16 and D % 8 == 0:
         qkv = qkv.contiguous()
         _lib.call("nsa_kv_append", _lib.ptr(qkv), _lib.ptr(kc), _lib.ptr(vc), _lib.ptr(pos), int(pos0), B, S, H, D,
                   Tmax, _lib.stream())
         return
     p0 = int(pos.item()) if pos is not None else int(pos0)
     k, v = qkv.view(B, S, 3, H, D)[:, :, 1:].permute(2, 0, 3, 1, 4)
-    kc[:, :, p0:p0 + S] = k.to(kc.dtype)
-    vc[:, :, p0:p0 + S] = v.to(vc.dtype)
+    _cache_store(kc, (slice(None), slice(None), slice(p0, p0 + S)), k)
+    _cache_store(vc, (slice(None), slice(None), slice(p0, p0 + S)), v)
 
 
 class AttnPartials(NamedTuple):
@@ -947,20 +1010,31 @@ def decode_attention(qkv, kc, vc, pos, n_head: int, append: bool = False, combin
     ``append``: also store the token's K / V at its position
     (the fused form of ``kv_append``).  GPU (head dim 64): split-K flash-decoding
     kernels; otherwise fp32 torch (CPU reference).  ``combine=False`` with one row on the
-    GPU returns the partials (``AttnPartials``) for ``decode_linear`` to combine."""
+    GPU returns the partials (``AttnPartials``) for ``decode_linear`` to combine.
+
+    ``kc`` / ``vc`` may be ``QuantCache``s (int8 rows with one scale each): the token's K / V
+    are appended quantized and it attends over the dequantized rows 0 .. pos, its own
+    included, so the result depends on the cache contents only and ``append=True`` equals
+    ``kv_append`` followed by ``append=False`` bit for bit.  GPU, bf16, D = 64: the ``_kv8``
+    forms of the same kernels (same partials); anything else: this function's fp32 torch
+    path over ``dequantize_cache``."""
     B, S, C3 = qkv.shape
     C = C3 // 3
     _, H, Tmax, D = kc.shape
     scale = 1.0 / math.sqrt(D)
     per_row = pos.numel() > 1
     assert pos.numel() == (B if per_row else 1), "pos holds one position, or one per row"
+    kv8 = isinstance(kc, QuantCache)
+    assert kv8 == isinstance(vc, QuantCache), "K and V caches of one form"
     if qkv.is_cuda and qkv.dtype == BF16 and D == 64:
         qkv = qkv.contiguous()
         n_split = -(-Tmax // 256)
         ws = torch.empty(B * H * n_split * (4 + D), device=qkv.device, dtype=F32)  # (m, l, pad, o[D]) per chunk
         partial = not combine and B == 1 and GEMV_MAX_ROWS >= 1 and C <= 8192
         out = None if partial else torch.empty(B, 1, C, device=qkv.device, dtype=qkv.dtype)
-        _lib.call("nsa_decode_attn_rows" if per_row else "nsa_decode_attn", _lib.ptr(qkv), _lib.ptr(kc), _lib.ptr(vc),
+        name = "nsa_decode_attn_rows" if per_row else "nsa_decode_attn"
+        caches = (kc.q, kc.scale, vc.q, vc.scale) if kv8 else (kc, vc)
+        _lib.call(name + ("_kv8" if kv8 else ""), _lib.ptr(qkv), *map(_lib.ptr, caches),
                   _lib.ptr(pos), _lib.ptr(ws), _lib.ptr(out), B, H, D, Tmax, scale, 1 if append else 0, _lib.stream())
         return AttnPartials(ws, n_split, C) if partial else out
     if append:
@@ -969,13 +1043,14 @@ def decode_attention(qkv, kc, vc, pos, n_head: int, append: bool = False, combin
     if per_row:  # every row over its own context (eager by construction: pos is read back)
         y = torch.empty(B, H, D, dtype=F32, device=qkv.device)
         for b, p in enumerate(pos.tolist()):
-            k, v = kc[b, :, :p + 1].float(), vc[b, :, :p + 1].float()      # [H, p+1, D]
+            k = _cache_rows(kc, (b, slice(None), slice(0, p + 1)))            # [H, p+1, D]
+            v = _cache_rows(vc, (b, slice(None), slice(0, p + 1)))
             att = torch.softmax(torch.einsum("hd,hkd->hk", q[b], k) * scale, dim=-1)
             y[b] = torch.einsum("hk,hkd->hd", att, v)
         return y.reshape(B, 1, C).to(qkv.dtype)
     p = int(pos.item())
-    k = kc[:, :, :p + 1].float()                                 # [B, H, p+1, D]
-    v = vc[:, :, :p + 1].float()
+    k = _cache_rows(kc, (slice(None), slice(None), slice(0, p + 1)))           # [B, H, p+1, D]
+    v = _cache_rows(vc, (slice(None), slice(None), slice(0, p + 1)))
     att = torch.softmax(torch.einsum("bhd,bhkd->bhk", q, k) * scale, dim=-1)
     y = torch.einsum("bhk,bhkd->bhd", att, v)
     return y.reshape(B, 1, C).to(qkv.dtype)

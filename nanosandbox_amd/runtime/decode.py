@@ -39,6 +39,16 @@ model's (``ops.quantize_rows_int8``): every step streams int8 weights through th
 ``_q8`` forms of the same kernels (half the bytes, the same launches, the same captured
 graph), and prefill and the embedding read the dequantized weights through the
 ``compute`` shadows, so prompt and steps see one model.
+``Decoder(..., kv_quantize="int8")`` keeps the caches as int8 rows with one fp32 scale per
+row (``ops.QuantCache``: 68 bytes per K or V row instead of 128, so a step reads 0.53x the
+cache bytes and the caches take 0.53x the memory).  The prompt goes through flash attention
+on its own unquantized K / V as always and its rows are then stored quantized
+(``ops.quantize_cache_rows``); every step quantizes the new token's K / V rows, appends them
+and attends over the dequantized rows 0 .. pos, its own included, so a step is a function of
+the cache contents.  Unlike the int8-weight mode, prompt and steps therefore do not see one
+model: the prompt's own attention is unquantized, the usual practice for KV quantization.
+Any batch size, per_row or not, with or without ``quantize="int8"``; same launches, same
+captured graph (the ``_kv8`` forms of the append and attention kernels).
 The caches hold at most ``block_size`` positions; ``GPT.generate_cached`` falls
 back to the recompute loop when prompt + new tokens exceed that (nanoGPT crops the
 context there, which a cache cannot do without re-encoding).
@@ -53,13 +63,20 @@ from .. import ops
 
 class Decoder:
     def __init__(self, model, batch_size: int, max_len: int | None = None, use_graph: bool | None = None,
-                 per_row: bool = False, quantize: str | None = None):
+                 per_row: bool = False, quantize: str | None = None, kv_quantize: str | None = None):
         if quantize not in (None, "int8"):
             raise ValueError(f"quantize must be None or 'int8', got {quantize!r}")
+        if kv_quantize not in (None, "int8"):
+            raise ValueError(f"kv_quantize must be None or 'int8', got {kv_quantize!r}")
         self.model = model
         self.per_row = per_row
         self.quantize = quantize
+        self.kv_quantize = kv_quantize
         cfg = model.config
+        if kv_quantize and model.lm_head.weight.is_cuda and not self.graph_capable(model):
+            # the int8-cache kernels are the head_dim-64 bf16 ones; no silent torch step instead
+            raise ValueError("kv_quantize='int8' needs the fused decode kernels on the GPU: head_dim 64, "
+                             "bfloat16 compute and a vocabulary of at most 53248")
         if quantize and model.lm_head.weight.is_cuda:
             # the int8 kernels are the single-row and skinny ones; there is no int8 form of the
             # larger-batch GEMMs or of the fallback ops, and no silent bf16 step instead
@@ -79,8 +96,15 @@ class Decoder:
         self.dtype = model.compute_dtype
         self.rdtype = model.residual_dtype
         shape = (batch_size, self.H, self.T, self.D)
-        self.kc = [torch.zeros(shape, device=self.device, dtype=self.dtype) for _ in range(cfg.n_layer)]
-        self.vc = [torch.zeros(shape, device=self.device, dtype=self.dtype) for _ in range(cfg.n_layer)]
+        if kv_quantize:  # int8 rows + one fp32 scale per row (a zero row: bytes 0, scale 1)
+            def cache():
+                return ops.QuantCache(torch.zeros(shape, device=self.device, dtype=torch.int8),
+                                      torch.ones(shape[:3], device=self.device, dtype=torch.float32))
+        else:
+            def cache():
+                return torch.zeros(shape, device=self.device, dtype=self.dtype)
+        self.kc = [cache() for _ in range(cfg.n_layer)]
+        self.vc = [cache() for _ in range(cfg.n_layer)]
         # position of the token being fed: one for the whole batch, or (per_row) one per sequence
         self.pos = torch.zeros(batch_size if per_row else 1, device=self.device, dtype=torch.int64)
         # per_row: done[b] != 0 once row b has drawn the stop token; such a row is frozen (it is
@@ -395,11 +419,14 @@ def sample_next(logits: torch.Tensor, temperature: float = 1.0, top_k: int | Non
 def generate_cached(model, idx: torch.Tensor, max_new_tokens: int, temperature: float = 1.0,
                     top_k: int | None = None, use_graph: bool | None = None,
                     decoder: "Decoder | None" = None, top_p: float | None = None,
-                    min_p: float | None = None, quantize: str | None = None) -> torch.Tensor:
+                    min_p: float | None = None, quantize: str | None = None,
+                    kv_quantize: str | None = None) -> torch.Tensor:
     """``model.generate`` with KV caches: same sampling, one token's forward per new token.
 
     ``quantize="int8"``: decode with int8 weights (``Decoder(..., quantize="int8")``); the
     recompute fallback cannot, so a prompt + new tokens past block_size raises ValueError.
+    ``kv_quantize="int8"``: int8 KV caches (``Decoder(..., kv_quantize="int8")``); the
+    recompute loop has no cache, so the same case raises ValueError as well.
 
     ``decoder``: a Decoder to reuse across calls (same batch size): its weight shadows and
     captured graphs survive, so ``sample.py``'s num_samples loop captures once.  The caller
@@ -410,15 +437,21 @@ def generate_cached(model, idx: torch.Tensor, max_new_tokens: int, temperature: 
         return idx
     if quantize not in (None, "int8"):
         raise ValueError(f"quantize must be None or 'int8', got {quantize!r}")
+    if kv_quantize not in (None, "int8"):
+        raise ValueError(f"kv_quantize must be None or 'int8', got {kv_quantize!r}")
     if T0 + max_new_tokens - 1 > model.config.block_size:
         if quantize:
             raise ValueError("quantize needs the KV-cache path: prompt + new tokens exceed block_size, and the "
                              "recompute loop runs the unquantized model")
+        if kv_quantize:
+            raise ValueError("kv_quantize needs the KV-cache path: prompt + new tokens exceed block_size, and the "
+                             "recompute loop has no cache to quantize")
         # the caches hold block_size positions; nanoGPT crops the context beyond that
         return model.generate(idx, max_new_tokens, temperature=temperature, top_k=top_k, top_p=top_p, min_p=min_p)
-    own = decoder is None or decoder.B != B or decoder.quantize != quantize
-    dec = (Decoder(model, B, max_len=model.config.block_size, use_graph=use_graph, quantize=quantize) if own
-           else decoder)
+    own = (decoder is None or decoder.B != B or decoder.quantize != quantize
+           or decoder.kv_quantize != kv_quantize)
+    dec = (Decoder(model, B, max_len=model.config.block_size, use_graph=use_graph, quantize=quantize,
+                   kv_quantize=kv_quantize) if own else decoder)
     try:
         dec.reseed()  # every call draws its own samples, also on a reused decoder / graph
         dec.sample_into(dec.prefill(idx), temperature, top_k, None, top_p, min_p)  # pos = T0: gen[:, T0]
@@ -441,7 +474,8 @@ def _cut_at_stop(new: torch.Tensor, stop_token: int | None) -> torch.Tensor:
 def generate_batch(model, prompts, max_new_tokens: int, temperature: float = 1.0, top_k: int | None = None,
                    stop_token: int | None = None, use_graph: bool | None = None,
                    decoder: "Decoder | None" = None, top_p: float | None = None,
-                   min_p: float | None = None, quantize: str | None = None) -> list[torch.Tensor]:
+                   min_p: float | None = None, quantize: str | None = None,
+                   kv_quantize: str | None = None) -> list[torch.Tensor]:
     """Generate for a list of prompts of unequal lengths as one batch.
 
     ``prompts``: 1-D token tensors, each of length >= 1.  Every result is its prompt followed
@@ -454,9 +488,12 @@ def generate_batch(model, prompts, max_new_tokens: int, temperature: float = 1.0
 
     ``decoder``: a per_row Decoder of the right batch size to reuse across calls (weight
     shadows and captured graphs survive); the caller releases it.  ``quantize="int8"``:
-    int8 weights; a row that needs the recompute loop then raises ValueError."""
+    int8 weights; a row that needs the recompute loop then raises ValueError.
+    ``kv_quantize="int8"``: int8 KV caches, with the same refusal."""
     if quantize not in (None, "int8"):
         raise ValueError(f"quantize must be None or 'int8', got {quantize!r}")
+    if kv_quantize not in (None, "int8"):
+        raise ValueError(f"kv_quantize must be None or 'int8', got {kv_quantize!r}")
     if stop_token is not None and stop_token < 0:
         stop_token = None
     top_p, min_p = sampling_filters(top_p, min_p)
@@ -471,7 +508,8 @@ def generate_batch(model, prompts, max_new_tokens: int, temperature: float = 1.0
     for i, p in enumerate(prompts):
         if i not in rows:
             y = generate_cached(model, p.to(device)[None], max_new_tokens, temperature=temperature, top_k=top_k,
-                                use_graph=use_graph, top_p=top_p, min_p=min_p, quantize=quantize)[0]
+                                use_graph=use_graph, top_p=top_p, min_p=min_p, quantize=quantize,
+                                kv_quantize=kv_quantize)[0]
             outs[i] = torch.cat([y[:p.numel()], _cut_at_stop(y[p.numel():], stop_token)])
     if not rows:
         return outs
@@ -480,8 +518,10 @@ def generate_batch(model, prompts, max_new_tokens: int, temperature: float = 1.0
     idx = torch.zeros(B, max(lens), dtype=torch.int64, device=device)  # right-padded (any valid id)
     for b, i in enumerate(rows):
         idx[b, :lens[b]] = prompts[i]
-    own = decoder is None or decoder.B != B or not decoder.per_row or decoder.quantize != quantize
-    dec = Decoder(model, B, max_len=T, use_graph=use_graph, per_row=True, quantize=quantize) if own else decoder
+    own = (decoder is None or decoder.B != B or not decoder.per_row or decoder.quantize != quantize
+           or decoder.kv_quantize != kv_quantize)
+    dec = (Decoder(model, B, max_len=T, use_graph=use_graph, per_row=True, quantize=quantize,
+                   kv_quantize=kv_quantize) if own else decoder)
     try:
         dec.reseed()
         logits = dec.prefill(idx, torch.tensor(lens, dtype=torch.int64, device=device))

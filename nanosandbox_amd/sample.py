@@ -15,7 +15,8 @@ batch of unequal lengths, ``--stop_token=ID`` ends a sample at that token
 ``--top_p=0.9`` (nucleus) and ``--min_p=0.05`` narrow the sampled set on top of ``top_k``
 (``--top_k=0``: no top-k); on the GPU the selection runs inside the sampling kernel.
 ``--quantize=int8`` decodes with int8 weight-only linears (per-row scales; the KV-cache
-path only, so it refuses ``--kv_cache=False``).
+path only, so it refuses ``--kv_cache=False``).  ``--kv_quantize=int8`` keeps the KV caches
+as int8 rows with one scale each (the same refusal).
 """
 
 from __future__ import annotations
@@ -51,6 +52,7 @@ SAMPLE_DEFAULTS = dict(
     prompts_file="",  # one prompt per line, generated as one ragged batch per sample round (start is ignored)
     stop_token=-1,  # token id that ends a sample (printed text ends before it); -1: none
     quantize="",  # "int8": int8 weight-only decoding on the KV-cache path (Decoder(quantize="int8")); "": off
+    kv_quantize="",  # "int8": int8 KV caches, one scale per cache row (Decoder(kv_quantize="int8")); "": off
 )
 
 
@@ -59,6 +61,7 @@ def _generate_batches(model, c, encode, decode, start, device):
     ``GPT.generate_batch`` (one per_row decoder per batch size, kept across batches)."""
     stop = c["stop_token"] if c["stop_token"] >= 0 else None
     quantize = c["quantize"] or None
+    kv_quantize = c["kv_quantize"] or None
     if c["prompts_file"]:
         with open(c["prompts_file"], "r", encoding="utf-8") as f:
             texts = [ln.rstrip("\n") for ln in f if ln.strip()]
@@ -74,10 +77,11 @@ def _generate_batches(model, c, encode, decode, start, device):
                 from .runtime.decode import Decoder
                 B = len(prompts)
                 if B not in decs:
-                    decs[B] = Decoder(model, B, max_len=model.config.block_size, per_row=True, quantize=quantize)
+                    decs[B] = Decoder(model, B, max_len=model.config.block_size, per_row=True, quantize=quantize,
+                                      kv_quantize=kv_quantize)
                 ys = model.generate_batch(prompts, c["max_new_tokens"], temperature=c["temperature"], top_k=c["top_k"],
                                           stop_token=stop, decoder=decs[B], top_p=c["top_p"], min_p=c["min_p"],
-                                          quantize=quantize)
+                                          quantize=quantize, kv_quantize=kv_quantize)
             else:
                 ys = [model.generate(p[None], c["max_new_tokens"], temperature=c["temperature"], top_k=c["top_k"],
                                      top_p=c["top_p"], min_p=c["min_p"])[0] for p in prompts]
@@ -127,7 +131,13 @@ def main(argv=None):
     if c["quantize"] and not c["kv_cache"]:
         raise ValueError("--quantize needs the KV-cache path: the recompute loop (--kv_cache=False) runs the "
                          "unquantized model")
+    if c["kv_quantize"] not in ("", "int8"):
+        raise ValueError(f"kv_quantize must be '' or 'int8', got {c['kv_quantize']!r}")
+    if c["kv_quantize"] and not c["kv_cache"]:
+        raise ValueError("--kv_quantize needs the KV-cache path: the recompute loop (--kv_cache=False) has no "
+                         "cache to quantize")
     quantize = c["quantize"] or None
+    kv_quantize = c["kv_quantize"] or None
     torch.manual_seed(c["seed"])
     device = c["device"]
     if device.startswith("cuda") and not torch.cuda.is_available():
@@ -159,13 +169,15 @@ def main(argv=None):
         # one decoder for all samples: weight shadows and the captured step graph are
         # built once, not per sample
         from .runtime.decode import Decoder
-        dec = Decoder(model, x.shape[0], max_len=model.config.block_size, quantize=quantize)
+        dec = Decoder(model, x.shape[0], max_len=model.config.block_size, quantize=quantize,
+                      kv_quantize=kv_quantize)
     try:
         with torch.no_grad():
             for _ in range(c["num_samples"]):
                 if dec is not None:
                     y = model.generate_cached(x, c["max_new_tokens"], temperature=c["temperature"], top_k=c["top_k"],
-                                              decoder=dec, top_p=c["top_p"], min_p=c["min_p"], quantize=quantize)
+                                              decoder=dec, top_p=c["top_p"], min_p=c["min_p"], quantize=quantize,
+                                              kv_quantize=kv_quantize)
                 else:
                     y = model.generate(x, c["max_new_tokens"], temperature=c["temperature"], top_k=c["top_k"],
                                        top_p=c["top_p"], min_p=c["min_p"])

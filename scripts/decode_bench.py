@@ -17,6 +17,13 @@ times sample.py's flow for N samples of one prompt: a reused batch-1 decoder N t
 (``sample_loop``) against one ``generate_batch`` of N rows (``sample_batch``).
 ``--quantize int8`` adds ``graph_int8`` / ``rows_int8``, the ``graph`` / ``rows`` modes on a
 ``Decoder(quantize="int8")``, next to their bf16 twins in the interleaved mode list.
+``--kv_quantize int8`` adds ``graph_kv8`` / ``rows_kv8`` (int8 KV caches,
+``Decoder(kv_quantize="int8")``) and, with ``--quantize int8``, ``graph_int8_kv8`` /
+``rows_int8_kv8``, each next to its twin; ``--prompt`` sets the context length the steps start
+from; a cached run feeds positions prompt .. prompt + new, which must stay below block_size
+(``--prompt 896 --new 127`` ends at position 1023).  ``--memory`` adds the decoder's peak
+allocated bytes (``torch.cuda.max_memory_allocated`` over construction, prefill and the timed
+steps, minus what was allocated before) to each line.
 """
 
 import argparse
@@ -35,9 +42,9 @@ SMP = dict(top_k=200, top_p=None, min_p=None)  # the sampling settings of every 
 DIMS = {"gpt2": (12, 12, 768), "gpt2-medium": (24, 16, 1024), "gpt2-large": (36, 20, 1280), "gpt2-xl": (48, 25, 1600)}
 
 
-def run_cached(model, idx, new, use_graph, quantize=None):
+def run_cached(model, idx, new, use_graph, quantize=None, kv_quantize=None):
     B = idx.shape[0]
-    dec = Decoder(model, B, use_graph=use_graph, quantize=quantize)
+    dec = Decoder(model, B, use_graph=use_graph, quantize=quantize, kv_quantize=kv_quantize)
     dec.sample_into(dec.prefill(idx), 0.8, **SMP)
     if use_graph:
         dec.run(1, 0.8, **SMP)  # capture outside the timed loop
@@ -60,10 +67,10 @@ def ragged_lengths(B, prompt):
     return [prompt if B == 1 else lo + (prompt - lo) * b // (B - 1) for b in range(B)]
 
 
-def run_rows(model, idx, new, lengths=None, quantize=None):
+def run_rows(model, idx, new, lengths=None, quantize=None, kv_quantize=None):
     """The graph mode on a per_row decoder: equal lengths, or (lengths) a ragged batch."""
     B = idx.shape[0]
-    dec = Decoder(model, B, use_graph=True, per_row=True, quantize=quantize)
+    dec = Decoder(model, B, use_graph=True, per_row=True, quantize=quantize, kv_quantize=kv_quantize)
     lens = None if lengths is None else torch.tensor(lengths, device=idx.device)
     dec.sample_into(dec.prefill(idx, lens), 0.8, **SMP)
     dec.run(1, 0.8, **SMP)  # capture outside the timed loop
@@ -116,6 +123,10 @@ def main():
     ap.add_argument("--calibrate", action="store_true", help="first print the box calibration GEMM (utils/boxcal.py)")
     ap.add_argument("--quantize", default="", choices=["", "int8"],
                     help="int8: add int8 weight-only twins of the graph and rows modes (graph_int8, rows_int8)")
+    ap.add_argument("--kv_quantize", default="", choices=["", "int8"],
+                    help="int8: add int8-KV-cache twins of the graph and rows modes (graph_kv8, rows_kv8; with "
+                         "--quantize int8 also graph_int8_kv8, rows_int8_kv8)")
+    ap.add_argument("--memory", action="store_true", help="add each run's peak allocated bytes (decoder_peak_mb)")
     ap.add_argument("--top_k", type=int, default=200, help="0: no top-k")
     ap.add_argument("--top_p", type=float, default=1.0, help="nucleus mass; 1.0: off")
     ap.add_argument("--min_p", type=float, default=0.0, help="floor relative to the most likely token; 0.0: off")
@@ -130,6 +141,13 @@ def main():
     modes = [m for m in modes if m]
     if a.quantize:  # each int8 twin right after its bf16 mode
         modes = [t for m in modes for t in ([m, f"{m}_{a.quantize}"] if m in ("graph", "rows") else [m])]
+    if a.kv_quantize:  # each int8-cache twin right after its mode (the int8-weight twins included)
+        modes = [t for m in modes for t in ([m, f"{m}_kv8"] if m.partition("_")[0] in ("graph", "rows") else [m])]
+    block_size = GPTConfig().block_size
+    if any(m != "recompute" for m in modes) and a.prompt + a.new >= block_size:
+        # a cached run feeds positions prompt .. prompt + new (one capture step, then --new timed
+        # ones); the position table and the caches end at block_size - 1
+        ap.error(f"--prompt + --new must stay below block_size ({block_size}): the last fed position is their sum")
     modes = modes * a.repeat
     for name in a.models.split(","):
         L, H, C = DIMS[name]
@@ -140,24 +158,31 @@ def main():
             idx = torch.randint(0, 50257, (B, a.prompt), device="cuda")
             with torch.no_grad():
                 for mode in modes:
-                    base, _, qz = mode.partition("_")  # graph_int8 -> (graph, int8)
-                    qz = qz or None
+                    base, *sfx = mode.split("_")  # graph_int8_kv8 -> graph, int8 weights, int8 caches
+                    qz = "int8" if "int8" in sfx else None
+                    kvq = "int8" if "kv8" in sfx else None
+                    if a.memory:
+                        torch.cuda.synchronize()
+                        torch.cuda.reset_peak_memory_stats()
+                        mem0 = torch.cuda.memory_allocated()
                     if base in ("rows", "ragged"):
                         n = a.new
                         lens = ragged_lengths(B, a.prompt) if base == "ragged" else None
-                        run_rows(model, idx, 4, lens, qz)
-                        dt = run_rows(model, idx, n, lens, qz)
+                        run_rows(model, idx, 4, lens, qz, kvq)
+                        dt = run_rows(model, idx, n, lens, qz, kvq)
                     elif mode == "recompute":
                         run_recompute(model, idx, 2)  # warm-up (tuner, allocator)
                         n = a.recompute_new
                         dt = run_recompute(model, idx, n)
                     else:
                         n = a.new
-                        run_cached(model, idx, 4, base == "graph", qz)
-                        dt = run_cached(model, idx, n, base == "graph", qz)
+                        run_cached(model, idx, 4, base == "graph", qz, kvq)
+                        dt = run_cached(model, idx, n, base == "graph", qz, kvq)
+                    mem = ({"decoder_peak_mb": round((torch.cuda.max_memory_allocated() - mem0) / 2 ** 20, 1)}
+                           if a.memory else {})
                     print(json.dumps({"model": name, "batch": B, "mode": mode, "prompt": a.prompt, "new_tokens": n,
                                       "tokens_per_s": round(B * n / dt, 1), "ms_per_token": round(dt / n * 1e3, 3),
-                                      **extra}),
+                                      **mem, **extra}),
                           flush=True)
         if a.samples:
             prompt = torch.randint(0, 50257, (a.prompt,), device="cuda")
