@@ -379,26 +379,28 @@ class GPT(nn.Module):
 
     @torch.no_grad()
     def generate_cached(self, idx, max_new_tokens, temperature=1.0, top_k=None, use_graph=None, decoder=None,
-                        top_p=None, min_p=None, quantize=None, kv_quantize=None):
+                        top_p=None, min_p=None, quantize=None, kv_quantize=None, shared_prompt=False):
         """``generate`` with per-layer KV caches: the prompt is encoded once and every
         new token runs one position through the model (a replayed HIP graph on the GPU;
         ``runtime/decode.py``).  Same sampling; falls back to ``generate`` when prompt +
         new tokens exceed block_size.  ``quantize="int8"``: int8 weight-only decoding;
         ``kv_quantize="int8"``: int8 KV caches (either: no fallback, ValueError past
-        block_size)."""
+        block_size).  ``shared_prompt=True``: the rows of ``idx`` are one prompt, cached once
+        for the whole batch (equal rows or ValueError; no fallback either)."""
         from ..runtime.decode import generate_cached
         return generate_cached(self, idx, max_new_tokens, temperature=temperature, top_k=top_k, use_graph=use_graph,
                                decoder=decoder, top_p=top_p, min_p=min_p, quantize=quantize,
-                               kv_quantize=kv_quantize)
+                               kv_quantize=kv_quantize, shared_prompt=shared_prompt)
 
     @torch.no_grad()
     def generate_batch(self, prompts, max_new_tokens, temperature=1.0, top_k=None, stop_token=None, use_graph=None,
-                       decoder=None, top_p=None, min_p=None, quantize=None, kv_quantize=None):
+                       decoder=None, top_p=None, min_p=None, quantize=None, kv_quantize=None, shared_prompt=False):
         """``generate_cached`` for a list of 1-D prompts of unequal lengths, decoded as one
         batch with a position per row; returns a list of 1-D tensors (prompt + new tokens).
         A row that draws ``stop_token`` ends with it; the others get exactly
-        ``max_new_tokens`` new tokens (``runtime/decode.py``)."""
+        ``max_new_tokens`` new tokens (``runtime/decode.py``).  ``shared_prompt=True``: the
+        prompts are all the same one, encoded and cached once for the batch."""
         from ..runtime.decode import generate_batch
         return generate_batch(self, prompts, max_new_tokens, temperature=temperature, top_k=top_k,
                               stop_token=stop_token, use_graph=use_graph, decoder=decoder, top_p=top_p, min_p=min_p,
-                              quantize=quantize, kv_quantize=kv_quantize)
+                              quantize=quantize, kv_quantize=kv_quantize, shared_prompt=shared_prompt)

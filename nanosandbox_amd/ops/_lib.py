@@ -111,6 +111,12 @@ _SIGNATURES = {
                             c_int, c_int, c_int, c_float, c_int, c_void_p],
     "nsa_decode_attn_rows_kv8": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                  c_int, c_int, c_int, c_int, c_float, c_int, c_void_p],
+    # shared prompt cache + per-row caches (csrc/kernels/decode_shared.hip): qkv, pk, pv, kc, vc, plen, pos, ws,
+    # out, B, H, Tp, R, scale, append
+    "nsa_decode_attn_shared": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                               c_void_p, c_int, c_int, c_int, c_int, c_float, c_int, c_void_p],
+    "nsa_decode_attn_shared_rows": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                    c_void_p, c_int, c_int, c_int, c_int, c_float, c_int, c_void_p],
     "nsa_flash_bwd2": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                        c_int, c_int, c_int, c_int, c_float, c_float, c_uint64, c_void_p],
     "nsa_rng_advance": [c_void_p],

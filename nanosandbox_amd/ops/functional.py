@@ -1056,6 +1056,59 @@ def decode_attention(qkv, kc, vc, pos, n_head: int, append: bool = False, combin
     return y.reshape(B, 1, C).to(qkv.dtype)
 
 
+SHARED_PROMPT_CHUNK = 128  # prompt keys per workgroup of the shared-prompt attention kernel
+
+
+def decode_attention_shared(qkv, pkc, pvc, kc, vc, plen, pos, n_head: int, append: bool = False):
+    """``decode_attention`` for a batch whose rows share one prompt: qkv [B, 1, 3C] -> [B, 1, C].
+
+    ``pkc`` / ``pvc`` [1, H, Tp, D] hold the prompt's K / V once (keys 0 .. P - 1, ``P = plen``:
+    an int64 device tensor with one entry) and ``kc`` / ``vc`` [B, H, R, D] the tokens every row
+    generated itself: row b's token at absolute position p >= P lives in slot p - P.  ``pos``
+    (int64 device tensor, one entry or B entries) is the absolute position of the newest
+    token; row b attends over prompt keys 0 .. P - 1 followed by its slots 0 .. pos[b] - P.
+    ``append``: also store the token's K / V at slot pos[b] - P (a slot >= R stores nothing and
+    the row attends over the prompt only).  The prompt caches are never written.
+
+    GPU, bf16, D = 64: one launch of ``nsa_decode_attn_shared`` (a workgroup per (head,
+    128-key prompt chunk) serving every row on the matrix cores, plus the per-row chunk body
+    of ``decode_attention`` on the row caches) and a combine over the same partials.  Anything else:
+    fp32 torch over the concatenated keys (the reference; bf16 caches only)."""
+    B, S, C3 = qkv.shape
+    C = C3 // 3
+    _, H, Tp, D = pkc.shape
+    R = kc.shape[2]
+    assert S == 1 and H == n_head and pkc.shape[0] == 1 and kc.shape[0] == B and kc.shape[1] == H and kc.shape[3] == D
+    assert not isinstance(kc, QuantCache) and not isinstance(pkc, QuantCache), "no int8 caches in the shared form"
+    assert plen.numel() == 1
+    scale = 1.0 / math.sqrt(D)
+    per_row = pos.numel() > 1
+    assert pos.numel() == (B if per_row else 1), "pos holds one position, or one per row"
+    if qkv.is_cuda and qkv.dtype == BF16 and pkc.dtype == BF16 and kc.dtype == BF16 and D == 64:
+        qkv = qkv.contiguous()
+        n_split = -(-Tp // SHARED_PROMPT_CHUNK) + -(-R // 256)
+        ws = torch.empty(B * H * n_split * (4 + D), device=qkv.device, dtype=F32)
+        out = torch.empty(B, 1, C, device=qkv.device, dtype=qkv.dtype)
+        _lib.call("nsa_decode_attn_shared_rows" if per_row else "nsa_decode_attn_shared", _lib.ptr(qkv),
+                  _lib.ptr(pkc), _lib.ptr(pvc), _lib.ptr(kc), _lib.ptr(vc), _lib.ptr(plen), _lib.ptr(pos),
+                  _lib.ptr(ws), _lib.ptr(out), B, H, Tp, R, scale, 1 if append else 0, _lib.stream())
+        return out
+    P = int(plen.item())
+    q, kn, vn = qkv.view(B, 3, H, D).unbind(1)                  # [B, H, D] each
+    y = torch.empty(B, H, D, dtype=F32, device=qkv.device)
+    for b, p in enumerate(pos.view(-1).expand(B).tolist()):
+        slot = p - P
+        if append and 0 <= slot < R:
+            kc[b, :, slot] = kn[b].to(kc.dtype)
+            vc[b, :, slot] = vn[b].to(vc.dtype)
+        n = min(max(slot + 1, 0), R) if slot < R else 0
+        k = torch.cat([pkc[0, :, :P].float(), kc[b, :, :n].float()], dim=1)       # [H, P + n, D]
+        v = torch.cat([pvc[0, :, :P].float(), vc[b, :, :n].float()], dim=1)
+        att = torch.softmax(torch.einsum("hd,hkd->hk", q[b].float(), k) * scale, dim=-1)
+        y[b] = torch.einsum("hk,hkd->hd", att, v)
+    return y.reshape(B, 1, C).to(qkv.dtype)
+
+
 class QuantWeight(NamedTuple):
     """An int8 weight-only form of a linear's weight [N, K]: ``q`` int8 [N, K] (contiguous,
     plain two's complement) and ``scale`` fp32 [N], one per output row; it stands for

@@ -49,6 +49,21 @@ the cache contents.  Unlike the int8-weight mode, prompt and steps therefore do 
 model: the prompt's own attention is unquantized, the usual practice for KV quantization.
 Any batch size, per_row or not, with or without ``quantize="int8"``; same launches, same
 captured graph (the ``_kv8`` forms of the append and attention kernels).
+``Decoder(..., shared_prompt=True, max_new=R)`` is for many samples of one prompt
+(``sample.py --sample_batch=N``, ``generate_batch([p] * N, ..., shared_prompt=True)``): the
+prompt runs through the model once, as one row (``prefill_shared``), into prompt caches
+[1, H, block_size, D] that the whole batch attends over, and every row caches only the
+tokens it generates, [B, H, R, D] (R = ``max_new`` or block_size), the token at absolute
+position p in slot p - ``plen``.  A step's attention (``ops.decode_attention_shared``) reads
+the prompt's K / V once per head for all rows, P + B n cache rows where the unshared form
+reads B (P + n); the prompt length lives on the device (``plen``), so one captured graph
+serves every prompt, and the rest of the step (embedding at the absolute position,
+linears, sampler, position advance, stop tokens) is the unshared one.  The prompt's ids and
+logits are kept, so a second round of samples of the same prompt does not encode it again
+(``prefills`` counts the real ones).  At least 2 rows, per_row or not, with or without
+``quantize="int8"``, not with ``kv_quantize``; on the GPU bf16 and head_dim 64 only.
+Prompts that share only a prefix (a system prompt followed by different questions) are not
+covered: that needs a prefill over prefix + suffix.
 The caches hold at most ``block_size`` positions; ``GPT.generate_cached`` falls
 back to the recompute loop when prompt + new tokens exceed that (nanoGPT crops the
 context there, which a cache cannot do without re-encoding).
@@ -63,16 +78,28 @@ from .. import ops
 
 class Decoder:
     def __init__(self, model, batch_size: int, max_len: int | None = None, use_graph: bool | None = None,
-                 per_row: bool = False, quantize: str | None = None, kv_quantize: str | None = None):
+                 per_row: bool = False, quantize: str | None = None, kv_quantize: str | None = None,
+                 shared_prompt: bool = False, max_new: int | None = None):
         if quantize not in (None, "int8"):
             raise ValueError(f"quantize must be None or 'int8', got {quantize!r}")
         if kv_quantize not in (None, "int8"):
             raise ValueError(f"kv_quantize must be None or 'int8', got {kv_quantize!r}")
+        if shared_prompt and kv_quantize:
+            raise ValueError("shared_prompt keeps bf16 caches: it cannot be combined with kv_quantize")
+        if shared_prompt and batch_size < 2:
+            raise ValueError(f"shared_prompt needs at least 2 rows to share a prompt, got batch size {batch_size}")
+        if max_new is not None and not shared_prompt:
+            raise ValueError("max_new sizes the row caches of a shared_prompt decoder")
         self.model = model
         self.per_row = per_row
         self.quantize = quantize
         self.kv_quantize = kv_quantize
+        self.shared = bool(shared_prompt)
         cfg = model.config
+        if shared_prompt and model.lm_head.weight.is_cuda and not self.graph_capable(model):
+            # the shared-prompt attention kernel is a head_dim-64 bf16 one; no silent torch step instead
+            raise ValueError("shared_prompt needs the fused decode kernels on the GPU: head_dim 64, "
+                             "bfloat16 compute and a vocabulary of at most 53248")
         if kv_quantize and model.lm_head.weight.is_cuda and not self.graph_capable(model):
             # the int8-cache kernels are the head_dim-64 bf16 ones; no silent torch step instead
             raise ValueError("kv_quantize='int8' needs the fused decode kernels on the GPU: head_dim 64, "
@@ -103,6 +130,19 @@ class Decoder:
         else:
             def cache():
                 return torch.zeros(shape, device=self.device, dtype=self.dtype)
+        if shared_prompt:
+            # one prompt cache for the batch and, per row, only the tokens it generates itself:
+            # the token at absolute position p >= plen lives in row-cache slot p - plen
+            self.R = int(max_new) if max_new else self.T
+            if not 1 <= self.R <= self.T:
+                raise ValueError(f"max_new must be in 1 .. {self.T}, got {max_new}")
+            pshape, shape = (1, self.H, self.T, self.D), (batch_size, self.H, self.R, self.D)
+            self.pkc = [torch.zeros(pshape, device=self.device, dtype=self.dtype) for _ in range(cfg.n_layer)]
+            self.pvc = [torch.zeros(pshape, device=self.device, dtype=self.dtype) for _ in range(cfg.n_layer)]
+            self.plen = torch.zeros(1, device=self.device, dtype=torch.int64)
+            self.prefills = 0            # prompts actually run through the model
+            self._prompt = None          # the cached prompt's token ids ...
+            self._prompt_logits = None   # ... and its last position's logits [1, V]
         self.kc = [cache() for _ in range(cfg.n_layer)]
         self.vc = [cache() for _ in range(cfg.n_layer)]
         # position of the token being fed: one for the whole batch, or (per_row) one per sequence
@@ -199,7 +239,10 @@ class Decoder:
         self.sgraphs = {}
 
     # ------------------------------------------------------------------ layers
-    def _prefill_layers(self, x):
+    def _prefill_layers(self, x, kc=None, vc=None):
+        """The prompt x through every block; its K / V rows go to the caches ``kc`` / ``vc``
+        (default: the decoder's own; ``prefill_shared`` passes the prompt caches)."""
+        kc, vc = kc or self.kc, vc or self.vc
         tr = self.model.transformer
         blocks = tr.h
         ln = blocks[0].ln_1
@@ -208,7 +251,7 @@ class Decoder:
             nxt = blocks[i + 1].ln_1 if i + 1 < len(blocks) else tr.ln_f
             attn, mlp = block.attn, block.mlp
             qkv = ops.linear(h, attn.c_attn.weight, attn.c_attn.bias)
-            ops.kv_append(qkv, self.kc[i], self.vc[i], None, 0)
+            ops.kv_append(qkv, kc[i], vc[i], None, 0)
             y = ops.attention(qkv, attn.n_head, 0.0, False)
             y = ops.linear(y, attn.c_proj.weight, attn.c_proj.bias)
             x, h2 = ops.add_layer_norm(x, y, block.ln_2.weight, block.ln_2.bias)
@@ -239,7 +282,12 @@ class Decoder:
             else:
                 x, qkv = ops.decode_linear_ln(x, branch, ln1.weight, ln1.bias, W(attn.c_attn.weight), attn.c_attn.bias,
                                               out_dtype=ln1.out_dtype)
-            y = ops.decode_attention(qkv, self.kc[i], self.vc[i], self.pos, attn.n_head, append=True, combine=False)
+            if self.shared:
+                y = ops.decode_attention_shared(qkv, self.pkc[i], self.pvc[i], self.kc[i], self.vc[i], self.plen,
+                                                self.pos, attn.n_head, append=True)
+            else:
+                y = ops.decode_attention(qkv, self.kc[i], self.vc[i], self.pos, attn.n_head, append=True,
+                                         combine=False)
             y = ops.decode_linear(y, W(attn.c_proj.weight), attn.c_proj.bias)
             x, u = ops.decode_linear_ln(x, y, ln2.weight, ln2.bias, W(mlp.c_fc.weight), mlp.c_fc.bias, gelu=True,
                                         out_dtype=ln2.out_dtype)
@@ -263,6 +311,7 @@ class Decoder:
         feeds that position before any step reads them.  Returns the logits of position
         ``lengths[b] - 1`` of each row and sets ``pos`` to ``lengths``."""
         B, T0 = idx.shape
+        assert not self.shared, "a shared_prompt decoder encodes its one prompt with prefill_shared"
         assert B == self.B and 1 <= T0 <= self.T
         tr = self.model.transformer
         if lengths is not None:
@@ -279,6 +328,34 @@ class Decoder:
         self.pos.copy_(lengths)
         last = h[torch.arange(B, device=self.device), lengths - 1].unsqueeze(1)  # [B, 1, C]
         return ops.lm_head_logits(last, self.model.lm_head.weight)[:, 0]
+
+    @torch.no_grad()
+    def prefill_shared(self, idx: torch.Tensor) -> torch.Tensor:
+        """Encode the one prompt ([T0] or [1, T0]) every row continues (shared_prompt decoders):
+        it runs through the model as a single row, its K / V rows go to the prompt caches,
+        ``plen`` becomes T0, every row's position T0 and ``done`` is cleared.  Returns the last
+        position's logits as [B, V] (fp32; one row expanded: every row draws from the same
+        distribution, each with its own uniform).
+
+        The prompt's ids and those logits are kept: a later call with the same ids only puts the
+        positions and flags back (``prefills`` counts the calls that ran the model), so rounds
+        of samples of one prompt encode it once per decoder."""
+        assert self.shared, "prefill_shared needs Decoder(..., shared_prompt=True)"
+        idx = idx.reshape(1, -1).to(self.device)
+        T0 = idx.shape[1]
+        assert 1 <= T0 <= self.T
+        if self._prompt is None or self._prompt.shape != idx.shape or not torch.equal(self._prompt, idx):
+            tr = self.model.transformer
+            x = ops.embedding(idx, tr.wte.weight, tr.wpe.weight, 0.0, False, dtype=self.rdtype, cdtype=self.dtype)
+            h = self._prefill_layers(x, self.pkc, self.pvc)
+            self._prompt_logits = ops.lm_head_logits(h[:, [-1], :], self.model.lm_head.weight)[:, 0].float()
+            self._prompt = idx.clone()
+            self.prefills += 1
+        self.plen.fill_(T0)
+        self.pos.fill_(T0)
+        if self.per_row:
+            self.done.zero_()
+        return self._prompt_logits.expand(self.B, -1)
 
     def _step_impl(self):
         return self._decode_layers()[:, 0]  # also advances pos
@@ -420,8 +497,13 @@ def generate_cached(model, idx: torch.Tensor, max_new_tokens: int, temperature: 
                     top_k: int | None = None, use_graph: bool | None = None,
                     decoder: "Decoder | None" = None, top_p: float | None = None,
                     min_p: float | None = None, quantize: str | None = None,
-                    kv_quantize: str | None = None) -> torch.Tensor:
+                    kv_quantize: str | None = None, shared_prompt: bool = False) -> torch.Tensor:
     """``model.generate`` with KV caches: same sampling, one token's forward per new token.
+
+    ``shared_prompt=True``: the rows of ``idx`` are one prompt (unequal rows raise ValueError)
+    whose K / V are cached once for the batch (``Decoder(..., shared_prompt=True)``); a single
+    row goes the ordinary way.  No recompute fallback: prompt + new tokens past block_size
+    raise ValueError, and so does ``kv_quantize``.
 
     ``quantize="int8"``: decode with int8 weights (``Decoder(..., quantize="int8")``); the
     recompute fallback cannot, so a prompt + new tokens past block_size raises ValueError.
@@ -439,6 +521,15 @@ def generate_cached(model, idx: torch.Tensor, max_new_tokens: int, temperature: 
         raise ValueError(f"quantize must be None or 'int8', got {quantize!r}")
     if kv_quantize not in (None, "int8"):
         raise ValueError(f"kv_quantize must be None or 'int8', got {kv_quantize!r}")
+    if shared_prompt:
+        if kv_quantize:
+            raise ValueError("shared_prompt keeps bf16 caches: it cannot be combined with kv_quantize")
+        if not bool((idx == idx[:1]).all()):
+            raise ValueError("shared_prompt needs every row of idx to be the same prompt")
+        if B > 1:
+            new = _generate_shared(model, idx[0], B, max_new_tokens, temperature, top_k, None, use_graph, decoder,
+                                   top_p, min_p, quantize, per_row=False)
+            return torch.cat([idx, new], dim=1)
     if T0 + max_new_tokens - 1 > model.config.block_size:
         if quantize:
             raise ValueError("quantize needs the KV-cache path: prompt + new tokens exceed block_size, and the "
@@ -449,7 +540,7 @@ def generate_cached(model, idx: torch.Tensor, max_new_tokens: int, temperature: 
         # the caches hold block_size positions; nanoGPT crops the context beyond that
         return model.generate(idx, max_new_tokens, temperature=temperature, top_k=top_k, top_p=top_p, min_p=min_p)
     own = (decoder is None or decoder.B != B or decoder.quantize != quantize
-           or decoder.kv_quantize != kv_quantize)
+           or decoder.kv_quantize != kv_quantize or decoder.shared)
     dec = (Decoder(model, B, max_len=model.config.block_size, use_graph=use_graph, quantize=quantize,
                    kv_quantize=kv_quantize) if own else decoder)
     try:
@@ -470,12 +561,37 @@ def _cut_at_stop(new: torch.Tensor, stop_token: int | None) -> torch.Tensor:
     return new[:int(hit[0]) + 1] if hit.numel() else new
 
 
+def _generate_shared(model, prompt, B, max_new_tokens, temperature, top_k, stop_token, use_graph, decoder, top_p,
+                     min_p, quantize, per_row) -> torch.Tensor:
+    """B continuations of the one 1-D ``prompt`` on a shared_prompt decoder -> the new tokens
+    [B, max_new_tokens] (whatever a row holds after its stop token is for the caller to cut).
+    ``decoder`` is reused if it is a shared one of this B, per_row and quantize whose row
+    caches hold max_new_tokens slots; the prompt it has cached is not encoded again.
+    (Prompts that share only a prefix would need a prefill over prefix + suffix: not done.)"""
+    T0 = prompt.numel()
+    if T0 + max_new_tokens > model.config.block_size:
+        raise ValueError(f"shared_prompt needs the KV-cache path: prompt ({T0}) + new tokens ({max_new_tokens}) "
+                         f"exceed block_size {model.config.block_size}, and the recompute loop has nothing to share")
+    own = (decoder is None or not decoder.shared or decoder.B != B or decoder.per_row != per_row
+           or decoder.quantize != quantize or decoder.R < max_new_tokens)
+    dec = (Decoder(model, B, max_len=model.config.block_size, use_graph=use_graph, per_row=per_row,
+                   quantize=quantize, shared_prompt=True, max_new=max_new_tokens) if own else decoder)
+    try:
+        dec.reseed()
+        dec.sample_into(dec.prefill_shared(prompt), temperature, top_k, stop_token, top_p, min_p)  # gen[:, T0]
+        dec.run(max_new_tokens - 1, temperature, top_k, stop_token, top_p, min_p)
+        return dec.gen[:, T0:T0 + max_new_tokens].clone()
+    finally:
+        if own:
+            dec.release()
+
+
 @torch.no_grad()
 def generate_batch(model, prompts, max_new_tokens: int, temperature: float = 1.0, top_k: int | None = None,
                    stop_token: int | None = None, use_graph: bool | None = None,
                    decoder: "Decoder | None" = None, top_p: float | None = None,
                    min_p: float | None = None, quantize: str | None = None,
-                   kv_quantize: str | None = None) -> list[torch.Tensor]:
+                   kv_quantize: str | None = None, shared_prompt: bool = False) -> list[torch.Tensor]:
     """Generate for a list of prompts of unequal lengths as one batch.
 
     ``prompts``: 1-D token tensors, each of length >= 1.  Every result is its prompt followed
@@ -489,7 +605,15 @@ def generate_batch(model, prompts, max_new_tokens: int, temperature: float = 1.0
     ``decoder``: a per_row Decoder of the right batch size to reuse across calls (weight
     shadows and captured graphs survive); the caller releases it.  ``quantize="int8"``:
     int8 weights; a row that needs the recompute loop then raises ValueError.
-    ``kv_quantize="int8"``: int8 KV caches, with the same refusal."""
+    ``kv_quantize="int8"``: int8 KV caches, with the same refusal.
+
+    ``shared_prompt=True``: every prompt must be the same one (ValueError otherwise); it is
+    encoded once, as a single row, into a prompt cache the whole batch attends over, and each
+    row caches only its own new tokens (``Decoder(..., shared_prompt=True, max_new=
+    max_new_tokens)``; ``decoder`` is reused only if it is such a one, and then keeps the
+    prompt between calls).  A single prompt goes the ordinary way.  Prompt + new tokens past
+    block_size and ``kv_quantize`` raise ValueError.  Prompts that share only a prefix are not
+    covered: that needs a prefill over prefix + suffix."""
     if quantize not in (None, "int8"):
         raise ValueError(f"quantize must be None or 'int8', got {quantize!r}")
     if kv_quantize not in (None, "int8"):
@@ -499,10 +623,20 @@ def generate_batch(model, prompts, max_new_tokens: int, temperature: float = 1.0
     top_p, min_p = sampling_filters(top_p, min_p)
     prompts = [p.view(-1) for p in prompts]
     assert all(p.numel() >= 1 for p in prompts), "every prompt needs at least one token"
+    if shared_prompt:
+        if kv_quantize:
+            raise ValueError("shared_prompt keeps bf16 caches: it cannot be combined with kv_quantize")
+        if any(p.shape != prompts[0].shape or not torch.equal(p, prompts[0]) for p in prompts[1:]):
+            raise ValueError("shared_prompt needs every prompt to be the same")
     if max_new_tokens <= 0:
         return list(prompts)
     T = model.config.block_size
     device = model.lm_head.weight.device
+    if shared_prompt and len(prompts) > 1:
+        p = prompts[0].to(device)
+        new = _generate_shared(model, p, len(prompts), max_new_tokens, temperature, top_k, stop_token, use_graph,
+                               decoder, top_p, min_p, quantize, per_row=True)
+        return [torch.cat([p, _cut_at_stop(row, stop_token)]) for row in new]
     outs: list = [None] * len(prompts)
     rows = [i for i, p in enumerate(prompts) if p.numel() + max_new_tokens - 1 <= T]
     for i, p in enumerate(prompts):
@@ -519,7 +653,7 @@ def generate_batch(model, prompts, max_new_tokens: int, temperature: float = 1.0
     for b, i in enumerate(rows):
         idx[b, :lens[b]] = prompts[i]
     own = (decoder is None or decoder.B != B or not decoder.per_row or decoder.quantize != quantize
-           or decoder.kv_quantize != kv_quantize)
+           or decoder.kv_quantize != kv_quantize or decoder.shared)
     dec = (Decoder(model, B, max_len=T, use_graph=use_graph, per_row=True, quantize=quantize,
                    kv_quantize=kv_quantize) if own else decoder)
     try:

@@ -16,7 +16,10 @@ batch of unequal lengths, ``--stop_token=ID`` ends a sample at that token
 (``--top_k=0``: no top-k); on the GPU the selection runs inside the sampling kernel.
 ``--quantize=int8`` decodes with int8 weight-only linears (per-row scales; the KV-cache
 path only, so it refuses ``--kv_cache=False``).  ``--kv_quantize=int8`` keeps the KV caches
-as int8 rows with one scale each (the same refusal).
+as int8 rows with one scale each (the same refusal).  ``--shared_prompt=True`` with
+``--sample_batch=N`` encodes and caches the prompt once for the N rows of a batch and once
+for all rounds (``Decoder(shared_prompt=True)``); it refuses ``--prompts_file``,
+``--kv_cache=False`` and ``--kv_quantize``.
 """
 
 from __future__ import annotations
@@ -53,6 +56,7 @@ SAMPLE_DEFAULTS = dict(
     stop_token=-1,  # token id that ends a sample (printed text ends before it); -1: none
     quantize="",  # "int8": int8 weight-only decoding on the KV-cache path (Decoder(quantize="int8")); "": off
     kv_quantize="",  # "int8": int8 KV caches, one scale per cache row (Decoder(kv_quantize="int8")); "": off
+    shared_prompt=False,  # sample_batch > 1: encode and cache the prompt once for the batch (Decoder(shared_prompt=True))
 )
 
 
@@ -62,6 +66,7 @@ def _generate_batches(model, c, encode, decode, start, device):
     stop = c["stop_token"] if c["stop_token"] >= 0 else None
     quantize = c["quantize"] or None
     kv_quantize = c["kv_quantize"] or None
+    shared = bool(c["shared_prompt"])  # main() has refused prompts_file, kv_cache=False and kv_quantize with it
     if c["prompts_file"]:
         with open(c["prompts_file"], "r", encoding="utf-8") as f:
             texts = [ln.rstrip("\n") for ln in f if ln.strip()]
@@ -76,12 +81,17 @@ def _generate_batches(model, c, encode, decode, start, device):
             if c["kv_cache"]:
                 from .runtime.decode import Decoder
                 B = len(prompts)
+                sh = shared and B > 1  # a last round of one sample goes the ordinary way
                 if B not in decs:
-                    decs[B] = Decoder(model, B, max_len=model.config.block_size, per_row=True, quantize=quantize,
-                                      kv_quantize=kv_quantize)
+                    if sh:  # the prompt stays cached in the decoder: later rounds do not encode it again
+                        decs[B] = Decoder(model, B, max_len=model.config.block_size, per_row=True, quantize=quantize,
+                                          shared_prompt=True, max_new=max(1, c["max_new_tokens"]))
+                    else:
+                        decs[B] = Decoder(model, B, max_len=model.config.block_size, per_row=True, quantize=quantize,
+                                          kv_quantize=kv_quantize)
                 ys = model.generate_batch(prompts, c["max_new_tokens"], temperature=c["temperature"], top_k=c["top_k"],
                                           stop_token=stop, decoder=decs[B], top_p=c["top_p"], min_p=c["min_p"],
-                                          quantize=quantize, kv_quantize=kv_quantize)
+                                          quantize=quantize, kv_quantize=kv_quantize, shared_prompt=sh)
             else:
                 ys = [model.generate(p[None], c["max_new_tokens"], temperature=c["temperature"], top_k=c["top_k"],
                                      top_p=c["top_p"], min_p=c["min_p"])[0] for p in prompts]
@@ -136,6 +146,15 @@ def main(argv=None):
     if c["kv_quantize"] and not c["kv_cache"]:
         raise ValueError("--kv_quantize needs the KV-cache path: the recompute loop (--kv_cache=False) has no "
                          "cache to quantize")
+    if c["shared_prompt"]:
+        if c["prompts_file"]:
+            raise ValueError("--shared_prompt shares one prompt among the rows of a batch: it cannot be combined "
+                             "with --prompts_file (different prompts)")
+        if not c["kv_cache"]:
+            raise ValueError("--shared_prompt needs the KV-cache path: the recompute loop (--kv_cache=False) has no "
+                             "cache to share")
+        if c["kv_quantize"]:
+            raise ValueError("--shared_prompt keeps bf16 caches: it cannot be combined with --kv_quantize")
     quantize = c["quantize"] or None
     kv_quantize = c["kv_quantize"] or None
     torch.manual_seed(c["seed"])

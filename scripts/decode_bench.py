@@ -24,6 +24,11 @@ from; a cached run feeds positions prompt .. prompt + new, which must stay below
 (``--prompt 896 --new 127`` ends at position 1023).  ``--memory`` adds the decoder's peak
 allocated bytes (``torch.cuda.max_memory_allocated`` over construction, prefill and the timed
 steps, minus what was allocated before) to each line.
+``--shared_prompt`` adds ``rows_shared`` (and ``rows_int8_shared``) after ``rows``: the same
+settings on a ``Decoder(shared_prompt=True, max_new=--new + 1)``, every row continuing row 0's
+prompt; with it the ``rows`` lines and their shared twins also carry ``ttft_ms``, the time from
+the start of the prefill to the first drawn token, and ``--samples`` adds
+``sample_batch_shared``.
 """
 
 import argparse
@@ -67,12 +72,21 @@ def ragged_lengths(B, prompt):
     return [prompt if B == 1 else lo + (prompt - lo) * b // (B - 1) for b in range(B)]
 
 
-def run_rows(model, idx, new, lengths=None, quantize=None, kv_quantize=None):
-    """The graph mode on a per_row decoder: equal lengths, or (lengths) a ragged batch."""
+def run_rows(model, idx, new, lengths=None, quantize=None, kv_quantize=None, shared=False):
+    """The graph mode on a per_row decoder: equal lengths, or (lengths) a ragged batch; shared:
+    a shared_prompt decoder, every row continuing idx[0].  Returns (seconds of the timed steps,
+    seconds from the start of the prefill to the first drawn token)."""
     B = idx.shape[0]
-    dec = Decoder(model, B, use_graph=True, per_row=True, quantize=quantize, kv_quantize=kv_quantize)
+    if shared:  # slots for the capture step and the timed ones
+        dec = Decoder(model, B, use_graph=True, per_row=True, quantize=quantize, shared_prompt=True, max_new=new + 1)
+    else:
+        dec = Decoder(model, B, use_graph=True, per_row=True, quantize=quantize, kv_quantize=kv_quantize)
     lens = None if lengths is None else torch.tensor(lengths, device=idx.device)
-    dec.sample_into(dec.prefill(idx, lens), 0.8, **SMP)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    dec.sample_into(dec.prefill_shared(idx[0]) if shared else dec.prefill(idx, lens), 0.8, **SMP)
+    torch.cuda.synchronize()
+    ttft = time.perf_counter() - t0
     dec.run(1, 0.8, **SMP)  # capture outside the timed loop
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -80,17 +94,19 @@ def run_rows(model, idx, new, lengths=None, quantize=None, kv_quantize=None):
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     dec.release()
-    return dt
+    return dt, ttft
 
 
-def run_samples(model, prompt, n, new, batched):
+def run_samples(model, prompt, n, new, batched, shared=False):
     """sample.py's flow for n samples of one prompt, decoder construction and capture
-    included: one batch-1 decoder reused n times, or one generate_batch of n rows."""
+    included: one batch-1 decoder reused n times, or one generate_batch of n rows (shared: on
+    a shared_prompt decoder)."""
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     if batched:
-        dec = Decoder(model, n, max_len=model.config.block_size, per_row=True)
-        model.generate_batch([prompt] * n, new, temperature=0.8, **SMP, decoder=dec)
+        dec = (Decoder(model, n, max_len=model.config.block_size, per_row=True, shared_prompt=True, max_new=new)
+               if shared else Decoder(model, n, max_len=model.config.block_size, per_row=True))
+        model.generate_batch([prompt] * n, new, temperature=0.8, **SMP, decoder=dec, shared_prompt=shared)
     else:
         dec = Decoder(model, 1, max_len=model.config.block_size)
         for _ in range(n):
@@ -126,6 +142,9 @@ def main():
     ap.add_argument("--kv_quantize", default="", choices=["", "int8"],
                     help="int8: add int8-KV-cache twins of the graph and rows modes (graph_kv8, rows_kv8; with "
                          "--quantize int8 also graph_int8_kv8, rows_int8_kv8)")
+    ap.add_argument("--shared_prompt", action="store_true",
+                    help="add shared-prompt twins of the rows modes (rows_shared, rows_int8_shared), ttft_ms on both, "
+                         "and sample_batch_shared with --samples")
     ap.add_argument("--memory", action="store_true", help="add each run's peak allocated bytes (decoder_peak_mb)")
     ap.add_argument("--top_k", type=int, default=200, help="0: no top-k")
     ap.add_argument("--top_p", type=float, default=1.0, help="nucleus mass; 1.0: off")
@@ -143,6 +162,8 @@ def main():
         modes = [t for m in modes for t in ([m, f"{m}_{a.quantize}"] if m in ("graph", "rows") else [m])]
     if a.kv_quantize:  # each int8-cache twin right after its mode (the int8-weight twins included)
         modes = [t for m in modes for t in ([m, f"{m}_kv8"] if m.partition("_")[0] in ("graph", "rows") else [m])]
+    if a.shared_prompt:  # each shared twin right after its rows mode (bf16 caches only)
+        modes = [t for m in modes for t in ([m, f"{m}_shared"] if m in ("rows", "rows_int8") else [m])]
     block_size = GPTConfig().block_size
     if any(m != "recompute" for m in modes) and a.prompt + a.new >= block_size:
         # a cached run feeds positions prompt .. prompt + new (one capture step, then --new timed
@@ -161,6 +182,7 @@ def main():
                     base, *sfx = mode.split("_")  # graph_int8_kv8 -> graph, int8 weights, int8 caches
                     qz = "int8" if "int8" in sfx else None
                     kvq = "int8" if "kv8" in sfx else None
+                    ttft = {}
                     if a.memory:
                         torch.cuda.synchronize()
                         torch.cuda.reset_peak_memory_stats()
@@ -168,8 +190,10 @@ def main():
                     if base in ("rows", "ragged"):
                         n = a.new
                         lens = ragged_lengths(B, a.prompt) if base == "ragged" else None
-                        run_rows(model, idx, 4, lens, qz, kvq)
-                        dt = run_rows(model, idx, n, lens, qz, kvq)
+                        run_rows(model, idx, 4, lens, qz, kvq, "shared" in sfx)
+                        dt, t1 = run_rows(model, idx, n, lens, qz, kvq, "shared" in sfx)
+                        if a.shared_prompt:
+                            ttft = {"ttft_ms": round(t1 * 1e3, 3)}
                     elif mode == "recompute":
                         run_recompute(model, idx, 2)  # warm-up (tuner, allocator)
                         n = a.recompute_new
@@ -182,16 +206,18 @@ def main():
                            if a.memory else {})
                     print(json.dumps({"model": name, "batch": B, "mode": mode, "prompt": a.prompt, "new_tokens": n,
                                       "tokens_per_s": round(B * n / dt, 1), "ms_per_token": round(dt / n * 1e3, 3),
-                                      **mem, **extra}),
+                                      **ttft, **mem, **extra}),
                           flush=True)
         if a.samples:
             prompt = torch.randint(0, 50257, (a.prompt,), device="cuda")
             with torch.no_grad():
-                for batched in [False, True] * a.repeat:
-                    run_samples(model, prompt, a.samples, 4, batched)  # warm-up (tuner, allocator)
-                    dt = run_samples(model, prompt, a.samples, a.new, batched)
+                flows = [(False, False), (True, False)] + ([(True, True)] if a.shared_prompt else [])
+                for batched, shared in flows * a.repeat:
+                    run_samples(model, prompt, a.samples, 4, batched, shared)  # warm-up (tuner, allocator)
+                    dt = run_samples(model, prompt, a.samples, a.new, batched, shared)
                     print(json.dumps({"model": name, "samples": a.samples, "new_tokens": a.new, "prompt": a.prompt,
-                                      "mode": "sample_batch" if batched else "sample_loop",
+                                      "mode": ("sample_batch_shared" if shared else "sample_batch") if batched
+                                      else "sample_loop",
                                       "tokens_per_s": round(a.samples * a.new / dt, 1), "seconds": round(dt, 3),
                                       **extra}),
                           flush=True)
