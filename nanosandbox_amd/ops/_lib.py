@@ -117,6 +117,9 @@ _SIGNATURES = {
                                c_void_p, c_int, c_int, c_int, c_int, c_float, c_int, c_void_p],
     "nsa_decode_attn_shared_rows": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                     c_void_p, c_int, c_int, c_int, c_int, c_float, c_int, c_void_p],
+    # suffix queries over a shared prefix cache + the row's own keys (csrc/kernels/prefix_attn.hip): qkv, pk, pv,
+    # out, B, S, H, Tp, P, scale
+    "nsa_prefix_attn": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p],
     "nsa_flash_bwd2": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                        c_int, c_int, c_int, c_int, c_float, c_float, c_uint64, c_void_p],
     "nsa_rng_advance": [c_void_p],

@@ -1109,6 +1109,42 @@ def decode_attention_shared(qkv, pkc, pvc, kc, vc, plen, pos, n_head: int, appen
     return y.reshape(B, 1, C).to(qkv.dtype)
 
 
+def prefix_attention(qkv, pkc, pvc, P: int, n_head: int):
+    """Prefill attention of suffixes that follow one shared prefix: qkv [B, S, 3C] -> [B, S, C].
+
+    ``pkc`` / ``pvc`` [1, H, Tp, D] hold the prefix's K / V once, rows 0 .. P - 1 live (``P``: a
+    host int, 1 <= P <= Tp; the prefill is not captured).  ``qkv`` holds the packed projections
+    of every row's S suffix tokens (absolute positions P .. P + S - 1), right-padded.  Query i
+    of row b attends over prefix keys 0 .. P - 1 followed by its own row's keys 0 .. i.  Every
+    output row is written, padding queries included; cache rows at or past P are never used
+    and nothing is written but the result.
+
+    GPU, bf16, D = 64: one launch of ``nsa_prefix_attn`` (csrc/kernels/prefix_attn.hip).
+    Anything else: fp32 torch over the concatenated keys (the reference; bf16 caches only)."""
+    B, S, C3 = qkv.shape
+    C = C3 // 3
+    _, H, Tp, D = pkc.shape
+    assert H == n_head and C == H * D and pkc.shape[0] == 1 and pvc.shape == pkc.shape
+    assert not isinstance(pkc, QuantCache), "no int8 caches in the shared form"
+    P = int(P)
+    assert 1 <= P <= Tp, f"prefix length {P} outside 1 .. {Tp}"
+    scale = 1.0 / math.sqrt(D)
+    if qkv.is_cuda and qkv.dtype == BF16 and pkc.dtype == BF16 and pvc.dtype == BF16 and D == 64:
+        qkv = qkv.contiguous()
+        assert pkc.is_contiguous() and pvc.is_contiguous()
+        out = torch.empty(B, S, C, device=qkv.device, dtype=qkv.dtype)
+        _lib.call("nsa_prefix_attn", _lib.ptr(qkv), _lib.ptr(pkc), _lib.ptr(pvc), _lib.ptr(out), B, S, H, Tp, P,
+                  scale, _lib.stream())
+        return out
+    q, k, v = qkv.float().view(B, S, 3, H, D).permute(2, 0, 3, 1, 4)           # [B, H, S, D] each
+    k = torch.cat([pkc[:, :, :P].float().expand(B, -1, -1, -1), k], dim=2)      # [B, H, P + S, D]
+    v = torch.cat([pvc[:, :, :P].float().expand(B, -1, -1, -1), v], dim=2)
+    att = (q @ k.transpose(-2, -1)) * scale                                     # [B, H, S, P + S]
+    mask = torch.ones(S, P + S, dtype=torch.bool, device=qkv.device).tril(diagonal=P)
+    att = torch.softmax(att.masked_fill(~mask, float("-inf")), dim=-1)
+    return (att @ v).transpose(1, 2).reshape(B, S, C).to(qkv.dtype)
+
+
 class QuantWeight(NamedTuple):
     """An int8 weight-only form of a linear's weight [N, K]: ``q`` int8 [N, K] (contiguous,
     plain two's complement) and ``scale`` fp32 [N], one per output row; it stands for

@@ -62,8 +62,15 @@ linears, sampler, position advance, stop tokens) is the unshared one.  The promp
 logits are kept, so a second round of samples of the same prompt does not encode it again
 (``prefills`` counts the real ones).  At least 2 rows, per_row or not, with or without
 ``quantize="int8"``, not with ``kv_quantize``; on the GPU bf16 and head_dim 64 only.
-Prompts that share only a prefix (a system prompt followed by different questions) are not
-covered: that needs a prefill over prefix + suffix.
+Prompts that share only a prefix (a system prompt followed by different questions;
+``generate_batch(..., shared_prefix=True)``, ``sample.py --shared_prefix=True``) use the same
+decoder, per_row: ``prefill_shared(prefix)`` caches the prefix once, and
+``prefill_suffixes(idx, lengths)`` runs every row's right-padded suffix through the model at
+positions P .., its K / V rows into row-cache slots 0 .. S - 1 and its queries over the prompt
+cache plus the row's own earlier suffix keys (``ops.prefix_attention``: one attention kernel
+that reads the prefix cache where it lies, so nothing is materialised per row and no prefix
+query is computed again).  ``pos`` becomes P + lengths and the steps are the shared-prompt
+ones, unchanged: a row's slots hold suffix and generated tokens alike (slot = position - P).
 The caches hold at most ``block_size`` positions; ``GPT.generate_cached`` falls
 back to the recompute loop when prompt + new tokens exceed that (nanoGPT crops the
 context there, which a cache cannot do without re-encoding).
@@ -239,9 +246,11 @@ class Decoder:
         self.sgraphs = {}
 
     # ------------------------------------------------------------------ layers
-    def _prefill_layers(self, x, kc=None, vc=None):
+    def _prefill_layers(self, x, kc=None, vc=None, prefix=None):
         """The prompt x through every block; its K / V rows go to the caches ``kc`` / ``vc``
-        (default: the decoder's own; ``prefill_shared`` passes the prompt caches)."""
+        (default: the decoder's own; ``prefill_shared`` passes the prompt caches).  ``prefix``
+        (``prefill_suffixes``: the prefix length P): x holds the suffixes that follow the cached
+        prefix, and every query also attends over prompt-cache rows 0 .. P - 1."""
         kc, vc = kc or self.kc, vc or self.vc
         tr = self.model.transformer
         blocks = tr.h
@@ -252,7 +261,10 @@ class Decoder:
             attn, mlp = block.attn, block.mlp
             qkv = ops.linear(h, attn.c_attn.weight, attn.c_attn.bias)
             ops.kv_append(qkv, kc[i], vc[i], None, 0)
-            y = ops.attention(qkv, attn.n_head, 0.0, False)
+            if prefix is None:
+                y = ops.attention(qkv, attn.n_head, 0.0, False)
+            else:
+                y = ops.prefix_attention(qkv, self.pkc[i], self.pvc[i], prefix, attn.n_head)
             y = ops.linear(y, attn.c_proj.weight, attn.c_proj.bias)
             x, h2 = ops.add_layer_norm(x, y, block.ln_2.weight, block.ln_2.bias)
             y = mlp(h2)
@@ -356,6 +368,42 @@ class Decoder:
         if self.per_row:
             self.done.zero_()
         return self._prompt_logits.expand(self.B, -1)
+
+    @torch.no_grad()
+    def prefill_suffixes(self, idx: torch.Tensor, lengths: torch.Tensor | None = None) -> torch.Tensor:
+        """Encode what every row adds to the shared prefix (after ``prefill_shared(prefix)``, P
+        tokens): ``idx`` [B, S] holds row b's tokens at absolute positions P .. P + S - 1,
+        right-padded with any valid id when ``lengths`` (per_row decoders; int64 [B], 1 <=
+        lengths[b] <= S) says that row b's suffix is its first ``lengths[b]`` tokens.  The
+        suffixes' K / V rows go to row-cache slots 0 .. S - 1 and their queries attend over the
+        prompt cache plus the row's own earlier suffix keys (``ops.prefix_attention``); the
+        prefix is not run again.  Padding is invisible to a row's own positions, and the rows
+        it leaves in the caches are overwritten by the step that feeds that position before any
+        step reads them, as after ``prefill(idx, lengths)``.  Sets ``pos`` to P + lengths (or
+        P + S), clears ``done`` and returns the logits of each row's last suffix token [B, V]."""
+        assert self.shared, "prefill_suffixes needs Decoder(..., shared_prompt=True)"
+        assert self._prompt is not None, "prefill_suffixes follows prefill_shared(prefix)"
+        B, S = idx.shape
+        P = self._prompt.shape[1]
+        assert B == self.B and 1 <= S <= self.R and P + S <= self.T
+        idx = idx.to(self.device)
+        if lengths is not None:
+            assert self.per_row, "unequal suffix lengths need Decoder(..., per_row=True)"
+            lengths = torch.as_tensor(lengths, dtype=torch.int64).to(self.device).view(B)
+            assert int(lengths.min()) >= 1 and int(lengths.max()) <= S
+        tr = self.model.transformer
+        wpe = ops.compute_weight(tr.wpe.weight, self.dtype)[P:P + S]  # positions P .. P + S - 1
+        x = ops.embedding(idx, tr.wte.weight, wpe, 0.0, False, dtype=self.rdtype, cdtype=self.dtype)
+        h = self._prefill_layers(x, prefix=P)
+        self.plen.fill_(P)
+        if self.per_row:
+            self.done.zero_()
+        if lengths is None:
+            self.pos.fill_(P + S)
+            return ops.lm_head_logits(h[:, [-1], :], self.model.lm_head.weight)[:, 0]
+        self.pos.copy_(lengths + P)
+        last = h[torch.arange(B, device=self.device), lengths - 1].unsqueeze(1)  # [B, 1, C]
+        return ops.lm_head_logits(last, self.model.lm_head.weight)[:, 0]
 
     def _step_impl(self):
         return self._decode_layers()[:, 0]  # also advances pos
@@ -567,7 +615,7 @@ def _generate_shared(model, prompt, B, max_new_tokens, temperature, top_k, stop_
     [B, max_new_tokens] (whatever a row holds after its stop token is for the caller to cut).
     ``decoder`` is reused if it is a shared one of this B, per_row and quantize whose row
     caches hold max_new_tokens slots; the prompt it has cached is not encoded again.
-    (Prompts that share only a prefix would need a prefill over prefix + suffix: not done.)"""
+    (Prompts that share only a prefix: ``_generate_prefix``.)"""
     T0 = prompt.numel()
     if T0 + max_new_tokens > model.config.block_size:
         raise ValueError(f"shared_prompt needs the KV-cache path: prompt ({T0}) + new tokens ({max_new_tokens}) "
@@ -586,12 +634,65 @@ def _generate_shared(model, prompt, B, max_new_tokens, temperature, top_k, stop_
             dec.release()
 
 
+def common_prefix_len(prompts) -> int:
+    """The prefix length P a shared_prefix batch caches once: the longest common token prefix of
+    the 1-D ``prompts``, but at most the shortest prompt - 1, so every row keeps a suffix token."""
+    n = min(p.numel() for p in prompts) - 1
+    if n <= 0 or len(prompts) < 2:
+        return max(n, 0)
+    first = prompts[0][:n]
+    same = torch.stack([p[:n].to(first.device) == first for p in prompts[1:]]).all(dim=0)
+    return int(same.long().cumprod(0).sum())
+
+
+def _generate_prefix(model, prompts, P, max_new_tokens, temperature, top_k, stop_token, use_graph, decoder, top_p,
+                     min_p, quantize) -> list[torch.Tensor]:
+    """``generate_batch`` for prompts whose first ``P`` tokens are one prefix, on a shared per-row
+    decoder: the prefix goes through the model once into the prompt caches (``prefill_shared``; not
+    at all if the decoder holds it already), the right-padded suffixes through ``prefill_suffixes``
+    into the row caches, and the steps are the shared-prompt ones.  ``decoder`` is reused if it
+    is a shared per_row one of this B and quantize whose row caches hold the longest suffix +
+    max_new_tokens slots."""
+    T = model.config.block_size
+    device = model.lm_head.weight.device
+    B = len(prompts)
+    lens = [p.numel() - P for p in prompts]
+    S = max(lens)
+    for p in prompts:
+        if p.numel() + max_new_tokens > T:
+            raise ValueError(f"shared_prefix needs the KV-cache path: prompt ({p.numel()}) + new tokens "
+                             f"({max_new_tokens}) exceed block_size {T}, and the recompute loop has nothing to share")
+    need = S + max_new_tokens
+    own = (decoder is None or not decoder.shared or decoder.B != B or not decoder.per_row
+           or decoder.quantize != quantize or decoder.R < need)
+    dec = (Decoder(model, B, max_len=T, use_graph=use_graph, per_row=True, quantize=quantize, shared_prompt=True,
+                   max_new=need) if own else decoder)
+    try:
+        idx = torch.zeros(B, S, dtype=torch.int64, device=device)  # right-padded (any valid id)
+        for b, p in enumerate(prompts):
+            idx[b, :lens[b]] = p[P:]
+        dec.reseed()
+        dec.prefill_shared(prompts[0][:P].to(device))
+        logits = dec.prefill_suffixes(idx, torch.tensor(lens, dtype=torch.int64, device=device))
+        dec.sample_into(logits, temperature, top_k, stop_token, top_p, min_p)  # gen[b, P + lens[b]]
+        dec.run(max_new_tokens - 1, temperature, top_k, stop_token, top_p, min_p)
+        outs = []
+        for b, p in enumerate(prompts):
+            new = dec.gen[b, p.numel():p.numel() + max_new_tokens]
+            outs.append(torch.cat([p.to(device), _cut_at_stop(new, stop_token)]))
+        return outs
+    finally:
+        if own:
+            dec.release()
+
+
 @torch.no_grad()
 def generate_batch(model, prompts, max_new_tokens: int, temperature: float = 1.0, top_k: int | None = None,
                    stop_token: int | None = None, use_graph: bool | None = None,
                    decoder: "Decoder | None" = None, top_p: float | None = None,
                    min_p: float | None = None, quantize: str | None = None,
-                   kv_quantize: str | None = None, shared_prompt: bool = False) -> list[torch.Tensor]:
+                   kv_quantize: str | None = None, shared_prompt: bool = False,
+                   shared_prefix: bool = False) -> list[torch.Tensor]:
     """Generate for a list of prompts of unequal lengths as one batch.
 
     ``prompts``: 1-D token tensors, each of length >= 1.  Every result is its prompt followed
@@ -612,8 +713,18 @@ def generate_batch(model, prompts, max_new_tokens: int, temperature: float = 1.0
     row caches only its own new tokens (``Decoder(..., shared_prompt=True, max_new=
     max_new_tokens)``; ``decoder`` is reused only if it is such a one, and then keeps the
     prompt between calls).  A single prompt goes the ordinary way.  Prompt + new tokens past
-    block_size and ``kv_quantize`` raise ValueError.  Prompts that share only a prefix are not
-    covered: that needs a prefill over prefix + suffix."""
+    block_size and ``kv_quantize`` raise ValueError.
+
+    ``shared_prefix=True``: the prompts share a prefix (a system prompt followed by different
+    questions).  P = the longest common token prefix, at most the shortest prompt - 1 so that
+    every row keeps a suffix token (``common_prefix_len``); the prefix is encoded once, as a
+    single row, into the prompt caches, the suffixes are prefilled against it
+    (``Decoder.prefill_suffixes``) and every row caches its suffix and its new tokens only
+    (``Decoder(..., shared_prompt=True, per_row=True, max_new=longest suffix +
+    max_new_tokens)``; ``decoder`` is reused only if it is such a one, and then keeps the
+    prefix between calls).  One prompt, or no common prefix: the ordinary path.  ``kv_quantize``,
+    ``shared_prompt=True`` at the same time and a row whose prompt + new tokens exceed
+    block_size raise ValueError."""
     if quantize not in (None, "int8"):
         raise ValueError(f"quantize must be None or 'int8', got {quantize!r}")
     if kv_quantize not in (None, "int8"):
@@ -628,10 +739,20 @@ def generate_batch(model, prompts, max_new_tokens: int, temperature: float = 1.0
             raise ValueError("shared_prompt keeps bf16 caches: it cannot be combined with kv_quantize")
         if any(p.shape != prompts[0].shape or not torch.equal(p, prompts[0]) for p in prompts[1:]):
             raise ValueError("shared_prompt needs every prompt to be the same")
+    if shared_prefix:
+        if shared_prompt:
+            raise ValueError("shared_prefix and shared_prompt are two forms of sharing: pass one of them")
+        if kv_quantize:
+            raise ValueError("shared_prefix keeps bf16 caches: it cannot be combined with kv_quantize")
     if max_new_tokens <= 0:
         return list(prompts)
     T = model.config.block_size
     device = model.lm_head.weight.device
+    if shared_prefix and len(prompts) > 1:
+        P = common_prefix_len(prompts)
+        if P > 0:
+            return _generate_prefix(model, prompts, P, max_new_tokens, temperature, top_k, stop_token, use_graph,
+                                    decoder, top_p, min_p, quantize)
     if shared_prompt and len(prompts) > 1:
         p = prompts[0].to(device)
         new = _generate_shared(model, p, len(prompts), max_new_tokens, temperature, top_k, stop_token, use_graph,

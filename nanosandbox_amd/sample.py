@@ -19,7 +19,11 @@ path only, so it refuses ``--kv_cache=False``).  ``--kv_quantize=int8`` keeps th
 as int8 rows with one scale each (the same refusal).  ``--shared_prompt=True`` with
 ``--sample_batch=N`` encodes and caches the prompt once for the N rows of a batch and once
 for all rounds (``Decoder(shared_prompt=True)``); it refuses ``--prompts_file``,
-``--kv_cache=False`` and ``--kv_quantize``.
+``--kv_cache=False`` and ``--kv_quantize``.  ``--shared_prefix=True`` is the same for prompts that
+share only a prefix (``--prompts_file``: a system prompt followed by different questions): the
+longest common token prefix is encoded and cached once for the batch and for all rounds, and
+every row prefills only what it adds (``Decoder.prefill_suffixes``); it refuses
+``--kv_cache=False``, ``--kv_quantize`` and ``--shared_prompt``.
 """
 
 from __future__ import annotations
@@ -57,6 +61,7 @@ SAMPLE_DEFAULTS = dict(
     quantize="",  # "int8": int8 weight-only decoding on the KV-cache path (Decoder(quantize="int8")); "": off
     kv_quantize="",  # "int8": int8 KV caches, one scale per cache row (Decoder(kv_quantize="int8")); "": off
     shared_prompt=False,  # sample_batch > 1: encode and cache the prompt once for the batch (Decoder(shared_prompt=True))
+    shared_prefix=False,  # prompts_file / sample_batch > 1: encode and cache the prompts' common prefix once for the batch
 )
 
 
@@ -67,6 +72,7 @@ def _generate_batches(model, c, encode, decode, start, device):
     quantize = c["quantize"] or None
     kv_quantize = c["kv_quantize"] or None
     shared = bool(c["shared_prompt"])  # main() has refused prompts_file, kv_cache=False and kv_quantize with it
+    prefix = bool(c["shared_prefix"])  # main() has refused kv_cache=False, kv_quantize and shared_prompt with it
     if c["prompts_file"]:
         with open(c["prompts_file"], "r", encoding="utf-8") as f:
             texts = [ln.rstrip("\n") for ln in f if ln.strip()]
@@ -79,19 +85,23 @@ def _generate_batches(model, c, encode, decode, start, device):
         for batch in batches:
             prompts = [torch.tensor(encode(t), dtype=torch.long, device=device) for t in batch]
             if c["kv_cache"]:
-                from .runtime.decode import Decoder
+                from .runtime.decode import Decoder, common_prefix_len
                 B = len(prompts)
                 sh = shared and B > 1  # a last round of one sample goes the ordinary way
+                # shared_prefix: row caches for the longest suffix + the new tokens (no common prefix: ordinary)
+                P = common_prefix_len(prompts) if prefix and B > 1 else 0
                 if B not in decs:
-                    if sh:  # the prompt stays cached in the decoder: later rounds do not encode it again
+                    if sh or P:  # the prompt / prefix stays cached in the decoder: later rounds do not encode it again
+                        new = max(1, c["max_new_tokens"]) + (max(p.numel() for p in prompts) - P if P else 0)
                         decs[B] = Decoder(model, B, max_len=model.config.block_size, per_row=True, quantize=quantize,
-                                          shared_prompt=True, max_new=max(1, c["max_new_tokens"]))
+                                          shared_prompt=True, max_new=min(new, model.config.block_size))
                     else:
                         decs[B] = Decoder(model, B, max_len=model.config.block_size, per_row=True, quantize=quantize,
                                           kv_quantize=kv_quantize)
                 ys = model.generate_batch(prompts, c["max_new_tokens"], temperature=c["temperature"], top_k=c["top_k"],
                                           stop_token=stop, decoder=decs[B], top_p=c["top_p"], min_p=c["min_p"],
-                                          quantize=quantize, kv_quantize=kv_quantize, shared_prompt=sh)
+                                          quantize=quantize, kv_quantize=kv_quantize, shared_prompt=sh,
+                                          shared_prefix=prefix)
             else:
                 ys = [model.generate(p[None], c["max_new_tokens"], temperature=c["temperature"], top_k=c["top_k"],
                                      top_p=c["top_p"], min_p=c["min_p"])[0] for p in prompts]
@@ -155,6 +165,14 @@ def main(argv=None):
                              "cache to share")
         if c["kv_quantize"]:
             raise ValueError("--shared_prompt keeps bf16 caches: it cannot be combined with --kv_quantize")
+    if c["shared_prefix"]:
+        if c["shared_prompt"]:
+            raise ValueError("--shared_prefix and --shared_prompt are two forms of sharing: pass one of them")
+        if not c["kv_cache"]:
+            raise ValueError("--shared_prefix needs the KV-cache path: the recompute loop (--kv_cache=False) has no "
+                             "cache to share")
+        if c["kv_quantize"]:
+            raise ValueError("--shared_prefix keeps bf16 caches: it cannot be combined with --kv_quantize")
     quantize = c["quantize"] or None
     kv_quantize = c["kv_quantize"] or None
     torch.manual_seed(c["seed"])

@@ -29,6 +29,12 @@ settings on a ``Decoder(shared_prompt=True, max_new=--new + 1)``, every row cont
 prompt; with it the ``rows`` lines and their shared twins also carry ``ttft_ms``, the time from
 the start of the prefill to the first drawn token, and ``--samples`` adds
 ``sample_batch_shared``.
+``--shared_prefix --suffix N`` replaces the mode list by ``prefix_rows`` and ``prefix_shared``
+(interleaved, ``--repeat`` times): B prompts made of one random prefix of ``--prompt`` tokens and
+unequal random suffixes of 1 .. N tokens, on the unshared per-row decoder (right-padded
+``prefill(idx, lengths)``) and on the shared-prefix one (``prefill_shared`` +
+``prefill_suffixes``, ``max_new = N + --new + 1``); both lines carry ``ttft_ms``, and the shared
+one ``ttft_cached_ms``: the same with the prefix already in the decoder, as in every later round.
 """
 
 import argparse
@@ -97,6 +103,51 @@ def run_rows(model, idx, new, lengths=None, quantize=None, kv_quantize=None, sha
     return dt, ttft
 
 
+def suffix_lengths(B, n):
+    """1 .. n, spread evenly over the batch."""
+    return [n if B == 1 else 1 + (n - 1) * b // (B - 1) for b in range(B)]
+
+
+def run_prefix(model, prefix, suf, lengths, new, shared):
+    """Prompts prefix + suf[b, :lengths[b]] on the unshared per-row decoder or (shared) on the
+    shared-prefix one; the graph mode.  Returns (seconds of the timed steps, seconds from the
+    start of the prefill to the first drawn token: the prefix is encoded inside that window,
+    and (shared) the same for a second round, whose prefix the decoder already holds)."""
+    B, S = suf.shape
+    P = prefix.numel()
+    lens = torch.tensor(lengths, device=suf.device)
+    if shared:  # slots for the suffixes, the capture step and the timed ones
+        dec = Decoder(model, B, use_graph=True, per_row=True, shared_prompt=True, max_new=S + new + 1)
+    else:
+        dec = Decoder(model, B, use_graph=True, per_row=True)
+        idx = torch.cat([prefix[None].expand(B, -1), suf], dim=1)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    if shared:
+        dec.prefill_shared(prefix)
+        logits = dec.prefill_suffixes(suf, lens)
+    else:
+        logits = dec.prefill(idx, lens + P)
+    dec.sample_into(logits, 0.8, **SMP)
+    torch.cuda.synchronize()
+    ttft = time.perf_counter() - t0
+    dec.run(1, 0.8, **SMP)  # capture outside the timed loop
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    dec.run(new, 0.8, **SMP)
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    cached = None
+    if shared:
+        t0 = time.perf_counter()
+        dec.prefill_shared(prefix)
+        dec.sample_into(dec.prefill_suffixes(suf, lens), 0.8, **SMP)
+        torch.cuda.synchronize()
+        cached = time.perf_counter() - t0
+    dec.release()
+    return dt, ttft, cached
+
+
 def run_samples(model, prompt, n, new, batched, shared=False):
     """sample.py's flow for n samples of one prompt, decoder construction and capture
     included: one batch-1 decoder reused n times, or one generate_batch of n rows (shared: on
@@ -145,6 +196,10 @@ def main():
     ap.add_argument("--shared_prompt", action="store_true",
                     help="add shared-prompt twins of the rows modes (rows_shared, rows_int8_shared), ttft_ms on both, "
                          "and sample_batch_shared with --samples")
+    ap.add_argument("--shared_prefix", action="store_true",
+                    help="time prompts of one --prompt-token prefix + unequal suffixes (--suffix): the unshared "
+                         "per-row decoder (prefix_rows) against the shared-prefix one (prefix_shared), ttft_ms on both")
+    ap.add_argument("--suffix", type=int, default=32, help="--shared_prefix: the longest suffix (1 .. N over the batch)")
     ap.add_argument("--memory", action="store_true", help="add each run's peak allocated bytes (decoder_peak_mb)")
     ap.add_argument("--top_k", type=int, default=200, help="0: no top-k")
     ap.add_argument("--top_p", type=float, default=1.0, help="nucleus mass; 1.0: off")
@@ -164,7 +219,11 @@ def main():
         modes = [t for m in modes for t in ([m, f"{m}_kv8"] if m.partition("_")[0] in ("graph", "rows") else [m])]
     if a.shared_prompt:  # each shared twin right after its rows mode (bf16 caches only)
         modes = [t for m in modes for t in ([m, f"{m}_shared"] if m in ("rows", "rows_int8") else [m])]
+    if a.shared_prefix:
+        modes = ["prefix_rows", "prefix_shared"]
     block_size = GPTConfig().block_size
+    if a.shared_prefix and (a.suffix < 1 or a.prompt + a.suffix + a.new >= block_size):
+        ap.error(f"--prompt + --suffix + --new must stay below block_size ({block_size})")
     if any(m != "recompute" for m in modes) and a.prompt + a.new >= block_size:
         # a cached run feeds positions prompt .. prompt + new (one capture step, then --new timed
         # ones); the position table and the caches end at block_size - 1
@@ -187,7 +246,16 @@ def main():
                         torch.cuda.synchronize()
                         torch.cuda.reset_peak_memory_stats()
                         mem0 = torch.cuda.memory_allocated()
-                    if base in ("rows", "ragged"):
+                    if base == "prefix":
+                        n = a.new
+                        lens = suffix_lengths(B, a.suffix)
+                        suf = torch.randint(0, 50257, (B, a.suffix), device="cuda")
+                        run_prefix(model, idx[0], suf, lens, 4, "shared" in sfx)
+                        dt, t1, t2 = run_prefix(model, idx[0], suf, lens, n, "shared" in sfx)
+                        ttft = {"ttft_ms": round(t1 * 1e3, 3), "suffix": a.suffix}
+                        if t2 is not None:
+                            ttft["ttft_cached_ms"] = round(t2 * 1e3, 3)
+                    elif base in ("rows", "ragged"):
                         n = a.new
                         lens = ragged_lengths(B, a.prompt) if base == "ragged" else None
                         run_rows(model, idx, 4, lens, qz, kvq, "shared" in sfx)
