@@ -21,6 +21,10 @@
 // reduces the partial rows (split over row ranges, fp32 atomics) into the flat
 // gradient buffer.  Backward rows are software-pipelined (next row's loads in
 // flight while the current row is reduced).
+//
+// Widths: C % 8 == 0; forward C <= 8192 (16 register groups), backward C <= 5120 (its
+// 2 x [4][C] fp32 accumulators are 32·C bytes of the workgroup's 160 KiB of LDS); wider
+// backward calls return hipErrorInvalidValue before any launch.
 #include <type_traits>
 
 #include "common.h"
@@ -451,6 +455,13 @@ hipError_t launch_fwd(const void* x, const void* res, void* sum_out, const void*
   return hipGetLastError();
 }
 
+// The backward's dw / db accumulators take 8·C·4 bytes of dynamic LDS, and a workgroup can have
+// the CU's 160 KiB: C <= 5120.  (The forward keeps rows in registers: C <= 8192.)  Launches
+// above 64 KiB, up to all 160, need no function attribute on this runtime (measured at
+// C = 2056, 4104 and 5120).
+constexpr int kLnBwdMaxC = 5120;
+inline bool ln_bwd_c_ok(int C) { return C > 0 && C % 8 == 0 && C <= kLnBwdMaxC; }
+
 template <int NK, bool PIPE, typename XT, bool NT, bool H>
 hipError_t launch_bwd_split(int split, const void* dy, const void* x, const void* w, const void* mean,
                             const void* rstd, const void* dres, void* dx, void* dx_branch, void* dw_part,
@@ -527,7 +538,7 @@ NSA_API hipError_t nsa_layernorm_fwd_x32(const void* x, const void* res, void* s
 NSA_API hipError_t nsa_layernorm_bwd(const void* dy, const void* x, const void* w, const void* mean,
                                      const void* rstd, const void* dres, void* dx, void* dw_part, void* db_part,
                                      int N, int C, int nblk, hipStream_t s) {
-  if (C % 8 != 0 || C > 8192) return hipErrorInvalidValue;
+  if (!ln_bwd_c_ok(C)) return hipErrorInvalidValue;
   NSA_NK_SWITCH((C + 511) / 512, (launch_bwd<K_, bf16_t>(dy, x, w, mean, rstd, dres, dx, nullptr, dw_part, db_part,
                                                          N, C, nblk, s)));
 }
@@ -536,7 +547,7 @@ NSA_API hipError_t nsa_layernorm_bwd(const void* dy, const void* x, const void* 
 NSA_API hipError_t nsa_layernorm_bwd_x32(const void* dy, const void* x, const void* w, const void* mean,
                                          const void* rstd, const void* dres, void* dx, void* dx_branch,
                                          void* dw_part, void* db_part, int N, int C, int nblk, hipStream_t s) {
-  if (C % 8 != 0 || C > 8192) return hipErrorInvalidValue;
+  if (!ln_bwd_c_ok(C)) return hipErrorInvalidValue;
   NSA_NK_SWITCH((C + 511) / 512, (launch_bwd<K_, float>(dy, x, w, mean, rstd, dres, dx, dx_branch, dw_part, db_part,
                                                         N, C, nblk, s)));
 }
@@ -548,7 +559,7 @@ NSA_API hipError_t nsa_layernorm_bwd_x32s(const void* dy, const void* x, const v
                                           const void* rstd, const void* dres, void* dx, void* dx_branch,
                                           void* dw_part, void* db_part, int N, int C, int nblk, int split,
                                           hipStream_t s) {
-  if (C % 8 != 0 || C > 8192 || split < 0 || split > 3 || (nblk & ~(1 << 30)) >= (1 << 28))
+  if (!ln_bwd_c_ok(C) || split < 0 || split > 3 || (nblk & ~(1 << 30)) >= (1 << 28))
     return hipErrorInvalidValue;
   nblk |= split << 28;
   NSA_NK_SWITCH((C + 511) / 512, (launch_bwd<K_, float>(dy, x, w, mean, rstd, dres, dx, dx_branch, dw_part, db_part,
@@ -560,7 +571,7 @@ NSA_API hipError_t nsa_layernorm_bwd_x32s_h(const void* dy, const void* x, const
                                             const void* rstd, const void* dres, void* dx, void* dx_branch,
                                             void* dw_part, void* db_part, int N, int C, int nblk, int split,
                                             hipStream_t s) {
-  if (C % 8 != 0 || C > 8192 || split < 0 || split > 3 || (nblk & ~(1 << 30)) >= (1 << 28))
+  if (!ln_bwd_c_ok(C) || split < 0 || split > 3 || (nblk & ~(1 << 30)) >= (1 << 28))
     return hipErrorInvalidValue;
   nblk |= split << 28;
   NSA_NK_SWITCH((C + 511) / 512, (launch_bwd<K_, float, true>(dy, x, w, mean, rstd, dres, dx, dx_branch, dw_part,
@@ -598,10 +609,13 @@ NSA_API hipError_t nsa_layernorm_fwd_x32_h(const void* x, const void* res, void*
 NSA_API hipError_t nsa_layernorm_bwd_x32_h(const void* dy, const void* x, const void* w, const void* mean,
                                            const void* rstd, const void* dres, void* dx, void* dx_branch,
                                            void* dw_part, void* db_part, int N, int C, int nblk, hipStream_t s) {
-  if (C % 8 != 0 || C > 8192) return hipErrorInvalidValue;
+  if (!ln_bwd_c_ok(C)) return hipErrorInvalidValue;
   NSA_NK_SWITCH((C + 511) / 512, (launch_bwd<K_, float, true>(dy, x, w, mean, rstd, dres, dx, dx_branch, dw_part,
                                                               db_part, N, C, nblk, s)));
 }
+
+// stream size (N * C * sizeof of the stream's element) from which the nontemporal instantiations are taken
+NSA_API int64_t nsa_ln_nt_min_bytes() { return NSA_NT_MIN_BYTES; }
 
 // set the streaming-store policy of the LayerNorm kernels (on < 0: keep); returns the old one
 NSA_API int nsa_ln_set_nt(int on) {

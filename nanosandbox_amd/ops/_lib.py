@@ -71,6 +71,7 @@ _SIGNATURES = {
     "nsa_flash_set_variant": [c_int, c_int, c_int],
     "nsa_ew_set_nt": [c_int],
     "nsa_ln_set_nt": [c_int],
+    "nsa_ln_nt_min_bytes": [],
     "nsa_kv_append": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
     "nsa_decode_attn": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                         c_float, c_int, c_void_p],
@@ -166,7 +167,7 @@ _SIGNATURES = {
     "nsa_probe_mark": [c_void_p, c_void_p],
 }
 # entry points whose return value is not a hipError_t
-_RESTYPES = {"nsa_keysort_ws_bytes": c_int64}
+_RESTYPES = {"nsa_keysort_ws_bytes": c_int64, "nsa_ln_nt_min_bytes": c_int64}
 
 
 class KernelLibraryMissing(RuntimeError):

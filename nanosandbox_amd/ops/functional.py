@@ -380,6 +380,9 @@ def embedding(idx, wte, wpe, p: float, training: bool, dtype=F32, cdtype=None):
 # ----------------------------------------------------------------------------
 
 LN_EPS = 1e-5
+# widest row of the LayerNorm backward kernel: its dw / db accumulators take 32 * C bytes of the
+# 160 KiB of LDS a workgroup can have (layernorm.hip kLnBwdMaxC); the forward takes C <= 8192
+LN_BWD_MAX_C = 5120
 # LayerNorm backward grid: every block resident at once (3 x 256-thread blocks per
 # CU at the kernel's ~146 VGPRs, 256 CUs), rows strided over the blocks; measured
 # 144 us at 122880 x 768 (5.2 TB/s) vs 148-168 us for 1024-3072 blocks
@@ -560,6 +563,8 @@ class LayerNormFn(torch.autograd.Function):
             return ds, _drop_grad(ctx, dyb), None, None, None, None, None, None
         dy2 = dh.reshape(-1, C)
         if ctx.kern:
+            assert C <= LN_BWD_MAX_C, \
+                f"layernorm backward kernel: C <= LN_BWD_MAX_C = {LN_BWD_MAX_C} (32 * C bytes of LDS per workgroup)"
             x32 = x2.dtype == F32
             dy2 = dy2.contiguous()
             ds2 = ds.reshape(-1, C).contiguous() if ds is not None else None
@@ -641,8 +646,17 @@ def _colsum_into(p, partial):
     return out.to(p.dtype)
 
 
+def _ln_check_width(x, *ts):
+    """A kernel-path forward that will be differentiated is refused here when the backward
+    kernel cannot take its width, not later inside autograd."""
+    if x.is_cuda and x.shape[-1] > LN_BWD_MAX_C and torch.is_grad_enabled():
+        assert not any(t is not None and t.requires_grad for t in (x, *ts)), \
+            f"layernorm backward kernel: C <= LN_BWD_MAX_C = {LN_BWD_MAX_C} (32 * C bytes of LDS per workgroup)"
+
+
 def layer_norm(x, w, b, out_dtype=None):
     """LN(x); ``out_dtype`` (default x's dtype) is the dtype of the normalised output."""
+    _ln_check_width(x, w, b)
     return LayerNormFn.apply(x, None, w, b, out_dtype)
 
 
@@ -651,6 +665,7 @@ def layer_norm_pass(x, w, b, out_dtype=None):
     so its gradient enters the LayerNorm backward kernel as the residual input (one
     pass computes dx = LN'(dh) + ds) instead of being summed with LN's own input
     gradient by a separate add kernel."""
+    _ln_check_width(x, w, b)
     return LayerNormFn.apply(x, None, w, b, out_dtype, True)
 
 
@@ -668,6 +683,7 @@ def add_layer_norm(x, y, w, b, out_dtype=None, split_grad=False, drop_p=0.0):
     branch's resid dropout (nanoGPT ``resid_dropout``), x + dropout(y): fused into the
     LayerNorm kernel on the fp32-stream kernel path (the same mask and rounding as
     ``dropout``), a separate ``dropout`` elsewhere."""
+    _ln_check_width(x, y, w, b)
     if drop_p > 0:
         od = out_dtype or y.dtype
         if not (LN_DROPOUT and x.is_cuda and x.dtype == F32 and od in KDT and y.dtype == od):
