@@ -96,8 +96,8 @@ __global__ __launch_bounds__(kBlock) void xent_kernel(bf16_t* __restrict__ logit
       store8e<H>(lr + i * 8, f);
     }
   } else {
-    for (int i = threadIdx.x; i < V; i += kBlock) {
-      float p = valid ? __expf(e2f<H>(lr[i]) - M) * invS : 0.0f;
+    for (int i = threadIdx.x; i < ld; i += kBlock) {  // columns [V, ld): zero gradient
+      float p = valid && i < V ? __expf(e2f<H>(lr[i]) - M) * invS : 0.0f;
       if (valid && i == tgt) p -= 1.0f;
       lr[i] = f2e<H>(p);
     }

@@ -182,6 +182,17 @@ __global__ __launch_bounds__(256) void xent_bwd_prep_kernel(const bf16_t* __rest
   }
 }
 
+// p = s x as an fp32 value of its own.  For fp16 the compiler otherwise fuses the multiply with
+// the rounding of f2e (v_fma_mixlo_f16: one rounding of the exact product), which differs from
+// the xs that nsa_xent_bwd_prep stored (the fp32 product, then v_cvt_pk_f16_f32) where the fp32
+// product is an fp16 tie: the onehot term would take back a rounding the GEMM never saw.
+template <bool H>
+__device__ __forceinline__ float fix_prod(float s, float a) {
+  float p = s * a;
+  if constexpr (H) asm("" : "+v"(p));
+  return p;
+}
+
 // The onehot part of dW, per valid row r with target t:  gW[t] += E[r,t] (s x_r - bf16(s x_r))
 // - g x_r  (s = g / S): subtracts g x_r and takes back the rounding the GEMM's bf16 operand
 // put on the target entry's product.  fp32 atomics, one wave per row.
@@ -205,7 +216,7 @@ __global__ __launch_bounds__(256) void xent_dw_fix_kernel(const bf16_t* __restri
   // instruction over 2 KB and ran ~9x slower: 2.56 ms per micro-step at 122880 rows)
   for (int c = lane; c < C; c += 64) {
     const float a = e2f<H>(xr[c]);
-    const float p = s * a;
+    const float p = fix_prod<H>(s, a);
     const float pr = e2f<H>(f2e<H>(p));
     atomicAdd(gr + c, et * (p - pr) - g * a);
   }
@@ -232,7 +243,7 @@ struct XentFixRow {
     load8e<H>(x + row * ldx + c, a);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      const float p = s * a[j];
+      const float p = fix_prod<H>(s, a[j]);
       f[j] = et * (p - e2f<H>(f2e<H>(p))) - g * a[j];
     }
   }

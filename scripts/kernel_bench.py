@@ -123,7 +123,7 @@ def main():
         base = logits.clone()
 
         def xe():
-            _lib.call("nsa_xent_fwd", logits.data_ptr(), tg.data_ptr(), rl.data_ptr(), N, V, 1, st())
+            _lib.call("nsa_xent_fwd", logits.data_ptr(), tg.data_ptr(), rl.data_ptr(), N, V, V, 1, st())
 
         t = timeit(xe, iters=5, rounds=3)
         out["xent"] = {"us": t * 1e6, "GBps": 3 * N * V * 2 / t / 1e9}
