@@ -36,9 +36,13 @@
 
 namespace {
 
+// ROWS (nsa_kv_append_rows): row b of qkv goes to cache row rows[b] of a cache of Bc rows (an
+// admission into a running batch); an index outside 0 .. Bc - 1 writes nothing.
+template <bool ROWS>
 __global__ __launch_bounds__(256) void kv_append_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ kc,
                                                         bf16_t* __restrict__ vc, const int64_t* __restrict__ pos_dev,
-                                                        int pos0, int B, int S, int H, int D, int Tmax) {
+                                                        int pos0, int B, int S, int H, int D, int Tmax,
+                                                        const int64_t* __restrict__ rows, int Bc) {
   // one thread per 16-byte chunk of a K or V row: index = (((b*S + s)*2 + kv)*H + h)*cpr + c
   const int cpr = D / 8;
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -55,20 +59,27 @@ __global__ __launch_bounds__(256) void kv_append_kernel(const bf16_t* __restrict
   const int p = (pos_dev ? (int)*pos_dev : pos0) + s;
   if (p < 0 || p >= Tmax) return;
   const int C = H * D;
+  int64_t cb = b;  // the cache row
+  if (ROWS) {
+    cb = rows[b];
+    if (cb < 0 || cb >= Bc) return;
+  }
   const bf16_t* src = qkv + ((int64_t)b * S + s) * 3 * C + (1 + kv) * C + hh * D + c * 8;
-  bf16_t* dst = (kv ? vc : kc) + (((int64_t)b * H + hh) * Tmax + p) * D + c * 8;
+  bf16_t* dst = (kv ? vc : kc) + ((cb * H + hh) * Tmax + p) * D + c * 8;
   *reinterpret_cast<uint4*>(dst) = *reinterpret_cast<const uint4*>(src);
 }
 
 // kv_append_kernel for int8 caches (D = 64): an 8-lane group per K or V row, lane c holds the
 // row's values 8c .. 8c+7; index = (((b*S + s)*2 + kv)*H + h)*8 + c.  The row's absmax meets in
 // three shuffles inside the group (groups never straddle the early exits: 256 and the total are
-// multiples of 8, and the position is the group's).
+// multiples of 8, and the position and, with ROWS, the cache row are the group's).  ROWS: as above.
+template <bool ROWS>
 __global__ __launch_bounds__(256) void kv_append_kv8_kernel(const bf16_t* __restrict__ qkv, int8_t* __restrict__ kq,
                                                             float* __restrict__ ksc, int8_t* __restrict__ vq,
                                                             float* __restrict__ vsc,
                                                             const int64_t* __restrict__ pos_dev, int pos0, int B,
-                                                            int S, int H, int Tmax) {
+                                                            int S, int H, int Tmax,
+                                                            const int64_t* __restrict__ rows, int Bc) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const int64_t total = (int64_t)B * S * 2 * H * 8;
   if (i >= total) return;
@@ -82,6 +93,11 @@ __global__ __launch_bounds__(256) void kv_append_kv8_kernel(const bf16_t* __rest
   const int b = (int)(r / S);
   const int p = (pos_dev ? (int)*pos_dev : pos0) + s;
   if (p < 0 || p >= Tmax) return;
+  int64_t cb = b;  // the cache row
+  if (ROWS) {
+    cb = rows[b];
+    if (cb < 0 || cb >= Bc) return;
+  }
   const int C = H * DA_D;
   float x[8];
   load8(qkv + ((int64_t)b * S + s) * 3 * C + (1 + kv) * C + hh * DA_D + c * 8, x);
@@ -93,7 +109,7 @@ __global__ __launch_bounds__(256) void kv_append_kv8_kernel(const bf16_t* __rest
   const float sc = kv8_scale(am);
 #pragma unroll
   for (int j = 0; j < 8; ++j) x[j] = kv8_quant(x[j], sc);
-  const int64_t row = ((int64_t)b * H + hh) * Tmax + p;
+  const int64_t row = (cb * H + hh) * Tmax + p;
   *reinterpret_cast<uint2*>((kv ? vq : kq) + row * DA_D + c * 8) =
       uint2{kv8_pack4(x[0], x[1], x[2], x[3]), kv8_pack4(x[4], x[5], x[6], x[7])};
   if (c == 0) (kv ? vsc : ksc)[row] = sc;
@@ -333,8 +349,19 @@ NSA_API hipError_t nsa_kv_append(const void* qkv, void* kc, void* vc, const void
                                  int D, int Tmax, hipStream_t s) {
   if (D % 8 || B < 1 || S < 1) return hipErrorInvalidValue;
   const int64_t total = (int64_t)B * S * 2 * H * (D / 8);
-  kv_append_kernel<<<(unsigned)((total + 255) / 256), 256, 0, s>>>(
-      (const bf16_t*)qkv, (bf16_t*)kc, (bf16_t*)vc, (const int64_t*)pos, pos0, B, S, H, D, Tmax);
+  kv_append_kernel<false><<<(unsigned)((total + 255) / 256), 256, 0, s>>>(
+      (const bf16_t*)qkv, (bf16_t*)kc, (bf16_t*)vc, (const int64_t*)pos, pos0, B, S, H, D, Tmax, nullptr, B);
+  return hipGetLastError();
+}
+
+// nsa_kv_append into chosen cache rows: the K / V rows of qkv [n, S, 3C] go to cache row rows[j]
+// (int64 [n] on the device, distinct, each < B) of caches [B, H, Tmax, D]; one launch for any n.
+NSA_API hipError_t nsa_kv_append_rows(const void* qkv, void* kc, void* vc, const void* rows, int pos0, int n, int B,
+                                      int S, int H, int D, int Tmax, hipStream_t s) {
+  if (D % 8 || n < 1 || B < 1 || S < 1 || pos0 < 0 || !rows) return hipErrorInvalidValue;
+  const int64_t total = (int64_t)n * S * 2 * H * (D / 8);
+  kv_append_kernel<true><<<(unsigned)((total + 255) / 256), 256, 0, s>>>(
+      (const bf16_t*)qkv, (bf16_t*)kc, (bf16_t*)vc, nullptr, pos0, n, S, H, D, Tmax, (const int64_t*)rows, B);
   return hipGetLastError();
 }
 
@@ -344,8 +371,20 @@ NSA_API hipError_t nsa_kv_append_kv8(const void* qkv, void* kq, void* ksc, void*
                                      int pos0, int B, int S, int H, int D, int Tmax, hipStream_t s) {
   if (D != DA_D || B < 1 || S < 1 || H < 1 || Tmax < 1) return hipErrorInvalidValue;
   const int64_t total = (int64_t)B * S * 2 * H * 8;
-  kv_append_kv8_kernel<<<(unsigned)((total + 255) / 256), 256, 0, s>>>(
-      (const bf16_t*)qkv, (int8_t*)kq, (float*)ksc, (int8_t*)vq, (float*)vsc, (const int64_t*)pos, pos0, B, S, H, Tmax);
+  kv_append_kv8_kernel<false><<<(unsigned)((total + 255) / 256), 256, 0, s>>>(
+      (const bf16_t*)qkv, (int8_t*)kq, (float*)ksc, (int8_t*)vq, (float*)vsc, (const int64_t*)pos, pos0, B, S, H, Tmax,
+      nullptr, B);
+  return hipGetLastError();
+}
+
+// nsa_kv_append_rows for int8 caches (D = 64): the same quantizer, into cache rows rows[j].
+NSA_API hipError_t nsa_kv_append_rows_kv8(const void* qkv, void* kq, void* ksc, void* vq, void* vsc, const void* rows,
+                                          int pos0, int n, int B, int S, int H, int D, int Tmax, hipStream_t s) {
+  if (D != DA_D || n < 1 || B < 1 || S < 1 || H < 1 || Tmax < 1 || pos0 < 0 || !rows) return hipErrorInvalidValue;
+  const int64_t total = (int64_t)n * S * 2 * H * 8;
+  kv_append_kv8_kernel<true><<<(unsigned)((total + 255) / 256), 256, 0, s>>>(
+      (const bf16_t*)qkv, (int8_t*)kq, (float*)ksc, (int8_t*)vq, (float*)vsc, nullptr, pos0, n, S, H, Tmax,
+      (const int64_t*)rows, B);
   return hipGetLastError();
 }
 

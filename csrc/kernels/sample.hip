@@ -48,6 +48,15 @@
 // instantiation's registers or spills.  FILT = true with top_p >= 1 and min_p <= 0 takes
 // the same steps (same thresholds, same summation order), so it draws the same ids.
 //
+// REQ = true is the serving queue's form (nsa_sample_requests), an instantiation of its own so
+// that the four above keep their registers (kernel-resource-usage, VGPRs / VGPR spills / SGPR
+// spills / LDS bytes: VEC4 FILT 128 / 25 / 74 / 53700, scalar FILT 128 / 14 / 74 / 53700, VEC4
+// top-k 96 / 0 / 34 / 41220, scalar top-k 124 / 0 / 34 / 41220, with and without the REQ
+// parameters in the signature; the REQ forms: 128 / 21 / 78, 128 / 14 / 78, 96 / 0 / 36,
+// 124 / 0 / 36).  row_key[b] replaces b in the hash, so a request draws the same stream in
+// whatever row it is served, and a row that writes its id at a position >= end[b] sets done[b]
+// where the stop token sets it; both are read once, the end position by the writing thread alone.
+//
 // The chosen id is written to tok[b] and gen[b, pos] (pos = *pos, or pos[b] in the per-row
 // form, where a row whose done[b] is set is skipped and a row that draws stop_token sets
 // it).  stats (int32 [B, 2], may be NULL): the row's kept count and the bits of its
@@ -276,12 +285,12 @@ __device__ __forceinline__ float mass_exp2(float x) { return __builtin_amdgcn_ex
 
 constexpr int SMP_NUC_LO = 832, SMP_NUC_HI = 928;  // per-thread maxima >= lo0 on the nucleus-only path
 
-template <bool VEC4, bool FILT>
+template <bool VEC4, bool FILT, bool REQ>
 __global__ __launch_bounds__(SMP_THREADS) void sample_kernel(
     const float* __restrict__ logits, int V, int ld, float scale_log2, int top_k, float top_p, float min_p,
     uint64_t salt, const uint64_t* __restrict__ salt_dev, const int64_t* __restrict__ pos, int pos_stride,
     int64_t* __restrict__ tok, int64_t* __restrict__ gen, int gen_ld, int stop_token, int64_t* done,
-    int32_t* __restrict__ stats) {
+    int32_t* __restrict__ stats, const int64_t* __restrict__ row_key, const int64_t* __restrict__ end) {
   __shared__ uint32_t redu[SMP_THREADS / 64];
   __shared__ float redf[SMP_THREADS / 64];
   __shared__ __attribute__((aligned(16))) uint32_t tmx[SMP_THREADS];
@@ -344,7 +353,9 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_kernel(
   // the device salt (when given) is read at run time, so a captured sampling graph draws a
   // fresh stream whenever the caller rewrites it (one per generate call)
   const uint64_t sl = salt ^ (salt_dev ? *salt_dev : 0ull);
-  const uint32_t hsh = nsa_hash(nsa_seed(sl), (uint64_t)b * 0x9E3779B97F4A7C15ull + (uint64_t)p);
+  // the stream is the row's, or (row_key) the request's: the same draws in whatever row it is served
+  const uint64_t hk = REQ && row_key ? (uint64_t)row_key[b] : (uint64_t)b;
+  const uint32_t hsh = nsa_hash(nsa_seed(sl), hk * 0x9E3779B97F4A7C15ull + (uint64_t)p);
   const float unif = (float)(hsh >> 8) * (1.0f / 16777216.0f);
 
   const bool use_k = top_k > 0 && top_k < V;
@@ -507,7 +518,8 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_kernel(
             if (ck[i] >= thr) pick = ci[i];
           tok[b] = pick;
           gen[(int64_t)b * gen_ld + p] = pick;
-          if (done && pick == stop_token) done[b] = 1;  // stop_token < 0: never (pick >= 0)
+          // stop_token < 0: never (pick >= 0); end: the row's last position (read by the writer alone)
+          if (done && (pick == stop_token || (REQ && end && (int64_t)p >= end[b]))) done[b] = 1;
         }
       }
       return;
@@ -611,7 +623,7 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_kernel(
     }
     tok[b] = pick;
     gen[(int64_t)b * gen_ld + p] = pick;
-    if (done && pick == stop_token) done[b] = 1;
+    if (done && (pick == stop_token || (REQ && end && (int64_t)p >= end[b]))) done[b] = 1;
   }
 }
 
@@ -619,16 +631,24 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_kernel(
 hipError_t sample_launch(bool filt, const void* logits, int B, int V, int ld, float temperature, int top_k,
                          uint64_t salt, const void* salt_dev, const void* pos, int pos_stride, void* tok, void* gen,
                          int gen_ld, int stop_token, void* done, float top_p, float min_p, void* stats,
-                         hipStream_t s) {
+                         const void* row_key, const void* end, hipStream_t s) {
   if (B < 1 || V < 1 || V > SMP_THREADS * SMP_MAXC || !(temperature > 0.0f)) return hipErrorInvalidValue;
   if (pos_stride != 0 && pos_stride != 1) return hipErrorInvalidValue;
   if (!(top_p > 0.0f && top_p <= 1.0f) || !(min_p >= 0.0f && min_p < 1.0f)) return hipErrorInvalidValue;
+  if (end && !done) return hipErrorInvalidValue;  // an end position finishes a row through its flag
   const bool vec4 = V % 4 == 0 && ld % 4 == 0 && ((uintptr_t)logits & 15) == 0;
-  const auto kernel = filt ? (vec4 ? sample_kernel<true, true> : sample_kernel<false, true>)
-                           : (vec4 ? sample_kernel<true, false> : sample_kernel<false, false>);
+  // REQ (a row key or an end position is given) is an instantiation of its own: the four others
+  // compile both away and keep their registers
+  const bool req = row_key || end;
+  const auto kernel =
+      req ? (filt ? (vec4 ? sample_kernel<true, true, true> : sample_kernel<false, true, true>)
+                  : (vec4 ? sample_kernel<true, false, true> : sample_kernel<false, false, true>))
+          : (filt ? (vec4 ? sample_kernel<true, true, false> : sample_kernel<false, true, false>)
+                  : (vec4 ? sample_kernel<true, false, false> : sample_kernel<false, false, false>));
   kernel<<<B, SMP_THREADS, 0, s>>>((const float*)logits, V, ld, 1.4426950408889634f / temperature, top_k, top_p, min_p,
                                    salt, (const uint64_t*)salt_dev, (const int64_t*)pos, pos_stride, (int64_t*)tok,
-                                   (int64_t*)gen, gen_ld, stop_token, (int64_t*)done, (int32_t*)stats);
+                                   (int64_t*)gen, gen_ld, stop_token, (int64_t*)done, (int32_t*)stats,
+                                   (const int64_t*)row_key, (const int64_t*)end);
   return hipGetLastError();
 }
 
@@ -641,7 +661,7 @@ NSA_API hipError_t nsa_sample_topk(const void* logits, int B, int V, int ld, flo
                                    uint64_t salt, const void* salt_dev, const void* pos, void* tok, void* gen,
                                    int gen_ld, hipStream_t s) {
   return sample_launch(false, logits, B, V, ld, temperature, top_k, salt, salt_dev, pos, 0, tok, gen, gen_ld, -1,
-                       nullptr, 1.0f, 0.0f, nullptr, s);
+                       nullptr, 1.0f, 0.0f, nullptr, nullptr, nullptr, s);
 }
 
 // The per-row form: row b draws at position pos[b * pos_stride] (pos_stride 1: int64[B];
@@ -652,7 +672,7 @@ NSA_API hipError_t nsa_sample_topk_rows(const void* logits, int B, int V, int ld
                                         uint64_t salt, const void* salt_dev, const void* pos, int pos_stride,
                                         void* tok, void* gen, int gen_ld, int stop_token, void* done, hipStream_t s) {
   return sample_launch(false, logits, B, V, ld, temperature, top_k, salt, salt_dev, pos, pos_stride, tok, gen, gen_ld,
-                       stop_token, done, 1.0f, 0.0f, nullptr, s);
+                       stop_token, done, 1.0f, 0.0f, nullptr, nullptr, nullptr, s);
 }
 
 // Top-k, nucleus and min-p sampling: top_p in (0, 1] (1: off), min_p in [0, 1) (0: off), the
@@ -663,5 +683,20 @@ NSA_API hipError_t nsa_sample_filtered(const void* logits, int B, int V, int ld,
                                        int pos_stride, void* tok, void* gen, int gen_ld, int stop_token, void* done,
                                        void* stats, hipStream_t s) {
   return sample_launch(true, logits, B, V, ld, temperature, top_k, salt, salt_dev, pos, pos_stride, tok, gen, gen_ld,
-                       stop_token, done, top_p, min_p, stats, s);
+                       stop_token, done, top_p, min_p, stats, nullptr, nullptr, s);
+}
+
+// The serving queue's form: filt != 0 is nsa_sample_filtered (top_p, min_p, stats), otherwise
+// nsa_sample_topk_rows, with two more per-row inputs, either of which may be NULL.  row_key
+// (int64 [B]): the hash takes row_key[b] where it takes b, so a request draws the same stream
+// in whatever row it is served.  end (int64 [B]; needs done): a row that has written its id at
+// position p sets done[b] = 1 if p >= end[b], where the stop token sets it.
+NSA_API hipError_t nsa_sample_requests(const void* logits, int B, int V, int ld, float temperature, int top_k,
+                                       int filt, float top_p, float min_p, uint64_t salt, const void* salt_dev,
+                                       const void* pos, int pos_stride, void* tok, void* gen, int gen_ld,
+                                       int stop_token, void* done, void* stats, const void* row_key, const void* end,
+                                       hipStream_t s) {
+  if (!filt && (top_p != 1.0f || min_p != 0.0f || stats)) return hipErrorInvalidValue;
+  return sample_launch(filt != 0, logits, B, V, ld, temperature, top_k, salt, salt_dev, pos, pos_stride, tok, gen,
+                       gen_ld, stop_token, done, top_p, min_p, stats, row_key, end, s);
 }

@@ -395,16 +395,18 @@ class GPT(nn.Module):
     @torch.no_grad()
     def generate_batch(self, prompts, max_new_tokens, temperature=1.0, top_k=None, stop_token=None, use_graph=None,
                        decoder=None, top_p=None, min_p=None, quantize=None, kv_quantize=None, shared_prompt=False,
-                       shared_prefix=False):
+                       shared_prefix=False, batch_size=None):
         """``generate_cached`` for a list of 1-D prompts of unequal lengths, decoded as one
         batch with a position per row; returns a list of 1-D tensors (prompt + new tokens).
         A row that draws ``stop_token`` ends with it; the others get exactly
         ``max_new_tokens`` new tokens (``runtime/decode.py``).  ``shared_prompt=True``: the
         prompts are all the same one, encoded and cached once for the batch.
         ``shared_prefix=True``: the prompts' longest common token prefix is encoded and cached
-        once, and every row prefills only what it adds to it."""
+        once, and every row prefills only what it adds to it.  ``batch_size=B`` (and / or
+        ``max_new_tokens`` as one int per prompt): the prompts are a queue served in order through
+        at most B rows, a finished row taking the next prompt; results in prompt order."""
         from ..runtime.decode import generate_batch
         return generate_batch(self, prompts, max_new_tokens, temperature=temperature, top_k=top_k,
                               stop_token=stop_token, use_graph=use_graph, decoder=decoder, top_p=top_p, min_p=min_p,
                               quantize=quantize, kv_quantize=kv_quantize, shared_prompt=shared_prompt,
-                              shared_prefix=shared_prefix)
+                              shared_prefix=shared_prefix, batch_size=batch_size)

@@ -83,6 +83,15 @@ _SIGNATURES = {
                              c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p],
     "nsa_sample_filtered": [c_void_p, c_int, c_int, c_int, c_float, c_int, c_float, c_float, c_uint64, c_void_p,
                             c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p],
+    # the serving queue's sampler: nsa_sample_filtered's arguments with filt before top_p and row_key, end last
+    "nsa_sample_requests": [c_void_p, c_int, c_int, c_int, c_float, c_int, c_int, c_float, c_float, c_uint64,
+                            c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
+                            c_void_p, c_void_p, c_void_p],
+    # row-mapped appends: qkv, caches, rows, pos0, n, B, S, H, D, Tmax
+    "nsa_kv_append_rows": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                           c_void_p],
+    "nsa_kv_append_rows_kv8": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                               c_int, c_int, c_int, c_int, c_void_p],
     "nsa_pos_advance": [c_void_p, c_void_p, c_int, c_void_p],
     "nsa_gemv":[c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p],
     "nsa_skinny_gemm": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p],

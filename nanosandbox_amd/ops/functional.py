@@ -970,16 +970,39 @@ def _cache_rows(c, index):
     return c[index].float()
 
 
-def kv_append(qkv, kc, vc, pos=None, pos0: int = 0):
+def kv_append(qkv, kc, vc, pos=None, pos0: int = 0, rows=None):
     """Write the K / V rows of ``qkv`` [B, S, 3C] into the caches [B, H, Tmax, D] at
     positions p0 .. p0+S-1, p0 = ``pos`` (int64 device tensor, graph-safe) or ``pos0``.
     ``pos`` with one entry per row (B > 1) places every row at its own p0 (eager torch).
     ``kc`` / ``vc`` may be ``QuantCache``s: every row is stored quantized
-    (``quantize_cache_rows``; GPU, bf16, D = 64: ``nsa_kv_append_kv8``)."""
+    (``quantize_cache_rows``; GPU, bf16, D = 64: ``nsa_kv_append_kv8``).
+
+    ``rows`` (int64 tensor on the caches' device, n = ``qkv.shape[0]`` distinct cache-row
+    indices, each < B): ``qkv`` is [n, S, 3C] and row j goes to cache row ``rows[j]`` at
+    positions ``pos0`` .. (an admission into a running batch; ``pos`` must be None).  One
+    launch for any n on the GPU (``nsa_kv_append_rows`` / ``_kv8``); torch elsewhere."""
     B, S, C3 = qkv.shape
-    _, H, Tmax, D = kc.shape
+    Bc, H, Tmax, D = kc.shape
     kv8 = isinstance(kc, QuantCache)
     assert kv8 == isinstance(vc, QuantCache), "K and V caches of one form"
+    if rows is not None:
+        assert pos is None, "a row map places the rows at the host position pos0"
+        assert rows.dtype == torch.int64 and rows.numel() == B and rows.device == qkv.device
+        assert 0 <= int(pos0) and int(pos0) + S <= Tmax
+        rows = rows.contiguous().view(B)
+        if qkv.is_cuda and qkv.dtype == BF16 and (D == 64 if kv8 else D % 8 == 0):
+            qkv = qkv.contiguous()
+            if kv8:
+                _lib.call("nsa_kv_append_rows_kv8", _lib.ptr(qkv), _lib.ptr(kc.q), _lib.ptr(kc.scale), _lib.ptr(vc.q),
+                          _lib.ptr(vc.scale), _lib.ptr(rows), int(pos0), B, Bc, S, H, D, Tmax, _lib.stream())
+            else:
+                _lib.call("nsa_kv_append_rows", _lib.ptr(qkv), _lib.ptr(kc), _lib.ptr(vc), _lib.ptr(rows), int(pos0),
+                          B, Bc, S, H, D, Tmax, _lib.stream())
+            return
+        k, v = qkv.view(B, S, 3, H, D)[:, :, 1:].permute(2, 0, 3, 1, 4)
+        _cache_store(kc, (rows, slice(None), slice(int(pos0), int(pos0) + S)), k)
+        _cache_store(vc, (rows, slice(None), slice(int(pos0), int(pos0) + S)), v)
+        return
     if pos is not None and pos.numel() > 1:
         assert pos.numel() == B
         if kv8 and qkv.is_cuda and qkv.dtype == BF16 and D == 64:  # the kernel, row by row
@@ -1384,7 +1407,7 @@ def filter_logits(z, top_k=None, top_p=None, min_p=None):
 
 
 def sample_topk_(logits, temperature: float, top_k, salt: int, pos, tok, gen, salt_dev=None, stop_token=None,
-                 done=None, top_p=None, min_p=None, stats=None):
+                 done=None, top_p=None, min_p=None, stats=None, row_key=None, end=None):
     """Device-side nanoGPT sampling (logits / temperature, top-k, softmax, multinomial)
     of logits [B, V] fp32: the drawn ids go to ``tok`` [B, 1] and ``gen[:, pos]``
     (``pos``: int64 device tensor with one entry, or with B entries: row b writes
@@ -1400,7 +1423,14 @@ def sample_topk_(logits, temperature: float, top_k, salt: int, pos, tok, gen, sa
     (``filter_logits`` states the rule; ``top_k`` 0 or None keeps every id).  ``stats``
     (int32 [B, 2], optional) receives every drawing row's kept count and the bits of its
     smallest kept logit.  With all three left at None the call is the top-k sampler's,
-    launch for launch."""
+    launch for launch.
+
+    The serving queue's two per-row inputs (int64 [B] each; with either one the GPU call is
+    ``nsa_sample_requests``, without them the three calls above, launch for launch):
+    ``row_key``: the hash takes ``row_key[b]`` where it takes the row index b, so a request
+    draws the same stream in whatever row it is served.  It is accepted and ignored on the
+    CPU, where the draw is ``torch.multinomial``.  ``end`` (needs ``done``): a row that has
+    written its id at position p sets ``done[b]`` if ``p >= end[b]``, as the stop token does."""
     B, V = logits.shape
     check_sampling_filters(top_p, min_p)
     filtered = top_p is not None or min_p is not None or stats is not None
@@ -1412,8 +1442,19 @@ def sample_topk_(logits, temperature: float, top_k, salt: int, pos, tok, gen, sa
     stop = -1 if stop_token is None else int(stop_token)
     if done is not None:
         assert done.numel() == B and done.dtype == torch.int64 and done.is_contiguous()
+    for t in (row_key, end):
+        if t is not None:
+            assert t.numel() == B and t.dtype == torch.int64 and t.is_contiguous() and t.device == logits.device
+    assert end is None or done is not None, "an end position finishes a row through its done flag"
     if logits.is_cuda:
         lg = logits if logits.dtype == F32 and logits.stride(1) == 1 else logits.float().contiguous()
+        if row_key is not None or end is not None:
+            _lib.call("nsa_sample_requests", _lib.ptr(lg), B, V, lg.stride(0), float(temperature), k,
+                      1 if filtered else 0, 1.0 if top_p is None else float(top_p),
+                      0.0 if min_p is None else float(min_p), int(salt) & (2 ** 64 - 1), _lib.ptr(salt_dev),
+                      _lib.ptr(pos), 1 if per_row else 0, _lib.ptr(tok), _lib.ptr(gen), gen.stride(0), stop,
+                      _lib.ptr(done), _lib.ptr(stats), _lib.ptr(row_key), _lib.ptr(end), _lib.stream())
+            return
         if filtered:
             _lib.call("nsa_sample_filtered", _lib.ptr(lg), B, V, lg.stride(0), float(temperature), k,
                       1.0 if top_p is None else float(top_p), 0.0 if min_p is None else float(min_p),
@@ -1445,6 +1486,8 @@ def sample_topk_(logits, temperature: float, top_k, salt: int, pos, tok, gen, sa
     gen[rows, pos.view(-1).expand(B)[rows]] = nxt.view(B)[rows]
     if done is not None and stop >= 0:
         done.view(B)[live & (nxt.view(B) == stop)] = 1
+    if end is not None:
+        done.view(B)[live & (pos.view(-1).expand(B) >= end.view(B))] = 1
 
 
 def advance_pos_(pos, done):

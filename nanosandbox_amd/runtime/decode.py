@@ -71,6 +71,18 @@ cache plus the row's own earlier suffix keys (``ops.prefix_attention``: one atte
 that reads the prefix cache where it lies, so nothing is materialised per row and no prefix
 query is computed again).  ``pos`` becomes P + lengths and the steps are the shared-prompt
 ones, unchanged: a row's slots hold suffix and generated tokens alike (slot = position - P).
+A queue of prompts longer than the batch (``generate_batch(..., batch_size=B)`` or one budget
+per prompt, ``sample.py --serve_batch=B``) is served through B rows of a per_row decoder whose
+finished rows are refilled (``Decoder.serve``).  Three per-row things make a row reusable: its
+token budget is on the device (``end``: the position of the request's last token; the sampler
+finishes the row there as it does at the stop token), its sampling stream is keyed by the
+request (``key``), not the row, and ``admit(rows, idx, lengths)`` prefills new prompts into a
+chosen subset of rows of the running caches (``ops.kv_append(rows=)``: one launch per layer)
+without touching any other row; on a shared_prompt decoder an admission only puts the row back
+to the prompt's end.  The loop replays the captured step ``DONE_POLL`` times (``run(...,
+queue=True)``: the same step with the keyed sampler, a graph of its own), reads ``done`` and
+``pos`` back once, harvests the finished rows, admits the next prompts into all freed rows in
+one pass and draws their first tokens alone (``sample_admitted``); no step waits for the host.
 The caches hold at most ``block_size`` positions; ``GPT.generate_cached`` falls
 back to the recompute loop when prompt + new tokens exceed that (nanoGPT crops the
 context there, which a cache cannot do without re-encoding).
@@ -164,6 +176,12 @@ class Decoder:
         # per-call part of the sampling stream, read by the kernel at run time (so a captured
         # sampling graph, reused across generate calls, draws independent samples each call)
         self.salt_dev = torch.zeros(1, device=self.device, dtype=torch.int64)
+        # the serving queue's per-row state (int64 [B] each, allocated when first used): the request a
+        # row serves, which keys its sampling stream, and the position of the request's last token
+        self.key = None
+        self.end = None
+        self.queue_stats = {"steps": 0, "admissions": 0, "admitted": 0}
+        self._admit_logits = None  # [B, V] fp32: the admitted rows' logits at their own row indices
         self.use_graph = (self.device.type == "cuda") if use_graph is None else use_graph
         if self.use_graph and not self.graph_capable(model):
             # the fused decode kernels cover head_dim 64, bf16 and V <= 53248; the fallback
@@ -246,11 +264,12 @@ class Decoder:
         self.sgraphs = {}
 
     # ------------------------------------------------------------------ layers
-    def _prefill_layers(self, x, kc=None, vc=None, prefix=None):
+    def _prefill_layers(self, x, kc=None, vc=None, prefix=None, rows=None):
         """The prompt x through every block; its K / V rows go to the caches ``kc`` / ``vc``
         (default: the decoder's own; ``prefill_shared`` passes the prompt caches).  ``prefix``
         (``prefill_suffixes``: the prefix length P): x holds the suffixes that follow the cached
-        prefix, and every query also attends over prompt-cache rows 0 .. P - 1."""
+        prefix, and every query also attends over prompt-cache rows 0 .. P - 1.  ``rows``
+        (``admit``; int64 [n] on the device): row j of x is cache row ``rows[j]``."""
         kc, vc = kc or self.kc, vc or self.vc
         tr = self.model.transformer
         blocks = tr.h
@@ -260,7 +279,7 @@ class Decoder:
             nxt = blocks[i + 1].ln_1 if i + 1 < len(blocks) else tr.ln_f
             attn, mlp = block.attn, block.mlp
             qkv = ops.linear(h, attn.c_attn.weight, attn.c_attn.bias)
-            ops.kv_append(qkv, kc[i], vc[i], None, 0)
+            ops.kv_append(qkv, kc[i], vc[i], None, 0, rows=rows)
             if prefix is None:
                 y = ops.attention(qkv, attn.n_head, 0.0, False)
             else:
@@ -405,6 +424,172 @@ class Decoder:
         last = h[torch.arange(B, device=self.device), lengths - 1].unsqueeze(1)  # [B, 1, C]
         return ops.lm_head_logits(last, self.model.lm_head.weight)[:, 0]
 
+    def _row_index(self, rows) -> torch.Tensor:
+        """``rows`` (a list or tensor of distinct cache-row indices < B) as int64 [n] on the device."""
+        host = rows.tolist() if torch.is_tensor(rows) else [int(r) for r in rows]
+        assert host and len(set(host)) == len(host) and all(0 <= r < self.B for r in host), \
+            f"rows must be distinct indices in 0 .. {self.B - 1}, got {host}"
+        return torch.tensor(host, dtype=torch.int64, device=self.device)
+
+    @torch.no_grad()
+    def admit(self, rows, idx: torch.Tensor | None = None, lengths: torch.Tensor | None = None) -> torch.Tensor:
+        """Start new prompts in the cache rows ``rows`` (n distinct indices) of a running per_row
+        batch; returns their last-position logits [n, V].  Every other row's caches, ``pos``,
+        ``done``, ``tok`` and ``gen`` stay bit for bit as they were.
+
+        Ordinary decoder: ``idx`` [n, S] holds the right-padded prompts (``lengths``: int64 [n], as in
+        ``prefill``; None: every prompt has S tokens); they run through the model as a batch of
+        n, the same kernels on the same shapes as ``Decoder(model, n).prefill(idx, lengths)``,
+        with their K / V rows going to cache rows ``rows`` (``ops.kv_append(rows=)``: one launch
+        per layer for any n).  ``pos[rows]`` becomes ``lengths`` and ``done[rows]`` 0.
+
+        ``shared_prompt`` decoder, after ``prefill_shared``: no ``idx`` and no model pass; a row
+        only goes back to the prompt's end (``pos[rows] = plen``, ``done[rows] = 0``) and the kept
+        prompt logits are returned, expanded to n rows."""
+        assert self.per_row, "admit needs Decoder(..., per_row=True): a position and a finished flag per row"
+        rows = self._row_index(rows)
+        n = rows.numel()
+        if self.shared:
+            assert idx is None and lengths is None, "a shared_prompt decoder admits rows of its one prompt"
+            assert self._prompt is not None, "admit follows prefill_shared(prompt)"
+            self.pos.index_copy_(0, rows, self.plen.expand(n))
+            self.done.index_fill_(0, rows, 0)
+            return self._prompt_logits.expand(n, -1)
+        assert idx is not None and idx.dim() == 2 and idx.shape[0] == n and 1 <= idx.shape[1] <= self.T
+        S = idx.shape[1]
+        idx = idx.to(self.device)
+        if lengths is None:
+            lengths = torch.full((n,), S, dtype=torch.int64, device=self.device)
+        else:
+            lengths = torch.as_tensor(lengths, dtype=torch.int64).to(self.device).view(n)
+            assert int(lengths.min()) >= 1 and int(lengths.max()) <= S
+        tr = self.model.transformer
+        x = ops.embedding(idx, tr.wte.weight, tr.wpe.weight, 0.0, False, dtype=self.rdtype, cdtype=self.dtype)
+        h = self._prefill_layers(x, rows=rows)
+        self.pos.index_copy_(0, rows, lengths)
+        self.done.index_fill_(0, rows, 0)
+        last = h[torch.arange(n, device=self.device), lengths - 1].unsqueeze(1)  # [n, 1, C]
+        return ops.lm_head_logits(last, self.model.lm_head.weight)[:, 0]
+
+    def _queue_state(self):
+        """``key`` and ``end`` (allocated on first use): a row that serves no request keeps key 0
+        and an end position no row reaches."""
+        if self.key is None:
+            self.key = torch.zeros(self.B, device=self.device, dtype=torch.int64)
+            self.end = torch.full((self.B,), 2 ** 62, device=self.device, dtype=torch.int64)
+
+    @torch.no_grad()
+    def sample_admitted(self, rows, logits, temperature, top_k, stop_token=None, top_p=None, min_p=None):
+        """Draw the first token of the just admitted rows ``rows`` from their ``logits`` [n, V]
+        (what ``admit`` returned) into ``tok`` and ``gen[b, pos[b]]``, keyed and ended by ``key`` /
+        ``end`` like the queue's steps.  The sampler runs over the whole batch with every other
+        row masked as finished, so those rows' ``tok``, ``gen`` and ``done`` stay untouched."""
+        assert self.per_row
+        self._queue_state()
+        top_p, min_p = sampling_filters(top_p, min_p)
+        rows = self._row_index(rows)
+        mask = torch.ones(self.B, device=self.device, dtype=torch.int64)
+        mask.index_fill_(0, rows, 0)
+        if logits.stride(0) == 0:  # one distribution for every row (shared_prompt)
+            full = logits[:1].expand(self.B, -1)
+        else:
+            if self._admit_logits is None:
+                self._admit_logits = torch.zeros(self.B, logits.shape[1], device=self.device, dtype=torch.float32)
+            full = self._admit_logits
+            full.index_copy_(0, rows, logits.float())
+        ops.sample_topk_(full, temperature, top_k, self.salt, self.pos, self.tok, self.gen, salt_dev=self.salt_dev,
+                         stop_token=stop_token, done=mask, top_p=top_p, min_p=min_p, row_key=self.key, end=self.end)
+        self.done.index_copy_(0, rows, mask[rows])
+
+    @torch.no_grad()
+    def serve(self, prompts, budgets, temperature: float = 1.0, top_k: int | None = None,
+              stop_token: int | None = None, top_p: float | None = None, min_p: float | None = None):
+        """Serve a queue of requests through the B rows of this per_row decoder, refilling a row as
+        soon as its request is seen finished; returns every request's new tokens (1-D tensors, in
+        request order: ``budgets[i]`` of them, or fewer, ending with ``stop_token``).
+
+        ``prompts``: 1-D token tensors (a ``shared_prompt`` decoder: all the same one, encoded once
+        by ``prefill_shared``); request i must fit, ``len(prompts[i]) + budgets[i] <= block_size``
+        (a finished row is fed again at its last position, which must be a cache row), on a
+        shared decoder also ``budgets[i] <=`` the row caches' slots.  The rows are filled from the
+        head of the queue; then ``DONE_POLL`` steps at a time run as ``run(..., queue=True)``
+        (the captured graph replayed, no host sync inside a step), ``done`` and ``pos`` are read
+        back once, every finished row is harvested (``gen[b, L : pos[b] + 1]``) and the next
+        prompts go into all freed rows in one ``admit`` call.  Request i samples with ``key`` i, so
+        its draws depend on neither the row nor the schedule, and ends at position ``L_i + N_i -
+        1`` (``end``).  ``queue_stats``: ``steps`` run, ``admissions`` (admit calls) and requests
+        ``admitted``."""
+        assert self.per_row, "serve needs Decoder(..., per_row=True)"
+        if stop_token is not None and stop_token < 0:
+            stop_token = None
+        top_p, min_p = sampling_filters(top_p, min_p)
+        nreq = len(prompts)
+        budgets = [int(n) for n in budgets]
+        lens = [int(p.numel()) for p in prompts]
+        assert len(budgets) == nreq
+        for L, N in zip(lens, budgets):
+            assert L >= 1 and N >= 1 and L + N <= self.T, f"a request of {L} + {N} tokens does not fit {self.T}"
+            assert not self.shared or N <= self.R, f"{N} new tokens exceed the {self.R} slots of a row cache"
+        self._queue_state()
+        self.queue_stats = stats = {"steps": 0, "admissions": 0, "admitted": 0}
+        outs: list = [None] * nreq
+        if not nreq:
+            return outs
+        B = self.B
+        if self.shared:
+            self.prefill_shared(prompts[0])  # every row at the prompt's end: a valid place to idle
+        else:
+            self.pos.zero_()
+        self.done.fill_(1)  # no row serves a request yet; an idle row is a frozen one
+        owner = [None] * B  # the request a row serves
+        left = [0] * B      # an upper bound of the steps the row still needs
+        nxt = 0
+
+        def fill():
+            nonlocal nxt
+            free = [b for b in range(B) if owner[b] is None][:nreq - nxt]
+            if not free:
+                return
+            reqs = list(range(nxt, nxt + len(free)))
+            nxt += len(free)
+            rows = torch.tensor(free, dtype=torch.int64, device=self.device)
+            self.key.index_copy_(0, rows, torch.tensor(reqs, dtype=torch.int64, device=self.device))
+            self.end.index_copy_(0, rows, torch.tensor([lens[i] + budgets[i] - 1 for i in reqs], dtype=torch.int64,
+                                                       device=self.device))
+            if self.shared:
+                logits = self.admit(free)
+            else:
+                ls = [lens[i] for i in reqs]
+                idx = torch.zeros(len(free), max(ls), dtype=torch.int64, device=self.device)  # right-padded
+                for j, i in enumerate(reqs):
+                    idx[j, :ls[j]] = prompts[i]
+                logits = self.admit(free, idx, torch.tensor(ls, dtype=torch.int64, device=self.device))
+            self.sample_admitted(free, logits, temperature, top_k, stop_token, top_p, min_p)
+            for b, i in zip(free, reqs):
+                owner[b], left[b] = i, budgets[i] - 1
+            stats["admissions"] += 1
+            stats["admitted"] += len(free)
+
+        fill()
+        while True:
+            k = min(self.DONE_POLL, max(left[b] for b in range(B) if owner[b] is not None))
+            if k > 0:
+                self.run(k, temperature, top_k, stop_token, top_p, min_p, queue=True)
+                stats["steps"] += k
+            done, pos = torch.stack([self.done, self.pos]).tolist()  # the one host look per poll
+            for b in range(B):
+                i = owner[b]
+                if i is None:
+                    continue
+                if done[b]:
+                    outs[i] = self.gen[b, lens[i]:pos[b] + 1].clone()
+                    owner[b] = None
+                else:
+                    left[b] = lens[i] + budgets[i] - 1 - pos[b]
+            fill()
+            if all(o is None for o in owner):
+                return outs
+
     def _step_impl(self):
         return self._decode_layers()[:, 0]  # also advances pos
 
@@ -447,13 +632,20 @@ class Decoder:
         with torch.cuda.graph(self.graph):  # recorded, not executed: pos is unchanged
             self.logits = self._step_impl()
 
-    def sample_into(self, logits, temperature, top_k, stop_token=None, top_p=None, min_p=None):
+    def sample_into(self, logits, temperature, top_k, stop_token=None, top_p=None, min_p=None, queue=False):
         """Draw the next token of every row from ``logits`` [B, V] into ``tok`` and
         ``gen[:, pos]`` (device kernel on the GPU: ``ops.sample_topk_``).  per_row: row b
         writes ``gen[b, pos[b]]``; a finished row draws nothing, and a row that draws
         ``stop_token`` is finished from then on.  ``top_p`` / ``min_p``: nucleus and min-p
-        filters on top of the top-k (off: the top-k sampler's own launch)."""
+        filters on top of the top-k (off: the top-k sampler's own launch).  ``queue``: the
+        serving queue's form, every row keyed by ``key`` and finished at ``end``."""
         top_p, min_p = sampling_filters(top_p, min_p)
+        if queue:
+            assert self.per_row and self.key is not None, "the queue form needs a per_row decoder with key / end"
+            ops.sample_topk_(logits, temperature, top_k, self.salt, self.pos, self.tok, self.gen,
+                             salt_dev=self.salt_dev, stop_token=stop_token, done=self.done, top_p=top_p, min_p=min_p,
+                             row_key=self.key, end=self.end)
+            return
         if not self.per_row:
             assert stop_token is None, "a stop token needs Decoder(..., per_row=True)"
             ops.sample_topk_(logits, temperature, top_k, self.salt, self.pos, self.tok, self.gen,
@@ -466,35 +658,39 @@ class Decoder:
         """A fresh sampling stream for the next generate call (torch.manual_seed governs)."""
         self.salt_dev.fill_(int(torch.randint(0, 2 ** 62, (1,)).item()))
 
-    def _step_sample_impl(self, temperature, top_k, stop_token=None, top_p=None, min_p=None):
-        self.sample_into(self._step_impl(), temperature, top_k, stop_token, top_p, min_p)  # pos is now p + 1
+    def _step_sample_impl(self, temperature, top_k, stop_token=None, top_p=None, min_p=None, queue=False):
+        self.sample_into(self._step_impl(), temperature, top_k, stop_token, top_p, min_p, queue)  # pos is now p + 1
 
     DONE_POLL = 16  # run(): replays between two host looks at the finished flags
 
     @torch.no_grad()
     def run(self, n: int, temperature: float = 1.0, top_k: int | None = None, stop_token: int | None = None,
-            top_p: float | None = None, min_p: float | None = None):
+            top_p: float | None = None, min_p: float | None = None, queue: bool = False):
         """Decode n tokens starting from ``self.tok`` at ``self.pos``: each step feeds the
         token, samples the next one and feeds it back on the device (one graph replay per
         token on the GPU, no host round trip).  Results land in ``self.gen``.  With a
         ``stop_token`` (per_row decoders) the finished flags are read back every
-        ``DONE_POLL`` steps and the loop ends early once every row has finished."""
+        ``DONE_POLL`` steps and the loop ends early once every row has finished.  ``queue``
+        (``serve``): the sampler reads ``key`` and ``end``, a graph of its own (the key gains
+        ``"queue"``); without it the graphs and their keys are the ones there always were."""
         if stop_token is not None and stop_token < 0:
             stop_token = None
         assert stop_token is None or self.per_row, "a stop token needs Decoder(..., per_row=True)"
         top_p, min_p = sampling_filters(top_p, min_p)
         if not self.use_graph:
-            step = lambda: self._step_sample_impl(temperature, top_k, stop_token, top_p, min_p)  # noqa: E731
+            step = lambda: self._step_sample_impl(temperature, top_k, stop_token, top_p, min_p, queue)  # noqa: E731
         else:
             key = (float(temperature), top_k, stop_token) if self.per_row else (float(temperature), top_k)
             if top_p is not None or min_p is not None:  # without them: the keys (and graphs) of the top-k sampler
                 key += (top_p, min_p)
+            if queue:
+                key += ("queue",)
             g = self.sgraphs.get(key)
             if g is None:
-                self._warmup(lambda: self._step_sample_impl(temperature, top_k, stop_token, top_p, min_p))
+                self._warmup(lambda: self._step_sample_impl(temperature, top_k, stop_token, top_p, min_p, queue))
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g):
-                    self._step_sample_impl(temperature, top_k, stop_token, top_p, min_p)
+                    self._step_sample_impl(temperature, top_k, stop_token, top_p, min_p, queue)
                 self.sgraphs[key] = g
             step = g.replay
         ran = 0
@@ -686,13 +882,62 @@ def _generate_prefix(model, prompts, P, max_new_tokens, temperature, top_k, stop
             dec.release()
 
 
+def _generate_queue(model, prompts, budgets, batch_size, temperature, top_k, stop_token, use_graph, decoder, top_p,
+                    min_p, quantize, kv_quantize, shared_prompt) -> list[torch.Tensor]:
+    """``generate_batch`` with a ``batch_size`` or one budget per prompt: the prompts are a queue
+    served in order through min(batch_size, number of prompts) rows of one per_row decoder
+    (``Decoder.serve``).  ``decoder`` is reused if it is a per_row one of that many rows and of
+    the same quantize / kv_quantize / shared form (a shared one: with row caches that hold the
+    largest budget)."""
+    T = model.config.block_size
+    device = model.lm_head.weight.device
+    outs: list = [None] * len(prompts)
+    fit = [i for i, p in enumerate(prompts) if p.numel() + budgets[i] <= T]
+    for i, p in enumerate(prompts):
+        if i in fit:
+            continue
+        if shared_prompt:
+            raise ValueError(f"shared_prompt needs the KV-cache path: prompt ({p.numel()}) + new tokens "
+                             f"({budgets[i]}) exceed block_size {T}, and the recompute loop has nothing to share")
+        # a finished row idles at its last position, which must be a cache row: such a request goes alone
+        y = generate_cached(model, p.to(device)[None], budgets[i], temperature=temperature, top_k=top_k,
+                            use_graph=use_graph, top_p=top_p, min_p=min_p, quantize=quantize,
+                            kv_quantize=kv_quantize)[0]
+        outs[i] = torch.cat([y[:p.numel()], _cut_at_stop(y[p.numel():], stop_token)])
+    if not fit:
+        return outs
+    B = min(len(fit) if batch_size is None else batch_size, len(fit))
+    shared = shared_prompt and B >= 2  # a single row goes the ordinary way
+    need = max(budgets[i] for i in fit)
+    own = (decoder is None or decoder.B != B or not decoder.per_row or decoder.quantize != quantize
+           or decoder.kv_quantize != kv_quantize or decoder.shared != shared or (shared and decoder.R < need))
+    if not own:
+        dec = decoder
+    elif shared:
+        dec = Decoder(model, B, max_len=T, use_graph=use_graph, per_row=True, quantize=quantize, shared_prompt=True,
+                      max_new=need)
+    else:
+        dec = Decoder(model, B, max_len=T, use_graph=use_graph, per_row=True, quantize=quantize,
+                      kv_quantize=kv_quantize)
+    try:
+        dec.reseed()
+        news = dec.serve([prompts[i].to(device) for i in fit], [budgets[i] for i in fit], temperature, top_k,
+                         stop_token, top_p, min_p)
+        for i, new in zip(fit, news):
+            outs[i] = torch.cat([prompts[i].to(device), new])
+    finally:
+        if own:
+            dec.release()
+    return outs
+
+
 @torch.no_grad()
-def generate_batch(model, prompts, max_new_tokens: int, temperature: float = 1.0, top_k: int | None = None,
+def generate_batch(model, prompts, max_new_tokens, temperature: float = 1.0, top_k: int | None = None,
                    stop_token: int | None = None, use_graph: bool | None = None,
                    decoder: "Decoder | None" = None, top_p: float | None = None,
                    min_p: float | None = None, quantize: str | None = None,
                    kv_quantize: str | None = None, shared_prompt: bool = False,
-                   shared_prefix: bool = False) -> list[torch.Tensor]:
+                   shared_prefix: bool = False, batch_size: int | None = None) -> list[torch.Tensor]:
     """Generate for a list of prompts of unequal lengths as one batch.
 
     ``prompts``: 1-D token tensors, each of length >= 1.  Every result is its prompt followed
@@ -724,7 +969,34 @@ def generate_batch(model, prompts, max_new_tokens: int, temperature: float = 1.0
     max_new_tokens)``; ``decoder`` is reused only if it is such a one, and then keeps the
     prefix between calls).  One prompt, or no common prefix: the ordinary path.  ``kv_quantize``,
     ``shared_prompt=True`` at the same time and a row whose prompt + new tokens exceed
-    block_size raise ValueError."""
+    block_size raise ValueError.
+
+    ``batch_size`` (and / or ``max_new_tokens`` as one budget per prompt): the prompts are a
+    queue served in order through min(batch_size, number of prompts) rows; a row whose request
+    has finished (its own budget, or the stop token) is given the next prompt (``Decoder.serve``:
+    finished rows are looked for every ``DONE_POLL`` steps and all freed rows are admitted in one
+    prefill pass), so neither the decoder nor the time grows with the longest request of a
+    chunk.  Results come back in prompt order, in the form above.  Sampling is keyed by the
+    request, not the row.  An admission's prefill shape depends on the schedule, so on the GPU
+    its logits may differ from a chunked run's in the last bf16 bits; with ``shared_prompt=True``
+    (the same prompt everywhere, at least 2 rows; admission costs nothing, one prefill) nothing
+    does, and the results do not depend on the schedule.  A request must fit the cache with one
+    row to spare, prompt + budget <= block_size: one that does not goes alone through
+    ``generate_cached`` (``quantize`` / ``kv_quantize`` / ``shared_prompt``: ValueError).
+    ``shared_prefix=True``, ``batch_size < 1`` and a budget list of the wrong length or with an
+    entry < 1 raise ValueError.  With ``batch_size=None`` and an int budget nothing changes."""
+    queue = batch_size is not None or not isinstance(max_new_tokens, int)
+    if queue:
+        if batch_size is not None and (not isinstance(batch_size, int) or batch_size < 1):
+            raise ValueError(f"batch_size must be a positive int, got {batch_size!r}")
+        if shared_prefix:
+            raise ValueError("shared_prefix batches are not served as a queue: drop batch_size / per-prompt budgets")
+        if not isinstance(max_new_tokens, int):
+            budgets = [int(n) for n in max_new_tokens]
+            if len(budgets) != len(prompts):
+                raise ValueError(f"{len(budgets)} budgets for {len(prompts)} prompts")
+            if any(n < 1 for n in budgets):
+                raise ValueError(f"every budget must be at least 1, got {budgets}")
     if quantize not in (None, "int8"):
         raise ValueError(f"quantize must be None or 'int8', got {quantize!r}")
     if kv_quantize not in (None, "int8"):
@@ -744,8 +1016,13 @@ def generate_batch(model, prompts, max_new_tokens: int, temperature: float = 1.0
             raise ValueError("shared_prefix and shared_prompt are two forms of sharing: pass one of them")
         if kv_quantize:
             raise ValueError("shared_prefix keeps bf16 caches: it cannot be combined with kv_quantize")
-    if max_new_tokens <= 0:
+    if isinstance(max_new_tokens, int) and max_new_tokens <= 0:
         return list(prompts)
+    if queue:
+        if isinstance(max_new_tokens, int):
+            budgets = [max_new_tokens] * len(prompts)
+        return _generate_queue(model, prompts, budgets, batch_size, temperature, top_k, stop_token, use_graph,
+                               decoder, top_p, min_p, quantize, kv_quantize, shared_prompt)
     T = model.config.block_size
     device = model.lm_head.weight.device
     if shared_prefix and len(prompts) > 1:

@@ -23,7 +23,11 @@ for all rounds (``Decoder(shared_prompt=True)``); it refuses ``--prompts_file``,
 share only a prefix (``--prompts_file``: a system prompt followed by different questions): the
 longest common token prefix is encoded and cached once for the batch and for all rounds, and
 every row prefills only what it adds (``Decoder.prefill_suffixes``); it refuses
-``--kv_cache=False``, ``--kv_quantize`` and ``--shared_prompt``.
+``--kv_cache=False``, ``--kv_quantize`` and ``--shared_prompt``.  ``--serve_batch=N`` serves all
+requests (``num_samples`` rounds of the prompts file, or ``num_samples`` copies of ``start``) as one
+queue through N decoder rows, a finished row taking the next request (``Decoder.serve``), and prints
+the results in request order; it needs the KV-cache path, refuses ``--shared_prefix`` and composes
+with ``--shared_prompt``, ``--quantize``, ``--kv_quantize`` and ``--stop_token``.
 """
 
 from __future__ import annotations
@@ -62,7 +66,33 @@ SAMPLE_DEFAULTS = dict(
     kv_quantize="",  # "int8": int8 KV caches, one scale per cache row (Decoder(kv_quantize="int8")); "": off
     shared_prompt=False,  # sample_batch > 1: encode and cache the prompt once for the batch (Decoder(shared_prompt=True))
     shared_prefix=False,  # prompts_file / sample_batch > 1: encode and cache the prompts' common prefix once for the batch
+    serve_batch=0,  # N > 0: all requests as one queue through N decoder rows, finished rows refilled (Decoder.serve); 0: off
 )
+
+
+def _serve_queue(model, c, encode, decode, start, device):
+    """serve_batch: every request (num_samples rounds of the prompts file, or num_samples copies
+    of start) through one queue of ``serve_batch`` rows (``GPT.generate_batch(batch_size=)``)."""
+    stop = c["stop_token"] if c["stop_token"] >= 0 else None
+    if c["prompts_file"]:
+        with open(c["prompts_file"], "r", encoding="utf-8") as f:
+            texts = [ln.rstrip("\n") for ln in f if ln.strip()] * c["num_samples"]
+    else:
+        texts = [start] * c["num_samples"]
+    prompts = [torch.tensor(encode(t), dtype=torch.long, device=device) for t in texts]
+    ys = model.generate_batch(prompts, c["max_new_tokens"], temperature=c["temperature"], top_k=c["top_k"],
+                              stop_token=stop, top_p=c["top_p"], min_p=c["min_p"], quantize=c["quantize"] or None,
+                              kv_quantize=c["kv_quantize"] or None, shared_prompt=bool(c["shared_prompt"]),
+                              batch_size=c["serve_batch"])
+    outs = []
+    for p, y in zip(prompts, ys):
+        new = y[p.numel():].tolist()
+        if stop is not None and stop in new:
+            new = new[:new.index(stop)]
+        outs.append(decode(p.tolist() + new))
+        print(outs[-1])
+        print("---------------")
+    return outs
 
 
 def _generate_batches(model, c, encode, decode, start, device):
@@ -173,6 +203,15 @@ def main(argv=None):
                              "cache to share")
         if c["kv_quantize"]:
             raise ValueError("--shared_prefix keeps bf16 caches: it cannot be combined with --kv_quantize")
+    if c["serve_batch"] < 0:
+        raise ValueError(f"serve_batch must be >= 0, got {c['serve_batch']}")
+    if c["serve_batch"]:
+        if not c["kv_cache"]:
+            raise ValueError("--serve_batch refills the rows of a KV-cache decoder: it cannot be combined with "
+                             "--kv_cache=False")
+        if c["shared_prefix"]:
+            raise ValueError("--serve_batch cannot admit suffixes against a shared prefix yet: it cannot be combined "
+                             "with --shared_prefix")
     quantize = c["quantize"] or None
     kv_quantize = c["kv_quantize"] or None
     torch.manual_seed(c["seed"])
@@ -196,6 +235,9 @@ def main(argv=None):
     if start.startswith("FILE:"):
         with open(start[5:], "r", encoding="utf-8") as f:
             start = f.read()
+    if c["serve_batch"]:
+        with torch.no_grad():
+            return _serve_queue(model, c, encode, decode, start, device)
     if c["sample_batch"] > 1 or c["prompts_file"] or c["stop_token"] >= 0:
         with torch.no_grad():
             return _generate_batches(model, c, encode, decode, start, device)

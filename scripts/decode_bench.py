@@ -35,6 +35,15 @@ unequal random suffixes of 1 .. N tokens, on the unshared per-row decoder (right
 ``prefill(idx, lengths)``) and on the shared-prefix one (``prefill_shared`` +
 ``prefill_suffixes``, ``max_new = N + --new + 1``); both lines carry ``ttft_ms``, and the shared
 one ``ttft_cached_ms``: the same with the prefix already in the decoder, as in every later round.
+``--queue R --budgets LO:HI`` replaces the mode list by ``queue_chunks`` and ``queue_serve``
+(interleaved, ``--repeat`` times; with ``--shared_prompt``: ``queue_chunks_shared`` and
+``queue_serve_shared``, every request the same prompt): R requests of ``--prompt`` tokens whose
+budgets are uniform in LO .. HI from a fixed seed, served on reused, warmed decoders of B rows,
+first the way a caller had to (chunks of B through ``generate_batch``, each running to its longest
+budget), then as one queue (``generate_batch(batch_size=B)``: ``Decoder.serve``).  Each line holds
+the useful tokens/s (sum of budgets / wall time), the steps, the admissions, the share of the
+stream's time between the start of an ``admit`` and the end of the first-token draw that follows
+it (device events, no extra syncs), and the calibration GEMM.
 """
 
 import argparse
@@ -168,6 +177,59 @@ def run_samples(model, prompt, n, new, batched, shared=False):
     return dt
 
 
+def queue_budgets(R, lo, hi):
+    """R budgets uniform in lo .. hi, from a fixed seed."""
+    g = torch.Generator().manual_seed(1234)
+    return torch.randint(lo, hi + 1, (R,), generator=g).tolist()
+
+
+def run_queue(model, prompts, budgets, B, serve, shared):
+    """The requests in chunks of B, each to its longest budget, or (serve) as one queue through B
+    rows, on a decoder built and warmed (graphs captured) outside the timed window.  Returns
+    (seconds, steps, admissions, seconds between the start of an admission and the end of its
+    first-token draw)."""
+    need = max(budgets)
+    dec = (Decoder(model, B, use_graph=True, per_row=True, shared_prompt=True, max_new=need) if shared
+           else Decoder(model, B, use_graph=True, per_row=True))
+    kw = dict(temperature=0.8, **SMP, decoder=dec, shared_prompt=shared)
+    evs = []
+    admit, first = dec.admit, dec.sample_admitted
+
+    def timed_admit(*args, **kwargs):
+        e = torch.cuda.Event(enable_timing=True)
+        e.record()
+        evs.append([e, None])
+        return admit(*args, **kwargs)
+
+    def timed_first(*args, **kwargs):
+        first(*args, **kwargs)
+        evs[-1][1] = torch.cuda.Event(enable_timing=True)
+        evs[-1][1].record()
+
+    dec.admit, dec.sample_admitted = timed_admit, timed_first
+    chunks = [range(i, min(i + B, len(prompts))) for i in range(0, len(prompts), B)]
+
+    def go(ps, bs):
+        if serve:
+            model.generate_batch(ps, bs, batch_size=B, **kw)
+            return dec.queue_stats["steps"], dec.queue_stats["admissions"]
+        mine = [c for c in chunks if c[-1] < len(ps)]
+        for ch in mine:
+            model.generate_batch([ps[i] for i in ch], max(bs[i] for i in ch), **kw)
+        return sum(max(bs[i] for i in ch) - 1 for ch in mine), len(mine)
+
+    go(prompts[:2 * B], [3] * (2 * B))  # warm-up: tuner, allocator, graph capture
+    del evs[:]
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    steps, admissions = go(prompts, budgets)
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    adm = sum(a.elapsed_time(b) for a, b in evs) * 1e-3
+    dec.release()
+    return dt, steps, admissions, adm
+
+
 def run_recompute(model, idx, new):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -200,6 +262,10 @@ def main():
                     help="time prompts of one --prompt-token prefix + unequal suffixes (--suffix): the unshared "
                          "per-row decoder (prefix_rows) against the shared-prefix one (prefix_shared), ttft_ms on both")
     ap.add_argument("--suffix", type=int, default=32, help="--shared_prefix: the longest suffix (1 .. N over the batch)")
+    ap.add_argument("--queue", type=int, default=0,
+                    help="time R requests of unequal budgets (--budgets) in chunks of B (queue_chunks) against one "
+                         "queue through B refilled rows (queue_serve); with --shared_prompt their _shared twins")
+    ap.add_argument("--budgets", default="16:256", help="--queue: new tokens per request, uniform in LO:HI")
     ap.add_argument("--memory", action="store_true", help="add each run's peak allocated bytes (decoder_peak_mb)")
     ap.add_argument("--top_k", type=int, default=200, help="0: no top-k")
     ap.add_argument("--top_p", type=float, default=1.0, help="nucleus mass; 1.0: off")
@@ -208,9 +274,11 @@ def main():
     SMP.update(top_k=a.top_k, top_p=a.top_p if a.top_p < 1.0 else None, min_p=a.min_p if a.min_p > 0.0 else None)
     extra = {k: v for k, v in (("top_k", a.top_k), ("top_p", a.top_p), ("min_p", a.min_p))
              if v != ap.get_default(k)}  # the default run prints what it always did
-    if a.calibrate:
+    cal = None
+    if a.calibrate or a.queue:
         from nanosandbox_amd.utils.boxcal import calibration_gemm
-        print(json.dumps({"calibration_gemm": calibration_gemm()}), flush=True)
+        cal = calibration_gemm()
+        print(json.dumps({"calibration_gemm": cal}), flush=True)
     modes = a.modes.split(",") + (["ragged"] if a.ragged else [])
     modes = [m for m in modes if m]
     if a.quantize:  # each int8 twin right after its bf16 mode
@@ -222,9 +290,16 @@ def main():
     if a.shared_prefix:
         modes = ["prefix_rows", "prefix_shared"]
     block_size = GPTConfig().block_size
+    if a.queue:
+        lo, hi = (int(x) for x in a.budgets.split(":"))
+        if a.queue < 1 or not 1 <= lo <= hi or a.prompt + hi > block_size:
+            ap.error(f"--queue needs 1 <= LO <= HI and --prompt + HI <= block_size ({block_size})")
+        sfx = "_shared" if a.shared_prompt else ""
+        modes = ["queue_chunks" + sfx, "queue_serve" + sfx]
+        budgets = queue_budgets(a.queue, lo, hi)
     if a.shared_prefix and (a.suffix < 1 or a.prompt + a.suffix + a.new >= block_size):
         ap.error(f"--prompt + --suffix + --new must stay below block_size ({block_size})")
-    if any(m != "recompute" for m in modes) and a.prompt + a.new >= block_size:
+    if not a.queue and any(m != "recompute" for m in modes) and a.prompt + a.new >= block_size:
         # a cached run feeds positions prompt .. prompt + new (one capture step, then --new timed
         # ones); the position table and the caches end at block_size - 1
         ap.error(f"--prompt + --new must stay below block_size ({block_size}): the last fed position is their sum")
@@ -237,7 +312,17 @@ def main():
         for B in [int(b) for b in a.batches.split(",")]:
             idx = torch.randint(0, 50257, (B, a.prompt), device="cuda")
             with torch.no_grad():
-                for mode in modes:
+                for mode in modes if a.queue else []:
+                    shared = mode.endswith("_shared")
+                    reqs = torch.randint(0, 50257, (a.queue, a.prompt), device="cuda")
+                    prompts = [reqs[0] if shared else r for r in reqs]
+                    dt, steps, adm, adm_s = run_queue(model, prompts, budgets, B, "serve" in mode, shared)
+                    print(json.dumps({"model": name, "batch": B, "mode": mode, "prompt": a.prompt, "requests": a.queue,
+                                      "budgets": a.budgets, "new_tokens": sum(budgets),
+                                      "tokens_per_s": round(sum(budgets) / dt, 1), "seconds": round(dt, 3),
+                                      "steps": steps, "admissions": adm, "admit_share": round(adm_s / dt, 4),
+                                      "calibration_tflops": cal.get("tflops"), **extra}), flush=True)
+                for mode in [] if a.queue else modes:
                     base, *sfx = mode.split("_")  # graph_int8_kv8 -> graph, int8 weights, int8 caches
                     qz = "int8" if "int8" in sfx else None
                     kvq = "int8" if "kv8" in sfx else None
