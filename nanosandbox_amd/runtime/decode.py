@@ -90,21 +90,37 @@ context there, which a cache cannot do without re-encoding).
 
 from __future__ import annotations
 
+import contextlib
+
 import torch
 
 from .. import ops
+
+
+def _check_mode(quantize, kv_quantize, shared_prompt=False, shared_prefix=False):
+    """The mode combinations a decoder and the front ends accept: ValueError for any other."""
+    if quantize not in (None, "int8"):
+        raise ValueError(f"quantize must be None or 'int8', got {quantize!r}")
+    if kv_quantize not in (None, "int8"):
+        raise ValueError(f"kv_quantize must be None or 'int8', got {kv_quantize!r}")
+    if shared_prompt and kv_quantize:
+        raise ValueError("shared_prompt keeps bf16 caches: it cannot be combined with kv_quantize")
+    if shared_prefix and shared_prompt:
+        raise ValueError("shared_prefix and shared_prompt are two forms of sharing: pass one of them")
+    if shared_prefix and kv_quantize:
+        raise ValueError("shared_prefix keeps bf16 caches: it cannot be combined with kv_quantize")
+
+
+def _stop(stop_token):
+    """A stop token < 0 means none."""
+    return None if stop_token is None or stop_token < 0 else stop_token
 
 
 class Decoder:
     def __init__(self, model, batch_size: int, max_len: int | None = None, use_graph: bool | None = None,
                  per_row: bool = False, quantize: str | None = None, kv_quantize: str | None = None,
                  shared_prompt: bool = False, max_new: int | None = None):
-        if quantize not in (None, "int8"):
-            raise ValueError(f"quantize must be None or 'int8', got {quantize!r}")
-        if kv_quantize not in (None, "int8"):
-            raise ValueError(f"kv_quantize must be None or 'int8', got {kv_quantize!r}")
-        if shared_prompt and kv_quantize:
-            raise ValueError("shared_prompt keeps bf16 caches: it cannot be combined with kv_quantize")
+        _check_mode(quantize, kv_quantize, shared_prompt)
         if shared_prompt and batch_size < 2:
             raise ValueError(f"shared_prompt needs at least 2 rows to share a prompt, got batch size {batch_size}")
         if max_new is not None and not shared_prompt:
@@ -115,23 +131,25 @@ class Decoder:
         self.kv_quantize = kv_quantize
         self.shared = bool(shared_prompt)
         cfg = model.config
-        if shared_prompt and model.lm_head.weight.is_cuda and not self.graph_capable(model):
-            # the shared-prompt attention kernel is a head_dim-64 bf16 one; no silent torch step instead
-            raise ValueError("shared_prompt needs the fused decode kernels on the GPU: head_dim 64, "
-                             "bfloat16 compute and a vocabulary of at most 53248")
-        if kv_quantize and model.lm_head.weight.is_cuda and not self.graph_capable(model):
-            # the int8-cache kernels are the head_dim-64 bf16 ones; no silent torch step instead
-            raise ValueError("kv_quantize='int8' needs the fused decode kernels on the GPU: head_dim 64, "
-                             "bfloat16 compute and a vocabulary of at most 53248")
-        if quantize and model.lm_head.weight.is_cuda:
+        on_gpu = model.lm_head.weight.is_cuda
+
+        def needs_fused(mode):
+            # the shared-prompt attention kernel, the int8-cache kernels and the int8-weight kernels are
+            # head_dim-64 bf16 ones, and there is no int8 form of the fallback ops; no silent torch step instead
+            if on_gpu and not self.graph_capable(model):
+                raise ValueError(f"{mode} needs the fused decode kernels on the GPU: head_dim 64, "
+                                 "bfloat16 compute and a vocabulary of at most 53248")
+        if shared_prompt:
+            needs_fused("shared_prompt")
+        if kv_quantize:
+            needs_fused("kv_quantize='int8'")
+        if quantize:
             # the int8 kernels are the single-row and skinny ones; there is no int8 form of the
-            # larger-batch GEMMs or of the fallback ops, and no silent bf16 step instead
-            if batch_size > ops.functional.SKINNY_MAX_ROWS:
+            # larger-batch GEMMs, and no silent bf16 step instead
+            if on_gpu and batch_size > ops.functional.SKINNY_MAX_ROWS:
                 raise ValueError(f"quantize='int8' decodes at most {ops.functional.SKINNY_MAX_ROWS} rows on the GPU "
                                  f"(the skinny int8 kernels), got batch size {batch_size}")
-            if not self.graph_capable(model):
-                raise ValueError("quantize='int8' needs the fused decode kernels on the GPU: head_dim 64, "
-                                 "bfloat16 compute and a vocabulary of at most 53248")
+            needs_fused("quantize='int8'")
         self.B = batch_size
         self.T = max_len or cfg.block_size
         assert self.T <= cfg.block_size, "caches cannot exceed the position-embedding table"
@@ -213,6 +231,14 @@ class Decoder:
         cfg = model.config
         return (cfg.n_embd // cfg.n_head == 64 and model.compute_dtype == torch.bfloat16
                 and cfg.vocab_size <= 53248)
+
+    def fits(self, batch_size, per_row=False, quantize=None, kv_quantize=None, shared_prompt=False,
+             max_new=None) -> bool:
+        """Whether a call that needs ``Decoder(model, batch_size, per_row=..., ...)`` can run on this
+        one: the same rows and form, and (shared) row caches of at least ``max_new`` slots."""
+        return (self.B == batch_size and self.per_row == bool(per_row) and self.quantize == quantize
+                and self.kv_quantize == kv_quantize and self.shared == bool(shared_prompt)
+                and (not self.shared or self.R >= (max_new or self.T)))
 
     def _quantize_weights(self):
         """int8 mode: quantize every linear weight and the tied lm_head / wte table, and point
@@ -331,6 +357,45 @@ class Decoder:
             ops.advance_pos_(self.pos, self.done)  # unfinished rows move on, finished rows stay
         return logits  # pos has advanced (by the head kernel itself on the fused path)
 
+    def _encode(self, idx, first=0, rows=None, kc=None, vc=None):
+        """``idx`` [n, S], its tokens at positions first .. first + S - 1, through the embedding and
+        ``_prefill_layers`` (``first`` > 0: the suffixes of the cached prefix of that length) -> ln_f(x)."""
+        tr = self.model.transformer
+        wpe = tr.wpe.weight
+        if first:
+            wpe = ops.compute_weight(wpe, self.dtype)[first:first + idx.shape[1]]
+        x = ops.embedding(idx, tr.wte.weight, wpe, 0.0, False, dtype=self.rdtype, cdtype=self.dtype)
+        return self._prefill_layers(x, kc, vc, prefix=first or None, rows=rows)
+
+    def _prefill(self, idx, first=0, lengths=None, rows=None):
+        """What ``prefill``, ``prefill_suffixes`` and ``admit`` share: ``_encode``, then the rows'
+        positions become ``first + lengths`` (no ``lengths``: first + S) and their finished flags 0
+        (``rows``: those cache rows only, else all), and the logits of every row's last token
+        [n, V] are returned."""
+        n, S = idx.shape
+        if lengths is not None:
+            assert self.per_row, "unequal prompt lengths need Decoder(..., per_row=True)"
+            lengths = torch.as_tensor(lengths, dtype=torch.int64).to(self.device).view(n)
+            assert int(lengths.min()) >= 1 and int(lengths.max()) <= S
+        h = self._encode(idx, first, rows)
+        if first:
+            self.plen.fill_(first)
+        if rows is not None:
+            self.pos.index_copy_(0, rows, lengths)
+            self.done.index_fill_(0, rows, 0)
+        else:
+            if self.per_row:
+                self.done.zero_()
+            if lengths is None:
+                self.pos.fill_(first + S)
+            else:
+                self.pos.copy_(lengths + first if first else lengths)
+        if lengths is None:
+            last = h[:, [-1], :]
+        else:
+            last = h[torch.arange(n, device=self.device), lengths - 1].unsqueeze(1)  # [n, 1, C]
+        return ops.lm_head_logits(last, self.model.lm_head.weight)[:, 0]
+
     @torch.no_grad()
     def prefill(self, idx: torch.Tensor, lengths: torch.Tensor | None = None) -> torch.Tensor:
         """Encode the prompt [B, T0]; returns the last position's logits [B, V] (fp32).
@@ -344,21 +409,7 @@ class Decoder:
         B, T0 = idx.shape
         assert not self.shared, "a shared_prompt decoder encodes its one prompt with prefill_shared"
         assert B == self.B and 1 <= T0 <= self.T
-        tr = self.model.transformer
-        if lengths is not None:
-            assert self.per_row, "unequal prompt lengths need Decoder(..., per_row=True)"
-            lengths = torch.as_tensor(lengths, dtype=torch.int64).to(self.device).view(B)
-            assert int(lengths.min()) >= 1 and int(lengths.max()) <= T0
-        x = ops.embedding(idx, tr.wte.weight, tr.wpe.weight, 0.0, False, dtype=self.rdtype, cdtype=self.dtype)
-        h = self._prefill_layers(x)
-        if self.per_row:
-            self.done.zero_()
-        if lengths is None:
-            self.pos.fill_(T0)
-            return ops.lm_head_logits(h[:, [-1], :], self.model.lm_head.weight)[:, 0]
-        self.pos.copy_(lengths)
-        last = h[torch.arange(B, device=self.device), lengths - 1].unsqueeze(1)  # [B, 1, C]
-        return ops.lm_head_logits(last, self.model.lm_head.weight)[:, 0]
+        return self._prefill(idx, 0, lengths)
 
     @torch.no_grad()
     def prefill_shared(self, idx: torch.Tensor) -> torch.Tensor:
@@ -376,9 +427,7 @@ class Decoder:
         T0 = idx.shape[1]
         assert 1 <= T0 <= self.T
         if self._prompt is None or self._prompt.shape != idx.shape or not torch.equal(self._prompt, idx):
-            tr = self.model.transformer
-            x = ops.embedding(idx, tr.wte.weight, tr.wpe.weight, 0.0, False, dtype=self.rdtype, cdtype=self.dtype)
-            h = self._prefill_layers(x, self.pkc, self.pvc)
+            h = self._encode(idx, kc=self.pkc, vc=self.pvc)
             self._prompt_logits = ops.lm_head_logits(h[:, [-1], :], self.model.lm_head.weight)[:, 0].float()
             self._prompt = idx.clone()
             self.prefills += 1
@@ -405,24 +454,7 @@ class Decoder:
         B, S = idx.shape
         P = self._prompt.shape[1]
         assert B == self.B and 1 <= S <= self.R and P + S <= self.T
-        idx = idx.to(self.device)
-        if lengths is not None:
-            assert self.per_row, "unequal suffix lengths need Decoder(..., per_row=True)"
-            lengths = torch.as_tensor(lengths, dtype=torch.int64).to(self.device).view(B)
-            assert int(lengths.min()) >= 1 and int(lengths.max()) <= S
-        tr = self.model.transformer
-        wpe = ops.compute_weight(tr.wpe.weight, self.dtype)[P:P + S]  # positions P .. P + S - 1
-        x = ops.embedding(idx, tr.wte.weight, wpe, 0.0, False, dtype=self.rdtype, cdtype=self.dtype)
-        h = self._prefill_layers(x, prefix=P)
-        self.plen.fill_(P)
-        if self.per_row:
-            self.done.zero_()
-        if lengths is None:
-            self.pos.fill_(P + S)
-            return ops.lm_head_logits(h[:, [-1], :], self.model.lm_head.weight)[:, 0]
-        self.pos.copy_(lengths + P)
-        last = h[torch.arange(B, device=self.device), lengths - 1].unsqueeze(1)  # [B, 1, C]
-        return ops.lm_head_logits(last, self.model.lm_head.weight)[:, 0]
+        return self._prefill(idx.to(self.device), P, lengths)
 
     def _row_index(self, rows) -> torch.Tensor:
         """``rows`` (a list or tensor of distinct cache-row indices < B) as int64 [n] on the device."""
@@ -456,20 +488,9 @@ class Decoder:
             self.done.index_fill_(0, rows, 0)
             return self._prompt_logits.expand(n, -1)
         assert idx is not None and idx.dim() == 2 and idx.shape[0] == n and 1 <= idx.shape[1] <= self.T
-        S = idx.shape[1]
-        idx = idx.to(self.device)
         if lengths is None:
-            lengths = torch.full((n,), S, dtype=torch.int64, device=self.device)
-        else:
-            lengths = torch.as_tensor(lengths, dtype=torch.int64).to(self.device).view(n)
-            assert int(lengths.min()) >= 1 and int(lengths.max()) <= S
-        tr = self.model.transformer
-        x = ops.embedding(idx, tr.wte.weight, tr.wpe.weight, 0.0, False, dtype=self.rdtype, cdtype=self.dtype)
-        h = self._prefill_layers(x, rows=rows)
-        self.pos.index_copy_(0, rows, lengths)
-        self.done.index_fill_(0, rows, 0)
-        last = h[torch.arange(n, device=self.device), lengths - 1].unsqueeze(1)  # [n, 1, C]
-        return ops.lm_head_logits(last, self.model.lm_head.weight)[:, 0]
+            lengths = torch.full((n,), idx.shape[1], dtype=torch.int64, device=self.device)
+        return self._prefill(idx.to(self.device), 0, lengths, rows)
 
     def _queue_state(self):
         """``key`` and ``end`` (allocated on first use): a row that serves no request keeps key 0
@@ -520,8 +541,7 @@ class Decoder:
         1`` (``end``).  ``queue_stats``: ``steps`` run, ``admissions`` (admit calls) and requests
         ``admitted``."""
         assert self.per_row, "serve needs Decoder(..., per_row=True)"
-        if stop_token is not None and stop_token < 0:
-            stop_token = None
+        stop_token = _stop(stop_token)
         top_p, min_p = sampling_filters(top_p, min_p)
         nreq = len(prompts)
         budgets = [int(n) for n in budgets]
@@ -559,11 +579,7 @@ class Decoder:
             if self.shared:
                 logits = self.admit(free)
             else:
-                ls = [lens[i] for i in reqs]
-                idx = torch.zeros(len(free), max(ls), dtype=torch.int64, device=self.device)  # right-padded
-                for j, i in enumerate(reqs):
-                    idx[j, :ls[j]] = prompts[i]
-                logits = self.admit(free, idx, torch.tensor(ls, dtype=torch.int64, device=self.device))
+                logits = self.admit(free, *_right_pad([prompts[i] for i in reqs], self.device))
             self.sample_admitted(free, logits, temperature, top_k, stop_token, top_p, min_p)
             for b, i in zip(free, reqs):
                 owner[b], left[b] = i, budgets[i] - 1
@@ -601,13 +617,14 @@ class Decoder:
         if not self.use_graph:
             return self._step_impl()
         if self.graph is None:
-            self._capture()
+            self.graph, self.logits = self._capture(self._step_impl)
         self.graph.replay()
         self.replays += 1
         return self.logits
 
-    def _warmup(self, fn):
-        # outside any graph (lazy library init, GEMM tuner decisions for M = B), at the
+    def _capture(self, fn):
+        """Warm ``fn`` (a step, with or without sampling) up and record it -> (graph, what fn returned)."""
+        # the warm-up: outside any graph (lazy library init, GEMM tuner decisions for M = B), at the
         # current position without advancing it or changing the fed token: the captured
         # step rewrites the same cache rows when it runs
         tok = self.tok.clone()
@@ -625,12 +642,10 @@ class Decoder:
                     self.pos.sub_(1)
                 self.tok.copy_(tok)
         torch.cuda.current_stream().wait_stream(side)
-
-    def _capture(self):
-        self._warmup(self._step_impl)
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):  # recorded, not executed: pos is unchanged
-            self.logits = self._step_impl()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):  # recorded, not executed: pos is unchanged
+            out = fn()
+        return graph, out
 
     def sample_into(self, logits, temperature, top_k, stop_token=None, top_p=None, min_p=None, queue=False):
         """Draw the next token of every row from ``logits`` [B, V] into ``tok`` and
@@ -642,17 +657,13 @@ class Decoder:
         top_p, min_p = sampling_filters(top_p, min_p)
         if queue:
             assert self.per_row and self.key is not None, "the queue form needs a per_row decoder with key / end"
-            ops.sample_topk_(logits, temperature, top_k, self.salt, self.pos, self.tok, self.gen,
-                             salt_dev=self.salt_dev, stop_token=stop_token, done=self.done, top_p=top_p, min_p=min_p,
-                             row_key=self.key, end=self.end)
-            return
         if not self.per_row:
             assert stop_token is None, "a stop token needs Decoder(..., per_row=True)"
-            ops.sample_topk_(logits, temperature, top_k, self.salt, self.pos, self.tok, self.gen,
-                             salt_dev=self.salt_dev, top_p=top_p, min_p=min_p)
-            return
+        # ``done`` is None without per_row, ``key`` / ``end`` are passed by the queue only: the sampler
+        # picks its entry point from what is there
         ops.sample_topk_(logits, temperature, top_k, self.salt, self.pos, self.tok, self.gen, salt_dev=self.salt_dev,
-                         stop_token=stop_token, done=self.done, top_p=top_p, min_p=min_p)
+                         stop_token=stop_token, done=self.done, top_p=top_p, min_p=min_p,
+                         row_key=self.key if queue else None, end=self.end if queue else None)
 
     def reseed(self):
         """A fresh sampling stream for the next generate call (torch.manual_seed governs)."""
@@ -673,26 +684,19 @@ class Decoder:
         ``DONE_POLL`` steps and the loop ends early once every row has finished.  ``queue``
         (``serve``): the sampler reads ``key`` and ``end``, a graph of its own (the key gains
         ``"queue"``); without it the graphs and their keys are the ones there always were."""
-        if stop_token is not None and stop_token < 0:
-            stop_token = None
+        stop_token = _stop(stop_token)
         assert stop_token is None or self.per_row, "a stop token needs Decoder(..., per_row=True)"
         top_p, min_p = sampling_filters(top_p, min_p)
-        if not self.use_graph:
-            step = lambda: self._step_sample_impl(temperature, top_k, stop_token, top_p, min_p, queue)  # noqa: E731
-        else:
+        step = lambda: self._step_sample_impl(temperature, top_k, stop_token, top_p, min_p, queue)  # noqa: E731
+        if self.use_graph:
             key = (float(temperature), top_k, stop_token) if self.per_row else (float(temperature), top_k)
             if top_p is not None or min_p is not None:  # without them: the keys (and graphs) of the top-k sampler
                 key += (top_p, min_p)
             if queue:
                 key += ("queue",)
-            g = self.sgraphs.get(key)
-            if g is None:
-                self._warmup(lambda: self._step_sample_impl(temperature, top_k, stop_token, top_p, min_p, queue))
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    self._step_sample_impl(temperature, top_k, stop_token, top_p, min_p, queue)
-                self.sgraphs[key] = g
-            step = g.replay
+            if key not in self.sgraphs:
+                self.sgraphs[key], _ = self._capture(step)
+            step = self.sgraphs[key].replay
         ran = 0
         while ran < n:
             if stop_token is not None and ran and ran % self.DONE_POLL == 0 and bool(self.done.all()):
@@ -736,6 +740,70 @@ def sample_next(logits: torch.Tensor, temperature: float = 1.0, top_k: int | Non
     return torch.multinomial(probs, num_samples=1, generator=generator)
 
 
+def _mode(B, per_row=False, quantize=None, kv_quantize=None, slots=None) -> dict:
+    """The decoder a call needs, as ``Decoder``'s arguments (and ``Decoder.fits``'s): B rows, per_row
+    or not, the two quantizations and ``slots``, the row-cache slots of a shared_prompt decoder
+    (None: an unshared one)."""
+    return dict(batch_size=B, per_row=per_row, quantize=quantize, kv_quantize=kv_quantize,
+                shared_prompt=slots is not None, max_new=slots)
+
+
+def _build(model, mode, use_graph=None):
+    return Decoder(model, max_len=model.config.block_size, use_graph=use_graph, **mode)
+
+
+@contextlib.contextmanager
+def _borrow(model, mode, decoder, use_graph):
+    """The decoder a call of ``mode`` runs on, reseeded: the caller's ``decoder`` if it fits (its
+    weight shadows, captured graphs and cached prompt survive; the caller releases it), otherwise
+    a temporary one, released on exit."""
+    own = decoder is None or not decoder.fits(**mode)
+    dec = _build(model, mode, use_graph) if own else decoder
+    try:
+        dec.reseed()  # every call draws its own samples, also on a reused decoder / graph
+        yield dec
+    finally:
+        if own:
+            dec.release()
+
+
+def _nothing_to_share(sharing, L, N, T):
+    return ValueError(f"{sharing} needs the KV-cache path: prompt ({L}) + new tokens ({N}) exceed block_size {T}, "
+                      "and the recompute loop has nothing to share")
+
+
+def _cached_mode(model, idx, max_new_tokens, quantize, kv_quantize, shared_prompt):
+    """The mode of the decoder ``generate_cached`` runs this call on (None: the recompute loop)."""
+    B, T0 = idx.shape
+    T = model.config.block_size
+    _check_mode(quantize, kv_quantize, shared_prompt)
+    if shared_prompt:
+        if not bool((idx == idx[:1]).all()):
+            raise ValueError("shared_prompt needs every row of idx to be the same prompt")
+        if B > 1:  # a single row goes the ordinary way
+            if T0 + max_new_tokens > T:
+                raise _nothing_to_share("shared_prompt", T0, max_new_tokens, T)
+            return _mode(B, False, quantize, slots=max_new_tokens)
+    if T0 + max_new_tokens - 1 > T:
+        if quantize:
+            raise ValueError("quantize needs the KV-cache path: prompt + new tokens exceed block_size, and the "
+                             "recompute loop runs the unquantized model")
+        if kv_quantize:
+            raise ValueError("kv_quantize needs the KV-cache path: prompt + new tokens exceed block_size, and the "
+                             "recompute loop has no cache to quantize")
+        return None
+    return _mode(B, False, quantize, kv_quantize)
+
+
+def cached_decoder(model, idx, max_new_tokens, use_graph=None, quantize=None, kv_quantize=None, shared_prompt=False):
+    """The Decoder this ``generate_cached`` call would build, for a caller that keeps it across
+    calls (``decoder=``) and releases it.  A call that runs on none (no new tokens, or the
+    recompute loop) gets the ordinary one all the same, as ``sample.py`` always has: building it
+    draws from torch's generator, and a seeded run keeps its tokens."""
+    mode = max_new_tokens > 0 and _cached_mode(model, idx, max_new_tokens, quantize, kv_quantize, shared_prompt)
+    return _build(model, mode or _mode(idx.shape[0], False, quantize, kv_quantize), use_graph)
+
+
 @torch.no_grad()
 def generate_cached(model, idx: torch.Tensor, max_new_tokens: int, temperature: float = 1.0,
                     top_k: int | None = None, use_graph: bool | None = None,
@@ -754,80 +822,41 @@ def generate_cached(model, idx: torch.Tensor, max_new_tokens: int, temperature: 
     ``kv_quantize="int8"``: int8 KV caches (``Decoder(..., kv_quantize="int8")``); the
     recompute loop has no cache, so the same case raises ValueError as well.
 
-    ``decoder``: a Decoder to reuse across calls (same batch size): its weight shadows and
-    captured graphs survive, so ``sample.py``'s num_samples loop captures once.  The caller
-    releases it; without one, a temporary decoder is built and released here."""
-    B, T0 = idx.shape
+    ``decoder``: a Decoder to reuse across calls (same batch size and form; ``cached_decoder``
+    builds the one a call needs): its weight shadows and captured graphs survive, so
+    ``sample.py``'s num_samples loop captures once.  The caller releases it; without one, or
+    with one that does not fit, a temporary decoder is built and released here."""
+    T0 = idx.shape[1]
     top_p, min_p = sampling_filters(top_p, min_p)
     if max_new_tokens <= 0:
         return idx
-    if quantize not in (None, "int8"):
-        raise ValueError(f"quantize must be None or 'int8', got {quantize!r}")
-    if kv_quantize not in (None, "int8"):
-        raise ValueError(f"kv_quantize must be None or 'int8', got {kv_quantize!r}")
-    if shared_prompt:
-        if kv_quantize:
-            raise ValueError("shared_prompt keeps bf16 caches: it cannot be combined with kv_quantize")
-        if not bool((idx == idx[:1]).all()):
-            raise ValueError("shared_prompt needs every row of idx to be the same prompt")
-        if B > 1:
-            new = _generate_shared(model, idx[0], B, max_new_tokens, temperature, top_k, None, use_graph, decoder,
-                                   top_p, min_p, quantize, per_row=False)
-            return torch.cat([idx, new], dim=1)
-    if T0 + max_new_tokens - 1 > model.config.block_size:
-        if quantize:
-            raise ValueError("quantize needs the KV-cache path: prompt + new tokens exceed block_size, and the "
-                             "recompute loop runs the unquantized model")
-        if kv_quantize:
-            raise ValueError("kv_quantize needs the KV-cache path: prompt + new tokens exceed block_size, and the "
-                             "recompute loop has no cache to quantize")
+    mode = _cached_mode(model, idx, max_new_tokens, quantize, kv_quantize, shared_prompt)
+    if mode is None:
         # the caches hold block_size positions; nanoGPT crops the context beyond that
         return model.generate(idx, max_new_tokens, temperature=temperature, top_k=top_k, top_p=top_p, min_p=min_p)
-    own = (decoder is None or decoder.B != B or decoder.quantize != quantize
-           or decoder.kv_quantize != kv_quantize or decoder.shared)
-    dec = (Decoder(model, B, max_len=model.config.block_size, use_graph=use_graph, quantize=quantize,
-                   kv_quantize=kv_quantize) if own else decoder)
-    try:
-        dec.reseed()  # every call draws its own samples, also on a reused decoder / graph
-        dec.sample_into(dec.prefill(idx), temperature, top_k, None, top_p, min_p)  # pos = T0: gen[:, T0]
+    with _borrow(model, mode, decoder, use_graph) as dec:
+        logits = dec.prefill_shared(idx[0]) if dec.shared else dec.prefill(idx)
+        dec.sample_into(logits, temperature, top_k, None, top_p, min_p)  # pos = T0: gen[:, T0]
         dec.run(max_new_tokens - 1, temperature, top_k, None, top_p, min_p)
         return torch.cat([idx, dec.gen[:, T0:T0 + max_new_tokens]], dim=1)
-    finally:
-        if own:
-            dec.release()
 
 
-def _cut_at_stop(new: torch.Tensor, stop_token: int | None) -> torch.Tensor:
-    """The new tokens up to and including the first ``stop_token``."""
-    if stop_token is None:
-        return new
-    hit = (new == stop_token).nonzero()
-    return new[:int(hit[0]) + 1] if hit.numel() else new
+def _right_pad(prompts, device):
+    """1-D ``prompts`` as one right-padded (any valid id) int64 [n, longest] and their lengths [n]."""
+    lens = [p.numel() for p in prompts]
+    idx = torch.zeros(len(prompts), max(lens), dtype=torch.int64, device=device)
+    for b, p in enumerate(prompts):
+        idx[b, :lens[b]] = p
+    return idx, torch.tensor(lens, dtype=torch.int64, device=device)
 
 
-def _generate_shared(model, prompt, B, max_new_tokens, temperature, top_k, stop_token, use_graph, decoder, top_p,
-                     min_p, quantize, per_row) -> torch.Tensor:
-    """B continuations of the one 1-D ``prompt`` on a shared_prompt decoder -> the new tokens
-    [B, max_new_tokens] (whatever a row holds after its stop token is for the caller to cut).
-    ``decoder`` is reused if it is a shared one of this B, per_row and quantize whose row
-    caches hold max_new_tokens slots; the prompt it has cached is not encoded again.
-    (Prompts that share only a prefix: ``_generate_prefix``.)"""
-    T0 = prompt.numel()
-    if T0 + max_new_tokens > model.config.block_size:
-        raise ValueError(f"shared_prompt needs the KV-cache path: prompt ({T0}) + new tokens ({max_new_tokens}) "
-                         f"exceed block_size {model.config.block_size}, and the recompute loop has nothing to share")
-    own = (decoder is None or not decoder.shared or decoder.B != B or decoder.per_row != per_row
-           or decoder.quantize != quantize or decoder.R < max_new_tokens)
-    dec = (Decoder(model, B, max_len=model.config.block_size, use_graph=use_graph, per_row=per_row,
-                   quantize=quantize, shared_prompt=True, max_new=max_new_tokens) if own else decoder)
-    try:
-        dec.reseed()
-        dec.sample_into(dec.prefill_shared(prompt), temperature, top_k, stop_token, top_p, min_p)  # gen[:, T0]
-        dec.run(max_new_tokens - 1, temperature, top_k, stop_token, top_p, min_p)
-        return dec.gen[:, T0:T0 + max_new_tokens].clone()
-    finally:
-        if own:
-            dec.release()
+def _result(prompt, new, stop_token=None) -> torch.Tensor:
+    """The prompt followed by its new tokens, those up to and including the first ``stop_token``."""
+    if stop_token is not None:
+        hit = (new == stop_token).nonzero()
+        if hit.numel():
+            new = new[:int(hit[0]) + 1]
+    return torch.cat([prompt, new])
 
 
 def common_prefix_len(prompts) -> int:
@@ -841,94 +870,64 @@ def common_prefix_len(prompts) -> int:
     return int(same.long().cumprod(0).sum())
 
 
-def _generate_prefix(model, prompts, P, max_new_tokens, temperature, top_k, stop_token, use_graph, decoder, top_p,
-                     min_p, quantize) -> list[torch.Tensor]:
-    """``generate_batch`` for prompts whose first ``P`` tokens are one prefix, on a shared per-row
-    decoder: the prefix goes through the model once into the prompt caches (``prefill_shared``; not
-    at all if the decoder holds it already), the right-padded suffixes through ``prefill_suffixes``
-    into the row caches, and the steps are the shared-prompt ones.  ``decoder`` is reused if it
-    is a shared per_row one of this B and quantize whose row caches hold the longest suffix +
-    max_new_tokens slots."""
-    T = model.config.block_size
+def _batch_plan(model, prompts, max_new_tokens, quantize, kv_quantize, shared_prompt, shared_prefix, batch_size):
+    """What ``generate_batch`` does with a call -> (prompts, budgets, queue, fit, P, mode): the
+    flattened prompts on the model's device, every prompt's budget of new tokens, whether they are
+    served as a queue, the indices of the prompts that share the decoder (the others go alone), the
+    length of the prefix they share through ``prefill_suffixes`` (0: none) and the decoder's mode
+    (None: no prompt fits).  None: there is nothing to generate."""
+    queue = batch_size is not None or not isinstance(max_new_tokens, int)
+    if queue:
+        if batch_size is not None and (not isinstance(batch_size, int) or batch_size < 1):
+            raise ValueError(f"batch_size must be a positive int, got {batch_size!r}")
+        if shared_prefix:
+            raise ValueError("shared_prefix batches are not served as a queue: drop batch_size / per-prompt budgets")
+        if not isinstance(max_new_tokens, int):
+            budgets = [int(n) for n in max_new_tokens]
+            if len(budgets) != len(prompts):
+                raise ValueError(f"{len(budgets)} budgets for {len(prompts)} prompts")
+            if any(n < 1 for n in budgets):
+                raise ValueError(f"every budget must be at least 1, got {budgets}")
+    _check_mode(quantize, kv_quantize, shared_prompt, shared_prefix)
+    assert all(p.numel() >= 1 for p in prompts), "every prompt needs at least one token"
     device = model.lm_head.weight.device
-    B = len(prompts)
-    lens = [p.numel() - P for p in prompts]
-    S = max(lens)
-    for p in prompts:
-        if p.numel() + max_new_tokens > T:
-            raise ValueError(f"shared_prefix needs the KV-cache path: prompt ({p.numel()}) + new tokens "
-                             f"({max_new_tokens}) exceed block_size {T}, and the recompute loop has nothing to share")
-    need = S + max_new_tokens
-    own = (decoder is None or not decoder.shared or decoder.B != B or not decoder.per_row
-           or decoder.quantize != quantize or decoder.R < need)
-    dec = (Decoder(model, B, max_len=T, use_graph=use_graph, per_row=True, quantize=quantize, shared_prompt=True,
-                   max_new=need) if own else decoder)
-    try:
-        idx = torch.zeros(B, S, dtype=torch.int64, device=device)  # right-padded (any valid id)
-        for b, p in enumerate(prompts):
-            idx[b, :lens[b]] = p[P:]
-        dec.reseed()
-        dec.prefill_shared(prompts[0][:P].to(device))
-        logits = dec.prefill_suffixes(idx, torch.tensor(lens, dtype=torch.int64, device=device))
-        dec.sample_into(logits, temperature, top_k, stop_token, top_p, min_p)  # gen[b, P + lens[b]]
-        dec.run(max_new_tokens - 1, temperature, top_k, stop_token, top_p, min_p)
-        outs = []
-        for b, p in enumerate(prompts):
-            new = dec.gen[b, p.numel():p.numel() + max_new_tokens]
-            outs.append(torch.cat([p.to(device), _cut_at_stop(new, stop_token)]))
-        return outs
-    finally:
-        if own:
-            dec.release()
-
-
-def _generate_queue(model, prompts, budgets, batch_size, temperature, top_k, stop_token, use_graph, decoder, top_p,
-                    min_p, quantize, kv_quantize, shared_prompt) -> list[torch.Tensor]:
-    """``generate_batch`` with a ``batch_size`` or one budget per prompt: the prompts are a queue
-    served in order through min(batch_size, number of prompts) rows of one per_row decoder
-    (``Decoder.serve``).  ``decoder`` is reused if it is a per_row one of that many rows and of
-    the same quantize / kv_quantize / shared form (a shared one: with row caches that hold the
-    largest budget)."""
+    prompts = [p.view(-1).to(device) for p in prompts]
+    if shared_prompt and any(p.shape != prompts[0].shape or not torch.equal(p, prompts[0]) for p in prompts[1:]):
+        raise ValueError("shared_prompt needs every prompt to be the same")
+    if isinstance(max_new_tokens, int):
+        if max_new_tokens <= 0:
+            return None
+        budgets = [max_new_tokens] * len(prompts)
     T = model.config.block_size
-    device = model.lm_head.weight.device
-    outs: list = [None] * len(prompts)
-    fit = [i for i, p in enumerate(prompts) if p.numel() + budgets[i] <= T]
-    for i, p in enumerate(prompts):
-        if i in fit:
-            continue
-        if shared_prompt:
-            raise ValueError(f"shared_prompt needs the KV-cache path: prompt ({p.numel()}) + new tokens "
-                             f"({budgets[i]}) exceed block_size {T}, and the recompute loop has nothing to share")
-        # a finished row idles at its last position, which must be a cache row: such a request goes alone
-        y = generate_cached(model, p.to(device)[None], budgets[i], temperature=temperature, top_k=top_k,
-                            use_graph=use_graph, top_p=top_p, min_p=min_p, quantize=quantize,
-                            kv_quantize=kv_quantize)[0]
-        outs[i] = torch.cat([y[:p.numel()], _cut_at_stop(y[p.numel():], stop_token)])
+    P = common_prefix_len(prompts) if shared_prefix and len(prompts) > 1 else 0  # one prompt, no prefix: ordinary
+    sharing = "shared_prefix" if P else "shared_prompt" if shared_prompt and (queue or len(prompts) > 1) else None
+    # an ordinary batch's last new token is drawn and never fed, so it needs no cache row; a queue's finished
+    # row idles at its last position, which must be a cache row: a request that does not fit so goes alone
+    spare = 0 if queue or sharing else 1
+    fit = [i for i, p in enumerate(prompts) if p.numel() + budgets[i] - spare <= T]
+    if sharing:
+        for i, p in enumerate(prompts):
+            if i not in fit:
+                raise _nothing_to_share(sharing, p.numel(), budgets[i], T)
     if not fit:
-        return outs
-    B = min(len(fit) if batch_size is None else batch_size, len(fit))
-    shared = shared_prompt and B >= 2  # a single row goes the ordinary way
-    need = max(budgets[i] for i in fit)
-    own = (decoder is None or decoder.B != B or not decoder.per_row or decoder.quantize != quantize
-           or decoder.kv_quantize != kv_quantize or decoder.shared != shared or (shared and decoder.R < need))
-    if not own:
-        dec = decoder
-    elif shared:
-        dec = Decoder(model, B, max_len=T, use_graph=use_graph, per_row=True, quantize=quantize, shared_prompt=True,
-                      max_new=need)
-    else:
-        dec = Decoder(model, B, max_len=T, use_graph=use_graph, per_row=True, quantize=quantize,
-                      kv_quantize=kv_quantize)
-    try:
-        dec.reseed()
-        news = dec.serve([prompts[i].to(device) for i in fit], [budgets[i] for i in fit], temperature, top_k,
-                         stop_token, top_p, min_p)
-        for i, new in zip(fit, news):
-            outs[i] = torch.cat([prompts[i].to(device), new])
-    finally:
-        if own:
-            dec.release()
-    return outs
+        return prompts, budgets, queue, fit, P, None
+    B = len(fit) if batch_size is None else min(batch_size, len(fit))
+    slots = None
+    if sharing and B >= 2:  # a single row goes the ordinary way
+        # a row's cache holds what follows the shared tokens: its suffix, if any, and its new tokens
+        slots = max(budgets[i] + (prompts[i].numel() - P if P else 0) for i in fit)
+    return prompts, budgets, queue, fit, P, _mode(B, True, quantize, kv_quantize, slots)
+
+
+def batch_decoder(model, prompts, max_new_tokens, use_graph=None, quantize=None, kv_quantize=None,
+                  shared_prompt=False, shared_prefix=False, batch_size=None):
+    """The Decoder this ``generate_batch`` call would build, for a caller that keeps it across
+    calls (``decoder=``; a shared one then keeps the prompt or prefix too) and releases it.  A call
+    that shares none (no new tokens, or no prompt that fits the cache) gets the ordinary one of a
+    row per prompt, for the reason ``cached_decoder`` gives."""
+    plan = _batch_plan(model, prompts, max_new_tokens, quantize, kv_quantize, shared_prompt, shared_prefix, batch_size)
+    mode = plan and plan[-1]
+    return _build(model, mode or _mode(len(prompts), True, quantize, kv_quantize), use_graph)
 
 
 @torch.no_grad()
@@ -949,8 +948,9 @@ def generate_batch(model, prompts, max_new_tokens, temperature: float = 1.0, top
     ``generate_cached`` on its own (the recompute loop) and is cut at the stop token.
 
     ``decoder``: a per_row Decoder of the right batch size to reuse across calls (weight
-    shadows and captured graphs survive); the caller releases it.  ``quantize="int8"``:
-    int8 weights; a row that needs the recompute loop then raises ValueError.
+    shadows and captured graphs survive; ``batch_decoder`` builds the one a call needs); the
+    caller releases it.  ``quantize="int8"``: int8 weights; a row that needs the recompute
+    loop then raises ValueError.
     ``kv_quantize="int8"``: int8 KV caches, with the same refusal.
 
     ``shared_prompt=True``: every prompt must be the same one (ValueError otherwise); it is
@@ -985,84 +985,37 @@ def generate_batch(model, prompts, max_new_tokens, temperature: float = 1.0, top
     ``generate_cached`` (``quantize`` / ``kv_quantize`` / ``shared_prompt``: ValueError).
     ``shared_prefix=True``, ``batch_size < 1`` and a budget list of the wrong length or with an
     entry < 1 raise ValueError.  With ``batch_size=None`` and an int budget nothing changes."""
-    queue = batch_size is not None or not isinstance(max_new_tokens, int)
-    if queue:
-        if batch_size is not None and (not isinstance(batch_size, int) or batch_size < 1):
-            raise ValueError(f"batch_size must be a positive int, got {batch_size!r}")
-        if shared_prefix:
-            raise ValueError("shared_prefix batches are not served as a queue: drop batch_size / per-prompt budgets")
-        if not isinstance(max_new_tokens, int):
-            budgets = [int(n) for n in max_new_tokens]
-            if len(budgets) != len(prompts):
-                raise ValueError(f"{len(budgets)} budgets for {len(prompts)} prompts")
-            if any(n < 1 for n in budgets):
-                raise ValueError(f"every budget must be at least 1, got {budgets}")
-    if quantize not in (None, "int8"):
-        raise ValueError(f"quantize must be None or 'int8', got {quantize!r}")
-    if kv_quantize not in (None, "int8"):
-        raise ValueError(f"kv_quantize must be None or 'int8', got {kv_quantize!r}")
-    if stop_token is not None and stop_token < 0:
-        stop_token = None
-    top_p, min_p = sampling_filters(top_p, min_p)
-    prompts = [p.view(-1) for p in prompts]
-    assert all(p.numel() >= 1 for p in prompts), "every prompt needs at least one token"
-    if shared_prompt:
-        if kv_quantize:
-            raise ValueError("shared_prompt keeps bf16 caches: it cannot be combined with kv_quantize")
-        if any(p.shape != prompts[0].shape or not torch.equal(p, prompts[0]) for p in prompts[1:]):
-            raise ValueError("shared_prompt needs every prompt to be the same")
-    if shared_prefix:
-        if shared_prompt:
-            raise ValueError("shared_prefix and shared_prompt are two forms of sharing: pass one of them")
-        if kv_quantize:
-            raise ValueError("shared_prefix keeps bf16 caches: it cannot be combined with kv_quantize")
-    if isinstance(max_new_tokens, int) and max_new_tokens <= 0:
-        return list(prompts)
-    if queue:
-        if isinstance(max_new_tokens, int):
-            budgets = [max_new_tokens] * len(prompts)
-        return _generate_queue(model, prompts, budgets, batch_size, temperature, top_k, stop_token, use_graph,
-                               decoder, top_p, min_p, quantize, kv_quantize, shared_prompt)
-    T = model.config.block_size
-    device = model.lm_head.weight.device
-    if shared_prefix and len(prompts) > 1:
-        P = common_prefix_len(prompts)
-        if P > 0:
-            return _generate_prefix(model, prompts, P, max_new_tokens, temperature, top_k, stop_token, use_graph,
-                                    decoder, top_p, min_p, quantize)
-    if shared_prompt and len(prompts) > 1:
-        p = prompts[0].to(device)
-        new = _generate_shared(model, p, len(prompts), max_new_tokens, temperature, top_k, stop_token, use_graph,
-                               decoder, top_p, min_p, quantize, per_row=True)
-        return [torch.cat([p, _cut_at_stop(row, stop_token)]) for row in new]
+    plan = _batch_plan(model, prompts, max_new_tokens, quantize, kv_quantize, shared_prompt, shared_prefix, batch_size)
+    stop_token = _stop(stop_token)
+    sampling = (temperature, top_k, stop_token, *sampling_filters(top_p, min_p))
+    if plan is None:
+        return [p.view(-1) for p in prompts]
+    prompts, budgets, queue, fit, P, mode = plan
     outs: list = [None] * len(prompts)
-    rows = [i for i, p in enumerate(prompts) if p.numel() + max_new_tokens - 1 <= T]
     for i, p in enumerate(prompts):
-        if i not in rows:
-            y = generate_cached(model, p.to(device)[None], max_new_tokens, temperature=temperature, top_k=top_k,
-                                use_graph=use_graph, top_p=top_p, min_p=min_p, quantize=quantize,
-                                kv_quantize=kv_quantize)[0]
-            outs[i] = torch.cat([y[:p.numel()], _cut_at_stop(y[p.numel():], stop_token)])
-    if not rows:
+        if i not in fit:  # alone through ``generate_cached``: the recompute loop, or a decoder of its own
+            y = generate_cached(model, p[None], budgets[i], temperature=temperature, top_k=top_k, use_graph=use_graph,
+                                top_p=top_p, min_p=min_p, quantize=quantize, kv_quantize=kv_quantize)[0]
+            outs[i] = _result(p, y[p.numel():], stop_token)
+    if not fit:
         return outs
-    B = len(rows)
-    lens = [prompts[i].numel() for i in rows]
-    idx = torch.zeros(B, max(lens), dtype=torch.int64, device=device)  # right-padded (any valid id)
-    for b, i in enumerate(rows):
-        idx[b, :lens[b]] = prompts[i]
-    own = (decoder is None or decoder.B != B or not decoder.per_row or decoder.quantize != quantize
-           or decoder.kv_quantize != kv_quantize or decoder.shared)
-    dec = (Decoder(model, B, max_len=T, use_graph=use_graph, per_row=True, quantize=quantize,
-                   kv_quantize=kv_quantize) if own else decoder)
-    try:
-        dec.reseed()
-        logits = dec.prefill(idx, torch.tensor(lens, dtype=torch.int64, device=device))
-        dec.sample_into(logits, temperature, top_k, stop_token, top_p, min_p)  # gen[b, lens[b]]
-        dec.run(max_new_tokens - 1, temperature, top_k, stop_token, top_p, min_p)
-        for b, i in enumerate(rows):
-            new = dec.gen[b, lens[b]:lens[b] + max_new_tokens]
-            outs[i] = torch.cat([idx[b, :lens[b]], _cut_at_stop(new, stop_token)])
-    finally:
-        if own:
-            dec.release()
+    with _borrow(model, mode, decoder, use_graph) as dec:
+        if queue:
+            news = dec.serve([prompts[i] for i in fit], [budgets[i] for i in fit], *sampling)
+        else:
+            if P:
+                dec.prefill_shared(prompts[0][:P])
+                logits = dec.prefill_suffixes(*_right_pad([p[P:] for p in prompts], dec.device))
+            elif dec.shared:
+                logits = dec.prefill_shared(prompts[0])
+            else:
+                logits = dec.prefill(*_right_pad([prompts[i] for i in fit], dec.device))
+            dec.sample_into(logits, *sampling)  # gen[b, its prompt's length]
+            dec.run(max_new_tokens - 1, *sampling)
+        for b, i in enumerate(fit):
+            L = prompts[i].numel()
+            outs[i] = (_result(prompts[i], news[b]) if queue else
+                       _result(prompts[i], dec.gen[b, L:L + max_new_tokens], stop_token))
     return outs
+
+

@@ -115,23 +115,13 @@ def _generate_batches(model, c, encode, decode, start, device):
         for batch in batches:
             prompts = [torch.tensor(encode(t), dtype=torch.long, device=device) for t in batch]
             if c["kv_cache"]:
-                from .runtime.decode import Decoder, common_prefix_len
+                from .runtime.decode import batch_decoder
                 B = len(prompts)
-                sh = shared and B > 1  # a last round of one sample goes the ordinary way
-                # shared_prefix: row caches for the longest suffix + the new tokens (no common prefix: ordinary)
-                P = common_prefix_len(prompts) if prefix and B > 1 else 0
-                if B not in decs:
-                    if sh or P:  # the prompt / prefix stays cached in the decoder: later rounds do not encode it again
-                        new = max(1, c["max_new_tokens"]) + (max(p.numel() for p in prompts) - P if P else 0)
-                        decs[B] = Decoder(model, B, max_len=model.config.block_size, per_row=True, quantize=quantize,
-                                          shared_prompt=True, max_new=min(new, model.config.block_size))
-                    else:
-                        decs[B] = Decoder(model, B, max_len=model.config.block_size, per_row=True, quantize=quantize,
-                                          kv_quantize=kv_quantize)
+                mode = dict(quantize=quantize, kv_quantize=kv_quantize, shared_prompt=shared, shared_prefix=prefix)
+                if B not in decs:  # a shared prompt / prefix stays cached in it: later rounds do not encode it again
+                    decs[B] = batch_decoder(model, prompts, c["max_new_tokens"], **mode)
                 ys = model.generate_batch(prompts, c["max_new_tokens"], temperature=c["temperature"], top_k=c["top_k"],
-                                          stop_token=stop, decoder=decs[B], top_p=c["top_p"], min_p=c["min_p"],
-                                          quantize=quantize, kv_quantize=kv_quantize, shared_prompt=sh,
-                                          shared_prefix=prefix)
+                                          stop_token=stop, decoder=decs[B], top_p=c["top_p"], min_p=c["min_p"], **mode)
             else:
                 ys = [model.generate(p[None], c["max_new_tokens"], temperature=c["temperature"], top_k=c["top_k"],
                                      top_p=c["top_p"], min_p=c["min_p"])[0] for p in prompts]
@@ -247,9 +237,8 @@ def main(argv=None):
     if c["kv_cache"]:
         # one decoder for all samples: weight shadows and the captured step graph are
         # built once, not per sample
-        from .runtime.decode import Decoder
-        dec = Decoder(model, x.shape[0], max_len=model.config.block_size, quantize=quantize,
-                      kv_quantize=kv_quantize)
+        from .runtime.decode import cached_decoder
+        dec = cached_decoder(model, x, c["max_new_tokens"], quantize=quantize, kv_quantize=kv_quantize)
     try:
         with torch.no_grad():
             for _ in range(c["num_samples"]):
