@@ -40,6 +40,11 @@ struct CacheScales<int8_t> {
 // append: also store the new token's K / V rows at position pos (kc_w / vc_w alias
 // kc / vc; separate non-restrict pointers for the one write)
 //
+// One contract for both cache forms: the output is a function of the cache contents only, the
+// row at pos included.  Without append every K and V row, pos too, is read from the cache and
+// the k | v parts of qkv are not looked at; with append the result is what kv_append followed
+// by a plain call gives, bit for bit, in the partials and in the output.
+//
 // CT: the cache's element type.  bf16_t: the rows hold the values.  int8_t: 64-byte rows with
 // one fp32 scale per row in cs.k / cs.v (CacheScales: empty in the bf16 form).  A thread scores
 // its key on the raw bytes (int8 -> float
@@ -106,7 +111,8 @@ __device__ __forceinline__ void decode_attn_chunk(const bf16_t* __restrict__ qro
   } else {
     if (append && pos < k0 + DA_CHUNK && tid < 2 * (DA_D / 8)) {
       // this chunk holds position pos: store the new token's K / V rows for later steps
-      // (this kernel itself takes them straight from qkv, so no write->read ordering)
+      // (appending, this kernel itself takes them straight from qkv, bitwise what it stores
+      // here, so no write->read ordering)
       const int c = tid & 7, kv = tid >> 3;
       *reinterpret_cast<uint4*>((kv ? vc_w : kc_w) + (row0 + pos) * DA_D + 8 * c) =
           *reinterpret_cast<const uint4*>(qrow + (1 + kv) * C + 8 * c);
@@ -134,7 +140,9 @@ __device__ __forceinline__ void decode_attn_chunk(const bf16_t* __restrict__ qro
       }
       acc *= ks;
     } else {
-      const bf16_t* krow = key == pos ? qrow + C : kc + (row0 + key) * DA_D;
+      // the new token's row comes from qkv when appending (this launch is what writes it to
+      // the cache), as its V row does below; otherwise every row, pos included, is the cache's
+      const bf16_t* krow = (append && key == pos) ? qrow + C : kc + (row0 + key) * DA_D;
 #pragma unroll
       for (int c = 0; c < DA_D / 8; ++c) {
         float kf[8];

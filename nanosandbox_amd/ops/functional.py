@@ -1051,12 +1051,15 @@ def decode_attention(qkv, kc, vc, pos, n_head: int, append: bool = False, combin
     kernels; otherwise fp32 torch (CPU reference).  ``combine=False`` with one row on the
     GPU returns the partials (``AttnPartials``) for ``decode_linear`` to combine.
 
+    One contract for every path and both cache forms: the token attends over cache rows
+    0 .. pos, its own included, so the result depends on the cache contents only.  Without
+    ``append`` the K / V parts of ``qkv`` are not read (the caches must already hold row
+    ``pos``); ``append=True`` equals ``kv_append`` followed by ``append=False`` bit for bit.
+
     ``kc`` / ``vc`` may be ``QuantCache``s (int8 rows with one scale each): the token's K / V
-    are appended quantized and it attends over the dequantized rows 0 .. pos, its own
-    included, so the result depends on the cache contents only and ``append=True`` equals
-    ``kv_append`` followed by ``append=False`` bit for bit.  GPU, bf16, D = 64: the ``_kv8``
-    forms of the same kernels (same partials); anything else: this function's fp32 torch
-    path over ``dequantize_cache``."""
+    are appended quantized and it attends over the dequantized rows.  GPU, bf16, D = 64: the
+    ``_kv8`` forms of the same kernels (same partials); anything else: this function's fp32
+    torch path over ``dequantize_cache``."""
     B, S, C3 = qkv.shape
     C = C3 // 3
     _, H, Tmax, D = kc.shape
