@@ -379,23 +379,27 @@ class GPT(nn.Module):
 
     @torch.no_grad()
     def generate_cached(self, idx, max_new_tokens, temperature=1.0, top_k=None, use_graph=None, decoder=None,
-                        top_p=None, min_p=None, quantize=None, kv_quantize=None, shared_prompt=False):
+                        top_p=None, min_p=None, quantize=None, kv_quantize=None, shared_prompt=False,
+                        speculate=None, spec_ngram=3, spec_table=None):
         """``generate`` with per-layer KV caches: the prompt is encoded once and every
         new token runs one position through the model (a replayed HIP graph on the GPU;
         ``runtime/decode.py``).  Same sampling; falls back to ``generate`` when prompt +
         new tokens exceed block_size.  ``quantize="int8"``: int8 weight-only decoding;
         ``kv_quantize="int8"``: int8 KV caches (either: no fallback, ValueError past
         block_size).  ``shared_prompt=True``: the rows of ``idx`` are one prompt, cached once
-        for the whole batch (equal rows or ValueError; no fallback either)."""
+        for the whole batch (equal rows or ValueError; no fallback either).  ``speculate=K``:
+        speculative decoding with K tokens drafted by ``spec_ngram``-gram lookup in the row's own
+        history (or read from ``spec_table``): the same tokens in fewer model passes."""
         from ..runtime.decode import generate_cached
         return generate_cached(self, idx, max_new_tokens, temperature=temperature, top_k=top_k, use_graph=use_graph,
                                decoder=decoder, top_p=top_p, min_p=min_p, quantize=quantize,
-                               kv_quantize=kv_quantize, shared_prompt=shared_prompt)
+                               kv_quantize=kv_quantize, shared_prompt=shared_prompt, speculate=speculate,
+                               spec_ngram=spec_ngram, spec_table=spec_table)
 
     @torch.no_grad()
     def generate_batch(self, prompts, max_new_tokens, temperature=1.0, top_k=None, stop_token=None, use_graph=None,
                        decoder=None, top_p=None, min_p=None, quantize=None, kv_quantize=None, shared_prompt=False,
-                       shared_prefix=False, batch_size=None):
+                       shared_prefix=False, batch_size=None, speculate=None, spec_ngram=3, spec_table=None):
         """``generate_cached`` for a list of 1-D prompts of unequal lengths, decoded as one
         batch with a position per row; returns a list of 1-D tensors (prompt + new tokens).
         A row that draws ``stop_token`` ends with it; the others get exactly
@@ -404,9 +408,12 @@ class GPT(nn.Module):
         ``shared_prefix=True``: the prompts' longest common token prefix is encoded and cached
         once, and every row prefills only what it adds to it.  ``batch_size=B`` (and / or
         ``max_new_tokens`` as one int per prompt): the prompts are a queue served in order through
-        at most B rows, a finished row taking the next prompt; results in prompt order."""
+        at most B rows, a finished row taking the next prompt; results in prompt order.
+        ``speculate=K`` / ``spec_ngram`` / ``spec_table``: speculative decoding, as in
+        ``generate_cached``."""
         from ..runtime.decode import generate_batch
         return generate_batch(self, prompts, max_new_tokens, temperature=temperature, top_k=top_k,
                               stop_token=stop_token, use_graph=use_graph, decoder=decoder, top_p=top_p, min_p=min_p,
                               quantize=quantize, kv_quantize=kv_quantize, shared_prompt=shared_prompt,
-                              shared_prefix=shared_prefix, batch_size=batch_size)
+                              shared_prefix=shared_prefix, batch_size=batch_size, speculate=speculate,
+                              spec_ngram=spec_ngram, spec_table=spec_table)

@@ -130,6 +130,14 @@ _SIGNATURES = {
     # suffix queries over a shared prefix cache + the row's own keys (csrc/kernels/prefix_attn.hip): qkv, pk, pv,
     # out, B, S, H, Tp, P, scale
     "nsa_prefix_attn": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p],
+    # S consecutive queries of one sequence (csrc/kernels/decode_spec.hip): qkv, kc, vc, pos, ws, out, B, S, H, D,
+    # Tmax, scale
+    "nsa_decode_attn_spec": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                             c_int, c_float, c_void_p],
+    # speculative accept + draft (csrc/kernels/spec.hip): gen, gen_ld, T, pos, tok, done, end, cand, stok, spos,
+    # cpos, table, table_ld, stats, B, K, N, stop_token
+    "nsa_spec_step": [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                      c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p],
     "nsa_flash_bwd2": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                        c_int, c_int, c_int, c_int, c_float, c_float, c_uint64, c_void_p],
     "nsa_rng_advance": [c_void_p],

@@ -1151,6 +1151,182 @@ def decode_attention_shared(qkv, pkc, pvc, kc, vc, plen, pos, n_head: int, appen
     return y.reshape(B, 1, C).to(qkv.dtype)
 
 
+SPEC_MAX_QUERIES = 8  # queries per row of decode_attention_spec: 1 fed token + at most 7 drafts
+
+
+def decode_attention_spec(qkv, kc, vc, pos, n_head: int):
+    """``decode_attention(append=True)`` for S consecutive tokens of every sequence, a speculative
+    step's fed token and its drafts: qkv [B, S, 3C] (2 <= S <= 8) -> [B, S, C].
+
+    ``pos`` is int64 [B] on the caches' device.  Query j of row b sits at position ``pos[b] + j``:
+    its K / V rows are stored at that cache row and it attends over keys 0 .. pos[b] + j, the
+    j + 1 new rows of this call included.  A dead query, ``pos[b] + j >= Tmax``, stores nothing
+    and its output row is zeros.
+
+    Output and caches equal S successive ``decode_attention(qkv[:, j:j+1], kc, vc, pos + j,
+    n_head, append=True)`` calls on the live queries, bit for bit on the GPU (bf16, D = 64:
+    one launch of ``nsa_decode_attn_spec``, which fetches a chunk's K / V rows once for all S
+    queries, plus the combine of ``decode_attention``), so a token's attention does not depend
+    on how positions were grouped into steps.  Anything else: fp32 torch with the same liveness
+    rule (the reference).  bf16 caches only."""
+    B, S, C3 = qkv.shape
+    C = C3 // 3
+    assert not isinstance(kc, QuantCache) and not isinstance(vc, QuantCache), "no int8 caches in the speculative form"
+    Bc, H, Tmax, D = kc.shape
+    assert 2 <= S <= SPEC_MAX_QUERIES, f"2 .. {SPEC_MAX_QUERIES} queries per row, got {S}"
+    assert H == n_head and C == H * D and Bc == B and vc.shape == kc.shape
+    assert pos.numel() == B and pos.dtype == torch.int64, "one position per row"
+    scale = 1.0 / math.sqrt(D)
+    if qkv.is_cuda and qkv.dtype == BF16 and kc.dtype == BF16 and vc.dtype == BF16 and D == 64:
+        qkv = qkv.contiguous()
+        assert kc.is_contiguous() and vc.is_contiguous() and pos.is_contiguous()
+        n_split = -(-Tmax // 256)
+        ws = torch.empty(B * S * H * n_split * (4 + D), device=qkv.device, dtype=F32)
+        out = torch.empty(B, S, C, device=qkv.device, dtype=qkv.dtype)
+        _lib.call("nsa_decode_attn_spec", _lib.ptr(qkv), _lib.ptr(kc), _lib.ptr(vc), _lib.ptr(pos), _lib.ptr(ws),
+                  _lib.ptr(out), B, S, H, D, Tmax, scale, _lib.stream())
+        return out
+    q, kn, vn = qkv.view(B, S, 3, H, D).unbind(2)               # [B, S, H, D] each
+    y = torch.zeros(B, S, H, D, dtype=F32, device=qkv.device)
+    for b, p in enumerate(pos.view(-1).tolist()):
+        for j in range(S):
+            pj = p + j
+            if pj >= Tmax:
+                break
+            kc[b, :, pj] = kn[b, j].to(kc.dtype)
+            vc[b, :, pj] = vn[b, j].to(vc.dtype)
+            k, v = kc[b, :, :pj + 1].float(), vc[b, :, :pj + 1].float()          # [H, pj + 1, D]
+            att = torch.softmax(torch.einsum("hd,hkd->hk", q[b, j].float(), k) * scale, dim=-1)
+            y[b, j] = torch.einsum("hk,hkd->hd", att, v)
+    return y.reshape(B, S, C).to(qkv.dtype)
+
+
+SPEC_MAX_DRAFTS = SPEC_MAX_QUERIES - 1
+SPEC_MAX_T = 16000  # nsa_spec_step keeps a row's history in LDS
+
+
+def _ngram_continue(h, p: int, K: int, N: int):
+    """The K ids prompt lookup drafts after ``h[0 .. p]`` (a list): for n = N down to 1 (n <= p)
+    the most recent earlier occurrence of the suffix ``h[p-n+1 .. p]``, starting at s with
+    s + n <= p, continued periodically with period L = p + 1 - (s + n); no match: ``h[p]``."""
+    for n in range(min(N, p), 0, -1):
+        suffix = h[p - n + 1:p + 1]
+        for s in range(p - n, -1, -1):
+            if h[s:s + n] == suffix:
+                L = p + 1 - (s + n)
+                return [h[s + n + i % L] for i in range(K)]
+    return [h[p]] * K
+
+
+def _spec_buffers(B, K, device):
+    return tuple(torch.zeros(B, K + 1, dtype=torch.int64, device=device) for _ in range(3))
+
+
+def _spec_step(gen, pos, tok, done, end, cand, stok, spos, cpos, table, stats, K, N, T, stop_token):
+    """Accept (``cand`` given) and draft: ``nsa_spec_step`` on the GPU, the loop that states its
+    rule elsewhere (csrc/kernels/spec.hip tells it in full)."""
+    B = pos.numel()
+    assert 1 <= K <= SPEC_MAX_DRAFTS and N >= 1, \
+        f"1 .. {SPEC_MAX_DRAFTS} drafts and n-grams of at least 1, got {K}, {N}"
+    assert gen.dim() == 2 and gen.shape[0] == B and gen.shape[1] > T >= 1 and gen.stride(1) == 1
+    for t in (gen, pos, tok, done, end, cand, stok, spos, cpos, table, stats):
+        assert t is None or (t.dtype == torch.int64 and t.device == gen.device)
+    for t in (pos, tok, done, end):
+        assert t is None or (t.numel() == B and t.is_contiguous())
+    for t in (cand, stok, spos, cpos):
+        assert t is None or (t.shape == (B, K + 1) and t.is_contiguous())
+    assert table is None or (table.dim() == 2 and table.shape[0] == B and table.shape[1] > T and table.stride(1) == 1)
+    assert stats is None or (stats.shape == (B, 3) and stats.is_contiguous())
+    stop = -1 if stop_token is None else int(stop_token)
+    if gen.is_cuda:
+        assert T <= SPEC_MAX_T, f"the drafter keeps at most {SPEC_MAX_T} positions of history"
+        _lib.call("nsa_spec_step", _lib.ptr(gen), gen.stride(0), T, _lib.ptr(pos), _lib.ptr(tok), _lib.ptr(done),
+                  _lib.ptr(end), _lib.ptr(cand), _lib.ptr(stok), _lib.ptr(spos), _lib.ptr(cpos), _lib.ptr(table),
+                  table.stride(0) if table is not None else 0, _lib.ptr(stats), B, K, N, stop, _lib.stream())
+        return
+    posv, tokv = pos.view(B), tok.view(B)
+    for b in range(B):
+        p = min(max(int(posv[b]), 0), T)
+        if cand is not None and not (done is not None and int(done.view(B)[b])):
+            limit = T if end is None else min(T, int(end.view(B)[b]))
+            if p + 1 > limit:
+                if done is not None:
+                    done.view(B)[b] = 1
+            else:
+                cap = min(K, limit - p - 1)
+                c, d = cand[b].tolist(), stok[b, 1:].tolist()
+                n = 0
+                while n < cap and d[n] == c[n]:
+                    n += 1
+                new = c[:n + 1]
+                if stop in new:
+                    new = new[:new.index(stop) + 1]
+                gen[b, p + 1:p + 1 + len(new)] = torch.tensor(new, dtype=torch.int64)
+                p += len(new)
+                posv[b] = p
+                tokv[b] = new[-1]
+                if done is not None and (new[-1] == stop or p >= limit):
+                    done.view(B)[b] = 1
+                if stats is not None:
+                    stats[b] += torch.tensor([1, cap, len(new) - 1], dtype=torch.int64)
+        if table is not None:
+            draft = [int(table[b, min(p + 1 + i, T)]) for i in range(K)]
+        else:
+            draft = _ngram_continue(gen[b, :p + 1].tolist(), p, K, N)
+        stok[b] = torch.tensor([int(tokv[b])] + draft, dtype=torch.int64)
+        spos[b] = torch.tensor([min(p + j, T - 1) for j in range(K + 1)], dtype=torch.int64)
+        if cpos is not None:
+            cpos[b] = torch.tensor([min(p + j + 1, T) for j in range(K + 1)], dtype=torch.int64)
+
+
+def ngram_draft(gen, pos, tok, K: int, N: int = 3, T: int | None = None, table=None, out=None):
+    """What a speculative step feeds: every row's token and K drafted continuations.
+
+    ``gen`` int64 [B, > T] holds the token fed at every position (``T``: the cache length,
+    default ``gen.shape[1] - 1``), ``pos`` int64 [B] the position p of the token about to be
+    fed, ``tok`` int64 [B] or [B, 1] that token.  Drafts are prompt lookup in the row's own
+    history ``gen[b, 0 .. p]``: for n = N down to 1 (n <= p) the most recent earlier occurrence
+    of the last n tokens, starting at s with s + n <= p, is continued periodically, ``draft[i] =
+    h[s + n + (i mod L)]`` with ``L = p + 1 - (s + n)`` (a loop is drafted whole); with no match at
+    any n, ``draft[i] = h[p]``.  With a draft ``table`` (int64 [B, > T]) instead ``draft[i] =
+    table[b, min(p + 1 + i, T)]``.
+
+    Returns (stok, spos, cpos), int64 [B, K + 1] each (``out``: such a triple to write into):
+    ``stok[b] = (tok[b], draft[0 .. K-1])``, the fed positions ``spos[b, j] = min(p + j, T - 1)``
+    (the clamp keeps the position-embedding gather in bounds; ``decode_attention_spec`` masks
+    such a query and ``spec_accept_`` never accepts it) and ``cpos[b, j] = min(p + j + 1, T)``,
+    the position the draw from logits row (b, j) is keyed by.  One workgroup per row on the GPU
+    (``nsa_spec_step``, graph-capturable); a Python loop elsewhere (the reference)."""
+    B = pos.numel()
+    T = gen.shape[1] - 1 if T is None else int(T)
+    stok, spos, cpos = out if out is not None else _spec_buffers(B, K, gen.device)
+    _spec_step(gen, pos, tok, None, None, None, stok, spos, cpos, table, None, K, N, T, None)
+    return stok, spos, cpos
+
+
+def spec_accept_(cand, stok, spos, cpos, gen, pos, tok, done, end=None, T: int | None = None, N: int = 3,
+                 stop_token=None, table=None, stats=None):
+    """The end of a speculative step: keep the drafts the model itself would have produced, then
+    draft for the next step (``ngram_draft`` into ``stok`` / ``spos`` / ``cpos``, same launch).
+
+    The step fed ``stok[b] = (tok[b], draft[0 .. K-1])`` at positions p .. p + K (p = ``pos[b]``)
+    and ``cand[b, j]`` (int64 [B, K + 1]) is the id drawn from logits row (b, j), for position
+    p + j + 1, with the stream the plain decoder uses there.  With ``limit = min(T, end[b])``
+    (``end``: the position of the row's last allowed token; None: T), n is the largest count with
+    ``draft[i] == cand[i]`` for all i < n, capped so that p + n + 1 <= limit; ``cand[0 .. n]`` go
+    to ``gen[b, p + 1 ..]``, cut after the first ``stop_token``; ``pos[b]`` grows by the number
+    emitted, ``tok[b]`` becomes the last emitted id and ``done[b]`` is set at the stop token or
+    at the limit.  ``stats`` (int64 [B, 3], optional) counts per row the live steps, the drafts
+    offered (the cap) and the drafts accepted (emitted - 1).  A done row changes nothing.
+
+    For a deterministic draft this accepts with probability p(draft), as rejection sampling
+    does, and what is emitted is always the model's own draw: the result is the plain decoder's
+    for any temperature / top-k / top-p / min-p."""
+    K = cand.shape[1] - 1
+    T = gen.shape[1] - 1 if T is None else int(T)
+    _spec_step(gen, pos, tok, done, end, cand, stok, spos, cpos, table, stats, K, N, T, stop_token)
+
+
 def prefix_attention(qkv, pkc, pvc, P: int, n_head: int):
     """Prefill attention of suffixes that follow one shared prefix: qkv [B, S, 3C] -> [B, S, C].
 

@@ -83,6 +83,29 @@ to the prompt's end.  The loop replays the captured step ``DONE_POLL`` times (``
 queue=True)``: the same step with the keyed sampler, a graph of its own), reads ``done`` and
 ``pos`` back once, harvests the finished rows, admits the next prompts into all freed rows in
 one pass and draws their first tokens alone (``sample_admitted``); no step waits for the host.
+``Decoder(..., speculate=K, spec_ngram=N)`` (1 <= K <= 7; implies per_row) verifies K drafted tokens
+per captured step.  A step feeds every row's token and K guessed continuations (``stok`` at the
+positions ``spos``, int64 [B, K + 1] on the device) as B (K + 1) rows through the same embedding and
+linear ops, attends with ``ops.decode_attention_spec`` (K + 1 consecutive queries of one sequence
+against one cache, bit for bit the K + 1 successive single-query calls), draws the token of every
+fed position with the stream the plain per-row decoder uses for it (the sampler's uniform is a
+counter hash of (salt, row, position): the ``row_key`` form over B (K + 1) rows, row (b, j) keyed
+(b, pos[b] + j + 1), into scratch) and ``ops.spec_accept_`` keeps a draft if and only if it equals
+that draw.  For a deterministic draft this accepts with probability p(draft), as rejection sampling
+does, and what is emitted is always the model's own draw: the tokens are the plain decoder's for
+any temperature / top-k / top-p / min-p, with no second sampler and no residual distribution.
+Drafts are n-gram lookup in the row's own history ``gen[b, 0 .. pos[b]]`` (``ops.ngram_draft``, in the
+accept kernel's launch; ``prefill`` therefore also copies the prompt ids into ``gen``), or come from
+a table (``set_draft_table``: for measuring a step at a chosen acceptance).  A row advances by what
+it accepts inside the captured graph: there is no ``advance_pos_`` and no ``pos_inc`` in such a
+step, ``run(n)`` gives every row a budget on the device (``end``), the graph key gains ``("spec", K,
+N)``, the loop looks at ``done`` every ``DONE_POLL`` replays (sooner when no row can need that many)
+and ``spec_stats`` reads the per-row counters back.  With ``quantize="int8"``, ``stop_token``,
+``top_p`` / ``min_p`` and eager mode; ``kv_quantize``, ``shared_prompt`` / ``shared_prefix``, the queue, on
+the GPU B (K + 1) > 16 and a model without the fused decode kernels raise ValueError.  Rows near the
+end of the cache have dead queries (positions >= block_size): they store nothing, come out as
+zeros and are never accepted.  With ``speculate`` unset nothing of this exists: every launch,
+graph key and result is what it was.
 The caches hold at most ``block_size`` positions; ``GPT.generate_cached`` falls
 back to the recompute loop when prompt + new tokens exceed that (nanoGPT crops the
 context there, which a cache cannot do without re-encoding).
@@ -111,6 +134,28 @@ def _check_mode(quantize, kv_quantize, shared_prompt=False, shared_prefix=False)
         raise ValueError("shared_prefix keeps bf16 caches: it cannot be combined with kv_quantize")
 
 
+def _check_spec(speculate, spec_ngram=3, kv_quantize=None, shared_prompt=False, shared_prefix=False, queue=False):
+    """(K, N) of a speculative call, validated (K = 0: none); ValueError for what speculation does not
+    compose with, never a silent plain step."""
+    K = int(speculate or 0)
+    if not K:
+        return 0, 3
+    N = 3 if spec_ngram is None else int(spec_ngram)
+    if not 1 <= K <= ops.functional.SPEC_MAX_DRAFTS:
+        raise ValueError(f"speculate must be in 1 .. {ops.functional.SPEC_MAX_DRAFTS} drafted tokens, "
+                         f"got {speculate!r}")
+    if N < 1:
+        raise ValueError(f"spec_ngram must be at least 1, got {spec_ngram!r}")
+    if kv_quantize:
+        raise ValueError("speculate keeps bf16 caches: it cannot be combined with kv_quantize")
+    if shared_prompt or shared_prefix:
+        raise ValueError("speculate decodes every row against its own cache: it cannot be combined with "
+                         "shared_prompt / shared_prefix")
+    if queue:
+        raise ValueError("speculative batches are not served as a queue: drop batch_size / per-prompt budgets")
+    return K, N
+
+
 def _stop(stop_token):
     """A stop token < 0 means none."""
     return None if stop_token is None or stop_token < 0 else stop_token
@@ -119,8 +164,11 @@ def _stop(stop_token):
 class Decoder:
     def __init__(self, model, batch_size: int, max_len: int | None = None, use_graph: bool | None = None,
                  per_row: bool = False, quantize: str | None = None, kv_quantize: str | None = None,
-                 shared_prompt: bool = False, max_new: int | None = None):
+                 shared_prompt: bool = False, max_new: int | None = None, speculate: int | None = None,
+                 spec_ngram: int = 3):
         _check_mode(quantize, kv_quantize, shared_prompt)
+        self.K, self.N = _check_spec(speculate, spec_ngram, kv_quantize, shared_prompt)
+        per_row = per_row or bool(self.K)  # a speculating row advances by its own number of positions
         if shared_prompt and batch_size < 2:
             raise ValueError(f"shared_prompt needs at least 2 rows to share a prompt, got batch size {batch_size}")
         if max_new is not None and not shared_prompt:
@@ -143,6 +191,13 @@ class Decoder:
             needs_fused("shared_prompt")
         if kv_quantize:
             needs_fused("kv_quantize='int8'")
+        if self.K:
+            needs_fused("speculate")
+            # a step runs B * (K + 1) rows through the linears: the skinny kernels' range, no larger GEMM instead
+            if on_gpu and batch_size * (self.K + 1) > ops.functional.SKINNY_MAX_ROWS:
+                raise ValueError(f"speculate={self.K} decodes at most {ops.functional.SKINNY_MAX_ROWS // (self.K + 1)} "
+                                 f"rows on the GPU ({ops.functional.SKINNY_MAX_ROWS} step rows), got batch size "
+                                 f"{batch_size}")
         if quantize:
             # the int8 kernels are the single-row and skinny ones; there is no int8 form of the
             # larger-batch GEMMs, and no silent bf16 step instead
@@ -199,6 +254,20 @@ class Decoder:
         self.key = None
         self.end = None
         self.queue_stats = {"steps": 0, "admissions": 0, "admitted": 0}
+        if self.K:
+            # a speculative step's device state: the fed tokens (the row's token and K drafts), their
+            # positions and the positions their draws are keyed by (int64 [B, K + 1] each); the draws
+            # themselves (ctok, with the sampler's per-position scratch cgen), keyed by the row (rkey);
+            # the per-row budget end and the counters (live steps, drafts offered, drafts accepted)
+            rows = batch_size * (self.K + 1)
+            self.stok, self.spos, self.cpos = (torch.zeros(batch_size, self.K + 1, device=self.device,
+                                                           dtype=torch.int64) for _ in range(3))
+            self.ctok = torch.zeros(rows, 1, device=self.device, dtype=torch.int64)
+            self.cgen = torch.zeros(rows, self.T + 1, device=self.device, dtype=torch.int64)
+            self.rkey = torch.arange(batch_size, device=self.device, dtype=torch.int64).repeat_interleave(self.K + 1)
+            self.end = torch.full((batch_size,), 2 ** 62, device=self.device, dtype=torch.int64)
+            self.spec_counts = torch.zeros(batch_size, 3, device=self.device, dtype=torch.int64)
+            self.table = None  # set_draft_table: drafts read from a table instead of the n-gram lookup
         self._admit_logits = None  # [B, V] fp32: the admitted rows' logits at their own row indices
         self.use_graph = (self.device.type == "cuda") if use_graph is None else use_graph
         if self.use_graph and not self.graph_capable(model):
@@ -233,12 +302,15 @@ class Decoder:
                 and cfg.vocab_size <= 53248)
 
     def fits(self, batch_size, per_row=False, quantize=None, kv_quantize=None, shared_prompt=False,
-             max_new=None) -> bool:
+             max_new=None, speculate=None, spec_ngram=3) -> bool:
         """Whether a call that needs ``Decoder(model, batch_size, per_row=..., ...)`` can run on this
-        one: the same rows and form, and (shared) row caches of at least ``max_new`` slots."""
-        return (self.B == batch_size and self.per_row == bool(per_row) and self.quantize == quantize
+        one: the same rows and form, (shared) row caches of at least ``max_new`` slots, and the same
+        number of drafted tokens and n-gram length (speculative)."""
+        K = int(speculate or 0)
+        return (self.B == batch_size and self.per_row == bool(per_row or K) and self.quantize == quantize
                 and self.kv_quantize == kv_quantize and self.shared == bool(shared_prompt)
-                and (not self.shared or self.R >= (max_new or self.T)))
+                and (not self.shared or self.R >= (max_new or self.T))
+                and self.K == K and (not K or self.N == int(spec_ngram)))
 
     def _quantize_weights(self):
         """int8 mode: quantize every linear weight and the tied lm_head / wte table, and point
@@ -357,6 +429,79 @@ class Decoder:
             ops.advance_pos_(self.pos, self.done)  # unfinished rows move on, finished rows stay
         return logits  # pos has advanced (by the head kernel itself on the fused path)
 
+    def _spec_layers(self):
+        """A speculative step's model pass: the B * (K + 1) fed tokens ``stok`` at the positions ``spos``
+        through the same embedding and linear ops as ``_decode_layers`` (row-generic: the skinny
+        kernels on the GPU), with ``ops.decode_attention_spec`` in place of the single-query attention
+        -> fp32 logits [B * (K + 1), V], row (b, j) for position ``pos[b] + j + 1``.  ``pos`` does not move
+        here: ``ops.spec_accept_`` advances every row by what it keeps."""
+        tr = self.model.transformer
+        W = self._w
+        B, S = self.B, self.K + 1
+        rows = B * S
+        branch = None
+        for i, block in enumerate(tr.h):
+            attn, mlp = block.attn, block.mlp
+            ln1, ln2 = block.ln_1, block.ln_2
+            if i == 0:
+                x, qkv = ops.decode_embed_linear_ln(self.stok.view(rows, 1), self.spos.view(rows), tr.wte.weight,
+                                                    tr.wpe.weight, ln1.weight, ln1.bias, W(attn.c_attn.weight),
+                                                    attn.c_attn.bias, dtype=self.dtype, res_dtype=self.rdtype,
+                                                    out_dtype=ln1.out_dtype)
+            else:
+                x, qkv = ops.decode_linear_ln(x, branch, ln1.weight, ln1.bias, W(attn.c_attn.weight), attn.c_attn.bias,
+                                              out_dtype=ln1.out_dtype)
+            y = ops.decode_attention_spec(qkv.view(B, S, -1), self.kc[i], self.vc[i], self.pos, attn.n_head)
+            y = ops.decode_linear(y.view(rows, 1, -1), W(attn.c_proj.weight), attn.c_proj.bias)
+            x, u = ops.decode_linear_ln(x, y, ln2.weight, ln2.bias, W(mlp.c_fc.weight), mlp.c_fc.bias, gelu=True,
+                                        out_dtype=ln2.out_dtype)
+            branch = ops.decode_linear(u, W(mlp.c_proj.weight), mlp.c_proj.bias)
+        lnf = tr.ln_f
+        _, logits = ops.decode_linear_ln(x, branch, lnf.weight, lnf.bias, W(self.model.lm_head.weight), None,
+                                         out_f32=True, out_dtype=lnf.out_dtype)
+        return logits[:, 0]
+
+    def _spec_step_impl(self, temperature, top_k, stop_token=None, top_p=None, min_p=None):
+        """One speculative step: the model pass over every row's token and its K drafts, one draw per
+        fed position with the stream the plain per-row decoder uses for it (row (b, j) hashes (b,
+        pos[b] + j + 1): the sampler's ``row_key`` form over B * (K + 1) rows, into scratch), then
+        ``ops.spec_accept_``: the drafts that equal their draws are kept, ``pos`` / ``tok`` / ``gen`` /
+        ``done`` move on and the next step's drafts are made.  No ``advance_pos_`` and no ``pos_inc``."""
+        logits = self._spec_layers()
+        ops.sample_topk_(logits, temperature, top_k, self.salt, self.cpos.view(-1), self.ctok, self.cgen,
+                         salt_dev=self.salt_dev, top_p=top_p, min_p=min_p, row_key=self.rkey)
+        ops.spec_accept_(self.ctok.view(self.B, self.K + 1), self.stok, self.spos, self.cpos, self.gen, self.pos,
+                         self.tok, self.done, self.end, T=self.T, N=self.N, stop_token=stop_token, table=self.table,
+                         stats=self.spec_counts)
+
+    def set_draft_table(self, table=None):
+        """Draft from a table instead of the n-gram lookup: ``table`` (int64 [B, n] or a list of 1-D
+        tensors, n <= block_size + 1) holds a guessed token for every position, the draft for position q
+        being ``table[b, q]`` (positions past n: id 0).  None: back to the n-gram drafts.  For
+        measuring a step at a chosen acceptance (``scripts/decode_bench.py --spec_table``) and for
+        the tests: whatever the table says, the result is the plain decoder's."""
+        assert self.K, "a draft table needs Decoder(..., speculate=K)"
+        if table is None:
+            self.table = None
+            return
+        if self.table is None:
+            self.table = getattr(self, "_table_buf", None)
+            if self.table is None:  # one buffer for the decoder's life: a captured step reads it
+                self.table = self._table_buf = torch.zeros(self.B, self.T + 1, device=self.device, dtype=torch.int64)
+        self.table.zero_()
+        for b in range(self.B):
+            row = table[b].view(-1)[:self.T + 1].to(self.device)
+            self.table[b, :row.numel()] = row
+
+    @property
+    def spec_stats(self) -> dict:
+        """The speculative counters since the last ``prefill``, per row: live ``steps``, drafts
+        ``offered`` (per step the K drafts, or as many as the row's budget left room for) and drafts
+        ``accepted``; a row's new tokens are 1 (the prefill's draw) + steps + accepted."""
+        assert self.K, "spec_stats needs Decoder(..., speculate=K)"
+        steps, offered, accepted = self.spec_counts.t().tolist()
+        return {"steps": steps, "offered": offered, "accepted": accepted}
+
     def _encode(self, idx, first=0, rows=None, kc=None, vc=None):
         """``idx`` [n, S], its tokens at positions first .. first + S - 1, through the embedding and
         ``_prefill_layers`` (``first`` > 0: the suffixes of the cached prefix of that length) -> ln_f(x)."""
@@ -409,6 +554,9 @@ class Decoder:
         B, T0 = idx.shape
         assert not self.shared, "a shared_prompt decoder encodes its one prompt with prefill_shared"
         assert B == self.B and 1 <= T0 <= self.T
+        if self.K:  # the drafter looks the row's own history up, prompt included
+            self.gen[:, :T0] = idx
+            self.spec_counts.zero_()
         return self._prefill(idx, 0, lengths)
 
     @torch.no_grad()
@@ -541,6 +689,8 @@ class Decoder:
         1`` (``end``).  ``queue_stats``: ``steps`` run, ``admissions`` (admit calls) and requests
         ``admitted``."""
         assert self.per_row, "serve needs Decoder(..., per_row=True)"
+        if self.K:
+            raise ValueError("a speculative decoder does not serve a queue")
         stop_token = _stop(stop_token)
         top_p, min_p = sampling_filters(top_p, min_p)
         nreq = len(prompts)
@@ -630,6 +780,8 @@ class Decoder:
         tok = self.tok.clone()
         if self.per_row:  # a warm-up draw may hit the stop token: positions and flags are put back
             pos, done = self.pos.clone(), self.done.clone()
+        # a speculative warm-up step also accepts and drafts: its fed tokens and counters are put back too
+        spec = [(t, t.clone()) for t in (self.stok, self.spos, self.cpos, self.spec_counts)] if self.K else []
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
@@ -641,6 +793,8 @@ class Decoder:
                 else:
                     self.pos.sub_(1)
                 self.tok.copy_(tok)
+                for t, saved in spec:
+                    t.copy_(saved)
         torch.cuda.current_stream().wait_stream(side)
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):  # recorded, not executed: pos is unchanged
@@ -687,6 +841,10 @@ class Decoder:
         stop_token = _stop(stop_token)
         assert stop_token is None or self.per_row, "a stop token needs Decoder(..., per_row=True)"
         top_p, min_p = sampling_filters(top_p, min_p)
+        if self.K:
+            if queue:
+                raise ValueError("a speculative decoder does not serve a queue")
+            return self._run_spec(n, temperature, top_k, stop_token, top_p, min_p)
         step = lambda: self._step_sample_impl(temperature, top_k, stop_token, top_p, min_p, queue)  # noqa: E731
         if self.use_graph:
             key = (float(temperature), top_k, stop_token) if self.per_row else (float(temperature), top_k)
@@ -703,6 +861,39 @@ class Decoder:
                 break
             step()
             ran += 1
+        if self.use_graph:
+            self.replays += ran
+
+    def _run_spec(self, n, temperature, top_k, stop_token, top_p, min_p):
+        """``run`` on a speculative decoder: every unfinished row gets n more tokens (``end`` = its
+        position + n), the first drafts are made, and the step (``_spec_step_impl``, captured once per
+        sampling key with ``("spec", K, N)`` added) is replayed until every row is done, looked for
+        every ``DONE_POLL`` replays: at most n of them, since a live step emits at least one token."""
+        if n <= 0:
+            return
+        self.end.copy_(torch.clamp(self.pos + n, max=self.T))
+        ops.ngram_draft(self.gen, self.pos, self.tok, self.K, self.N, self.T, self.table,
+                        out=(self.stok, self.spos, self.cpos))
+        step = lambda: self._spec_step_impl(temperature, top_k, stop_token, top_p, min_p)  # noqa: E731
+        if self.use_graph:
+            key = (float(temperature), top_k, stop_token)
+            if top_p is not None or min_p is not None:
+                key += (top_p, min_p)
+            key += ("spec", self.K, self.N) + (("table",) if self.table is not None else ())
+            if key not in self.sgraphs:
+                self.sgraphs[key], _ = self._capture(step)
+            step = self.sgraphs[key].replay
+        # between two host looks: DONE_POLL replays, or fewer when the rows cannot need that many (a row
+        # that is ``left`` tokens short needs at least ceil(left / (K + 1)) more steps), so the tail of a
+        # well-drafted run is not padded with idle replays
+        ran, left = 0, n
+        while left > 0 and ran < n:
+            k = min(self.DONE_POLL, -(-left // (self.K + 1)), n - ran)
+            for _ in range(k):
+                step()
+            ran += k
+            done, pos, end = torch.stack([self.done, self.pos, self.end]).tolist()  # the one host look per poll
+            left = max([e - p for d, p, e in zip(done, pos, end) if not d], default=0)
         if self.use_graph:
             self.replays += ran
 
@@ -740,12 +931,16 @@ def sample_next(logits: torch.Tensor, temperature: float = 1.0, top_k: int | Non
     return torch.multinomial(probs, num_samples=1, generator=generator)
 
 
-def _mode(B, per_row=False, quantize=None, kv_quantize=None, slots=None) -> dict:
+def _mode(B, per_row=False, quantize=None, kv_quantize=None, slots=None, spec=(0, 3)) -> dict:
     """The decoder a call needs, as ``Decoder``'s arguments (and ``Decoder.fits``'s): B rows, per_row
-    or not, the two quantizations and ``slots``, the row-cache slots of a shared_prompt decoder
-    (None: an unshared one)."""
-    return dict(batch_size=B, per_row=per_row, quantize=quantize, kv_quantize=kv_quantize,
+    or not, the two quantizations, ``slots``, the row-cache slots of a shared_prompt decoder
+    (None: an unshared one), and ``spec``, the (K, N) of ``_check_spec`` (K > 0: a speculative
+    one, which is per_row)."""
+    mode = dict(batch_size=B, per_row=per_row, quantize=quantize, kv_quantize=kv_quantize,
                 shared_prompt=slots is not None, max_new=slots)
+    if spec[0]:
+        mode.update(per_row=True, speculate=spec[0], spec_ngram=spec[1])
+    return mode
 
 
 def _build(model, mode, use_graph=None):
@@ -772,11 +967,12 @@ def _nothing_to_share(sharing, L, N, T):
                       "and the recompute loop has nothing to share")
 
 
-def _cached_mode(model, idx, max_new_tokens, quantize, kv_quantize, shared_prompt):
+def _cached_mode(model, idx, max_new_tokens, quantize, kv_quantize, shared_prompt, speculate=None, spec_ngram=3):
     """The mode of the decoder ``generate_cached`` runs this call on (None: the recompute loop)."""
     B, T0 = idx.shape
     T = model.config.block_size
     _check_mode(quantize, kv_quantize, shared_prompt)
+    spec = _check_spec(speculate, spec_ngram, kv_quantize, shared_prompt)
     if shared_prompt:
         if not bool((idx == idx[:1]).all()):
             raise ValueError("shared_prompt needs every row of idx to be the same prompt")
@@ -791,17 +987,23 @@ def _cached_mode(model, idx, max_new_tokens, quantize, kv_quantize, shared_promp
         if kv_quantize:
             raise ValueError("kv_quantize needs the KV-cache path: prompt + new tokens exceed block_size, and the "
                              "recompute loop has no cache to quantize")
+        if spec[0]:
+            raise ValueError("speculate needs the KV-cache path: prompt + new tokens exceed block_size, and the "
+                             "recompute loop decodes one token per pass")
         return None
-    return _mode(B, False, quantize, kv_quantize)
+    return _mode(B, False, quantize, kv_quantize, spec=spec)
 
 
-def cached_decoder(model, idx, max_new_tokens, use_graph=None, quantize=None, kv_quantize=None, shared_prompt=False):
+def cached_decoder(model, idx, max_new_tokens, use_graph=None, quantize=None, kv_quantize=None, shared_prompt=False,
+                   speculate=None, spec_ngram=3):
     """The Decoder this ``generate_cached`` call would build, for a caller that keeps it across
     calls (``decoder=``) and releases it.  A call that runs on none (no new tokens, or the
     recompute loop) gets the ordinary one all the same, as ``sample.py`` always has: building it
     draws from torch's generator, and a seeded run keeps its tokens."""
-    mode = max_new_tokens > 0 and _cached_mode(model, idx, max_new_tokens, quantize, kv_quantize, shared_prompt)
-    return _build(model, mode or _mode(idx.shape[0], False, quantize, kv_quantize), use_graph)
+    mode = max_new_tokens > 0 and _cached_mode(model, idx, max_new_tokens, quantize, kv_quantize, shared_prompt,
+                                               speculate, spec_ngram)
+    return _build(model, mode or _mode(idx.shape[0], False, quantize, kv_quantize,
+                                       spec=_check_spec(speculate, spec_ngram, kv_quantize)), use_graph)
 
 
 @torch.no_grad()
@@ -809,8 +1011,18 @@ def generate_cached(model, idx: torch.Tensor, max_new_tokens: int, temperature: 
                     top_k: int | None = None, use_graph: bool | None = None,
                     decoder: "Decoder | None" = None, top_p: float | None = None,
                     min_p: float | None = None, quantize: str | None = None,
-                    kv_quantize: str | None = None, shared_prompt: bool = False) -> torch.Tensor:
+                    kv_quantize: str | None = None, shared_prompt: bool = False,
+                    speculate: int | None = None, spec_ngram: int = 3, spec_table=None) -> torch.Tensor:
     """``model.generate`` with KV caches: same sampling, one token's forward per new token.
+
+    ``speculate=K`` (1 .. 7): speculative decoding (``Decoder(..., speculate=K, spec_ngram=N)``). A
+    step feeds every row's token and K continuations guessed by n-gram lookup in the row's own
+    history, draws the token of every fed position with the stream the plain decoder uses for it
+    and keeps the drafts that equal their draws: up to K + 1 tokens per model pass, and the same
+    tokens as without it.  ``spec_table`` ([B, n] ids by position) drafts from a table instead
+    (``Decoder.set_draft_table``).  ValueError with ``kv_quantize``, ``shared_prompt``, prompt + new
+    tokens past block_size and, on the GPU, B * (K + 1) > 16 or a model without the fused decode
+    kernels.
 
     ``shared_prompt=True``: the rows of ``idx`` are one prompt (unequal rows raise ValueError)
     whose K / V are cached once for the batch (``Decoder(..., shared_prompt=True)``); a single
@@ -830,11 +1042,13 @@ def generate_cached(model, idx: torch.Tensor, max_new_tokens: int, temperature: 
     top_p, min_p = sampling_filters(top_p, min_p)
     if max_new_tokens <= 0:
         return idx
-    mode = _cached_mode(model, idx, max_new_tokens, quantize, kv_quantize, shared_prompt)
+    mode = _cached_mode(model, idx, max_new_tokens, quantize, kv_quantize, shared_prompt, speculate, spec_ngram)
     if mode is None:
         # the caches hold block_size positions; nanoGPT crops the context beyond that
         return model.generate(idx, max_new_tokens, temperature=temperature, top_k=top_k, top_p=top_p, min_p=min_p)
     with _borrow(model, mode, decoder, use_graph) as dec:
+        if dec.K:
+            dec.set_draft_table(spec_table)
         logits = dec.prefill_shared(idx[0]) if dec.shared else dec.prefill(idx)
         dec.sample_into(logits, temperature, top_k, None, top_p, min_p)  # pos = T0: gen[:, T0]
         dec.run(max_new_tokens - 1, temperature, top_k, None, top_p, min_p)
@@ -870,7 +1084,8 @@ def common_prefix_len(prompts) -> int:
     return int(same.long().cumprod(0).sum())
 
 
-def _batch_plan(model, prompts, max_new_tokens, quantize, kv_quantize, shared_prompt, shared_prefix, batch_size):
+def _batch_plan(model, prompts, max_new_tokens, quantize, kv_quantize, shared_prompt, shared_prefix, batch_size,
+                speculate=None, spec_ngram=3):
     """What ``generate_batch`` does with a call -> (prompts, budgets, queue, fit, P, mode): the
     flattened prompts on the model's device, every prompt's budget of new tokens, whether they are
     served as a queue, the indices of the prompts that share the decoder (the others go alone), the
@@ -889,6 +1104,7 @@ def _batch_plan(model, prompts, max_new_tokens, quantize, kv_quantize, shared_pr
             if any(n < 1 for n in budgets):
                 raise ValueError(f"every budget must be at least 1, got {budgets}")
     _check_mode(quantize, kv_quantize, shared_prompt, shared_prefix)
+    spec = _check_spec(speculate, spec_ngram, kv_quantize, shared_prompt, shared_prefix, queue)
     assert all(p.numel() >= 1 for p in prompts), "every prompt needs at least one token"
     device = model.lm_head.weight.device
     prompts = [p.view(-1).to(device) for p in prompts]
@@ -916,18 +1132,20 @@ def _batch_plan(model, prompts, max_new_tokens, quantize, kv_quantize, shared_pr
     if sharing and B >= 2:  # a single row goes the ordinary way
         # a row's cache holds what follows the shared tokens: its suffix, if any, and its new tokens
         slots = max(budgets[i] + (prompts[i].numel() - P if P else 0) for i in fit)
-    return prompts, budgets, queue, fit, P, _mode(B, True, quantize, kv_quantize, slots)
+    return prompts, budgets, queue, fit, P, _mode(B, True, quantize, kv_quantize, slots, spec)
 
 
 def batch_decoder(model, prompts, max_new_tokens, use_graph=None, quantize=None, kv_quantize=None,
-                  shared_prompt=False, shared_prefix=False, batch_size=None):
+                  shared_prompt=False, shared_prefix=False, batch_size=None, speculate=None, spec_ngram=3):
     """The Decoder this ``generate_batch`` call would build, for a caller that keeps it across
     calls (``decoder=``; a shared one then keeps the prompt or prefix too) and releases it.  A call
     that shares none (no new tokens, or no prompt that fits the cache) gets the ordinary one of a
     row per prompt, for the reason ``cached_decoder`` gives."""
-    plan = _batch_plan(model, prompts, max_new_tokens, quantize, kv_quantize, shared_prompt, shared_prefix, batch_size)
+    plan = _batch_plan(model, prompts, max_new_tokens, quantize, kv_quantize, shared_prompt, shared_prefix, batch_size,
+                       speculate, spec_ngram)
     mode = plan and plan[-1]
-    return _build(model, mode or _mode(len(prompts), True, quantize, kv_quantize), use_graph)
+    return _build(model, mode or _mode(len(prompts), True, quantize, kv_quantize,
+                                       spec=_check_spec(speculate, spec_ngram, kv_quantize)), use_graph)
 
 
 @torch.no_grad()
@@ -936,8 +1154,15 @@ def generate_batch(model, prompts, max_new_tokens, temperature: float = 1.0, top
                    decoder: "Decoder | None" = None, top_p: float | None = None,
                    min_p: float | None = None, quantize: str | None = None,
                    kv_quantize: str | None = None, shared_prompt: bool = False,
-                   shared_prefix: bool = False, batch_size: int | None = None) -> list[torch.Tensor]:
+                   shared_prefix: bool = False, batch_size: int | None = None, speculate: int | None = None,
+                   spec_ngram: int = 3, spec_table=None) -> list[torch.Tensor]:
     """Generate for a list of prompts of unequal lengths as one batch.
+
+    ``speculate=K`` / ``spec_ngram=N`` / ``spec_table``: speculative decoding, as in
+    ``generate_cached`` (``spec_table``: one 1-D tensor of ids by position per prompt); every row
+    advances by what it accepts, and the results are those of the call without it.  ValueError with
+    ``kv_quantize``, ``shared_prompt``, ``shared_prefix`` and a queue (``batch_size`` / per-prompt
+    budgets); a row that does not fit the cache goes alone, speculating too.
 
     ``prompts``: 1-D token tensors, each of length >= 1.  Every result is its prompt followed
     by the new tokens: up to and including the first ``stop_token`` if the row drew it,
@@ -985,7 +1210,8 @@ def generate_batch(model, prompts, max_new_tokens, temperature: float = 1.0, top
     ``generate_cached`` (``quantize`` / ``kv_quantize`` / ``shared_prompt``: ValueError).
     ``shared_prefix=True``, ``batch_size < 1`` and a budget list of the wrong length or with an
     entry < 1 raise ValueError.  With ``batch_size=None`` and an int budget nothing changes."""
-    plan = _batch_plan(model, prompts, max_new_tokens, quantize, kv_quantize, shared_prompt, shared_prefix, batch_size)
+    plan = _batch_plan(model, prompts, max_new_tokens, quantize, kv_quantize, shared_prompt, shared_prefix, batch_size,
+                       speculate, spec_ngram)
     stop_token = _stop(stop_token)
     sampling = (temperature, top_k, stop_token, *sampling_filters(top_p, min_p))
     if plan is None:
@@ -995,7 +1221,9 @@ def generate_batch(model, prompts, max_new_tokens, temperature: float = 1.0, top
     for i, p in enumerate(prompts):
         if i not in fit:  # alone through ``generate_cached``: the recompute loop, or a decoder of its own
             y = generate_cached(model, p[None], budgets[i], temperature=temperature, top_k=top_k, use_graph=use_graph,
-                                top_p=top_p, min_p=min_p, quantize=quantize, kv_quantize=kv_quantize)[0]
+                                top_p=top_p, min_p=min_p, quantize=quantize, kv_quantize=kv_quantize,
+                                speculate=speculate, spec_ngram=spec_ngram,
+                                spec_table=None if spec_table is None else [spec_table[i]])[0]
             outs[i] = _result(p, y[p.numel():], stop_token)
     if not fit:
         return outs
@@ -1009,6 +1237,8 @@ def generate_batch(model, prompts, max_new_tokens, temperature: float = 1.0, top
             elif dec.shared:
                 logits = dec.prefill_shared(prompts[0])
             else:
+                if dec.K:
+                    dec.set_draft_table(None if spec_table is None else [spec_table[i] for i in fit])
                 logits = dec.prefill(*_right_pad([prompts[i] for i in fit], dec.device))
             dec.sample_into(logits, *sampling)  # gen[b, its prompt's length]
             dec.run(max_new_tokens - 1, *sampling)

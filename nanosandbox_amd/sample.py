@@ -28,6 +28,12 @@ requests (``num_samples`` rounds of the prompts file, or ``num_samples`` copies 
 queue through N decoder rows, a finished row taking the next request (``Decoder.serve``), and prints
 the results in request order; it needs the KV-cache path, refuses ``--shared_prefix`` and composes
 with ``--shared_prompt``, ``--quantize``, ``--kv_quantize`` and ``--stop_token``.
+``--speculate=K`` (1 .. 7) decodes speculatively: every model pass feeds a row's token and K
+continuations guessed by ``--spec_ngram=N``-gram lookup in the row's own text and keeps those the
+model itself draws (``Decoder(speculate=K)``): the same samples for the same seed, up to K + 1
+tokens per pass.  It needs the KV-cache path, refuses ``--kv_quantize``, ``--shared_prompt``,
+``--shared_prefix`` and ``--serve_batch`` and composes with ``--quantize``, ``--stop_token``,
+``--top_p`` / ``--min_p``, ``--sample_batch`` and ``--prompts_file`` (rows * (K + 1) <= 16 on the GPU).
 """
 
 from __future__ import annotations
@@ -67,6 +73,8 @@ SAMPLE_DEFAULTS = dict(
     shared_prompt=False,  # sample_batch > 1: encode and cache the prompt once for the batch (Decoder(shared_prompt=True))
     shared_prefix=False,  # prompts_file / sample_batch > 1: encode and cache the prompts' common prefix once for the batch
     serve_batch=0,  # N > 0: all requests as one queue through N decoder rows, finished rows refilled (Decoder.serve); 0: off
+    speculate=0,  # K > 0: speculative decoding, K tokens drafted per model pass (Decoder(speculate=K)); 0: off
+    spec_ngram=3,  # speculate: the longest n-gram looked up in the row's own text for a draft
 )
 
 
@@ -118,6 +126,8 @@ def _generate_batches(model, c, encode, decode, start, device):
                 from .runtime.decode import batch_decoder
                 B = len(prompts)
                 mode = dict(quantize=quantize, kv_quantize=kv_quantize, shared_prompt=shared, shared_prefix=prefix)
+                if c["speculate"]:
+                    mode.update(speculate=c["speculate"], spec_ngram=c["spec_ngram"])
                 if B not in decs:  # a shared prompt / prefix stays cached in it: later rounds do not encode it again
                     decs[B] = batch_decoder(model, prompts, c["max_new_tokens"], **mode)
                 ys = model.generate_batch(prompts, c["max_new_tokens"], temperature=c["temperature"], top_k=c["top_k"],
@@ -202,6 +212,14 @@ def main(argv=None):
         if c["shared_prefix"]:
             raise ValueError("--serve_batch cannot admit suffixes against a shared prefix yet: it cannot be combined "
                              "with --shared_prefix")
+    if c["speculate"]:
+        from .runtime.decode import _check_spec
+        _check_spec(c["speculate"], c["spec_ngram"], c["kv_quantize"], c["shared_prompt"], c["shared_prefix"],
+                    bool(c["serve_batch"]))
+        if not c["kv_cache"]:
+            raise ValueError("--speculate needs the KV-cache path: the recompute loop (--kv_cache=False) decodes one "
+                             "token per pass")
+    spec = dict(speculate=c["speculate"], spec_ngram=c["spec_ngram"]) if c["speculate"] else {}
     quantize = c["quantize"] or None
     kv_quantize = c["kv_quantize"] or None
     torch.manual_seed(c["seed"])
@@ -238,14 +256,14 @@ def main(argv=None):
         # one decoder for all samples: weight shadows and the captured step graph are
         # built once, not per sample
         from .runtime.decode import cached_decoder
-        dec = cached_decoder(model, x, c["max_new_tokens"], quantize=quantize, kv_quantize=kv_quantize)
+        dec = cached_decoder(model, x, c["max_new_tokens"], quantize=quantize, kv_quantize=kv_quantize, **spec)
     try:
         with torch.no_grad():
             for _ in range(c["num_samples"]):
                 if dec is not None:
                     y = model.generate_cached(x, c["max_new_tokens"], temperature=c["temperature"], top_k=c["top_k"],
                                               decoder=dec, top_p=c["top_p"], min_p=c["min_p"], quantize=quantize,
-                                              kv_quantize=kv_quantize)
+                                              kv_quantize=kv_quantize, **spec)
                 else:
                     y = model.generate(x, c["max_new_tokens"], temperature=c["temperature"], top_k=c["top_k"],
                                        top_p=c["top_p"], min_p=c["min_p"])

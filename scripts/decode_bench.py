@@ -44,6 +44,13 @@ budget), then as one queue (``generate_batch(batch_size=B)``: ``Decoder.serve``)
 the useful tokens/s (sum of budgets / wall time), the steps, the admissions, the share of the
 stream's time between the start of an ``admit`` and the end of the first-token draw that follows
 it (device events, no extra syncs), and the calibration GEMM.
+``--speculate K[,K ...]`` adds ``rows_specK`` after ``rows`` (and ``rows_int8_specK`` after
+``rows_int8``): the same settings on a ``Decoder(speculate=K)`` with n-gram drafts (``--spec_ngram``).
+``--spec_table right|wrong`` (comma-separated for both) adds ``rows_specK_right`` / ``_wrong``: drafts
+read from a table holding the tokens the run will draw (every draft accepted: the ceiling) or those
+tokens + 1 (none accepted: the cost of the wider step, the floor); the table comes from an untimed
+pass with the same sampling stream.  These lines carry the live ``steps`` per row, the drafts
+``accepted`` / ``offered`` and their ratio.
 """
 
 import argparse
@@ -110,6 +117,32 @@ def run_rows(model, idx, new, lengths=None, quantize=None, kv_quantize=None, sha
     dt = time.perf_counter() - t0
     dec.release()
     return dt, ttft
+
+
+def run_spec(model, idx, new, K, ngram, table=None, quantize=None):
+    """The graph mode on a speculative decoder.  table: None (n-gram drafts), "right" or "wrong".
+    Returns (seconds of the timed steps, the decoder's spec_stats for them)."""
+    B = idx.shape[0]
+    dec = Decoder(model, B, use_graph=True, speculate=K, spec_ngram=ngram, quantize=quantize)
+
+    def go(n):  # the sampling stream is the decoder's, the same in every pass
+        dec.sample_into(dec.prefill(idx), 0.8, **SMP)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        dec.run(n, 0.8, **SMP)
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+
+    go(4)  # capture outside the timed loop
+    if table:
+        go(new)
+        y = dec.gen.clone()  # what the timed pass will draw, by position
+        dec.set_draft_table(y if table == "right" else (y + 1) % model.config.vocab_size)
+        go(4)
+    dt = go(new)
+    stats = dec.spec_stats
+    dec.release()
+    return dt, stats
 
 
 def suffix_lengths(B, n):
@@ -267,6 +300,10 @@ def main():
                          "queue through B refilled rows (queue_serve); with --shared_prompt their _shared twins")
     ap.add_argument("--budgets", default="16:256", help="--queue: new tokens per request, uniform in LO:HI")
     ap.add_argument("--memory", action="store_true", help="add each run's peak allocated bytes (decoder_peak_mb)")
+    ap.add_argument("--speculate", default="", help="K[,K ...]: add speculative twins of the rows modes (rows_specK)")
+    ap.add_argument("--spec_ngram", type=int, default=3, help="--speculate: the longest n-gram looked up")
+    ap.add_argument("--spec_table", default="", help="right, wrong or both: add table-drafted twins "
+                                                     "(rows_specK_right: all accepted, rows_specK_wrong: none)")
     ap.add_argument("--top_k", type=int, default=200, help="0: no top-k")
     ap.add_argument("--top_p", type=float, default=1.0, help="nucleus mass; 1.0: off")
     ap.add_argument("--min_p", type=float, default=0.0, help="floor relative to the most likely token; 0.0: off")
@@ -287,6 +324,10 @@ def main():
         modes = [t for m in modes for t in ([m, f"{m}_kv8"] if m.partition("_")[0] in ("graph", "rows") else [m])]
     if a.shared_prompt:  # each shared twin right after its rows mode (bf16 caches only)
         modes = [t for m in modes for t in ([m, f"{m}_shared"] if m in ("rows", "rows_int8") else [m])]
+    if a.speculate:  # the speculative twins right after their rows mode (bf16 caches only)
+        twins = [f"spec{int(k)}" + t for k in a.speculate.split(",")
+                 for t in [""] + ["_" + x for x in a.spec_table.split(",") if x]]
+        modes = [t for m in modes for t in ([m] + [f"{m}_{x}" for x in twins] if m in ("rows", "rows_int8") else [m])]
     if a.shared_prefix:
         modes = ["prefix_rows", "prefix_shared"]
     block_size = GPTConfig().block_size
@@ -327,6 +368,7 @@ def main():
                     qz = "int8" if "int8" in sfx else None
                     kvq = "int8" if "kv8" in sfx else None
                     ttft = {}
+                    spec = next((int(x[4:]) for x in sfx if x.startswith("spec")), 0)
                     if a.memory:
                         torch.cuda.synchronize()
                         torch.cuda.reset_peak_memory_stats()
@@ -340,6 +382,12 @@ def main():
                         ttft = {"ttft_ms": round(t1 * 1e3, 3), "suffix": a.suffix}
                         if t2 is not None:
                             ttft["ttft_cached_ms"] = round(t2 * 1e3, 3)
+                    elif spec:
+                        n = a.new
+                        table = next((x for x in sfx if x in ("right", "wrong")), None)
+                        dt, st = run_spec(model, idx, n, spec, a.spec_ngram, table, qz)
+                        ttft = {"steps": st["steps"], "accepted": sum(st["accepted"]), "offered": sum(st["offered"]),
+                                "acceptance": round(sum(st["accepted"]) / max(1, sum(st["offered"])), 4)}
                     elif base in ("rows", "ragged"):
                         n = a.new
                         lens = ragged_lengths(B, a.prompt) if base == "ragged" else None
