@@ -57,6 +57,26 @@
 // whatever row it is served, and a row that writes its id at a position >= end[b] sets done[b]
 // where the stop token sets it; both are read once, the end position by the writing thread alone.
 //
+// PEN = true is the penalised sampler (nsa_sample_penalized; the REQ parameters always present,
+// so four more instantiations).  A row's counts (int32, how often every id occurs in the row's
+// text) are loaded beside its logits, int4 beside float4 with the same clamped index and live
+// mask, and the key is formed from penalize(logit, count): the repetition, frequency and presence
+// penalties of ops.penalize_logits, bit for bit.  Everything after the load works on the keys, so
+// the row maximum, the thresholds, the masses and the draw all see the penalised row, the stats'
+// smallest kept logit is a penalised one, and the wide path's last-resort re-read penalises again.
+// The loads go in two groups of 7 and 6 vectors (in_groups / count_fence): 13 count vectors
+// beside 13 logit vectors do not fit the 128 VGPRs of a 1024-thread block, and left alone the
+// scheduler serialises the 26 loads two at a time to stay below them.  The thread that writes
+// the drawn id adds 1 to counts[b, id] with a plain load and store: the row's block is the
+// table row's only writer and every load of it lies before the first barrier.  A skipped row
+// (done[b] != 0) reads and writes none of it.  kernel-resource-usage of the four, VGPRs / VGPR
+// spills / SGPR spills / LDS bytes: VEC4 FILT 128 / 14 / 86 / 53700, scalar FILT 128 / 21 / 90 /
+// 53700, VEC4 top-k 125 / 0 / 42 / 41220, scalar top-k 109 / 0 / 42 / 41220 (waves per EU capped
+// at 4, what a 1024-thread block occupies anyway, for these four alone).  The eight instantiations
+// above compile to the instructions they compiled to before the PEN parameters existed (the
+// assembly differs in the symbol name and the kernarg size, 120 -> 144 bytes, only), with the
+// figures listed above.
+//
 // The chosen id is written to tok[b] and gen[b, pos] (pos = *pos, or pos[b] in the per-row
 // form, where a row whose done[b] is set is skipped and a row that draws stop_token sets
 // it).  stats (int32 [B, 2], may be NULL): the row's kept count and the bits of its
@@ -210,6 +230,7 @@ __device__ uint32_t block_kth_largest(const uint32_t* a, int npad, int k, uint32
 }
 
 constexpr int SMP_MAXC = 52;  // logits per thread kept in registers (V <= 53248: the GPT-2 vocab is 50304)
+constexpr int SMP_PEN_GROUP = 7;  // penalised sampler: logit and count vectors (scalar loads: 4 times as many) in flight per group
 
 // one wave: mass and number of the candidates a[i] >= th (wgt[i] their weights; npad % 256
 // == 0, padding has weight 0 and key 0 < th): <= 64 adds per lane, then a butterfly (every
@@ -285,12 +306,48 @@ __device__ __forceinline__ float mass_exp2(float x) { return __builtin_amdgcn_ex
 
 constexpr int SMP_NUC_LO = 832, SMP_NUC_HI = 928;  // per-thread maxima >= lo0 on the nucleus-only path
 
-template <bool VEC4, bool FILT, bool REQ>
-__global__ __launch_bounds__(SMP_THREADS) void sample_kernel(
+// The repetition / frequency / presence penalties on a raw logit l of an id that occurs c times in
+// the row's text (ops.penalize_logits states the rule): four separately rounded fp32 operations,
+// a true division and no fused multiply-add (hipcc contracts by default: switched off here), so
+// the result is the torch reference's bit for bit.  Selects, no branch: the loads stay in flight.
+__device__ __forceinline__ float penalize(float l, int c, float rp, float pp, float fp) {
+#pragma clang fp contract(off)
+  const bool s = c > 0;
+  float q = l / rp;
+  asm("" : "+v"(q));  // opaque: a select on a division's result is turned into a branch around the division
+  const float r = l * rp;
+  const float x = s ? (l > 0.0f ? q : r) : l;
+  const float f = fp * (float)c;
+  const float y = x - f;
+  return y - (s ? pp : 0.0f);
+}
+
+// N loads in groups of G: a group's loads, then its uses.  use(j) starts with count_fence on the
+// count that load(j) fetched, and program order between the fences and the count loads on either
+// side of them is kept: the counts of one group are in flight together, and those of the next
+// wait until this group's keys are being formed, whatever the scheduler would like to hoist.
+template <int G, int N, typename Load, typename Use>
+__device__ __forceinline__ void in_groups(Load load, Use use) {
+#pragma unroll
+  for (int g = 0; g < (N + G - 1) / G; ++g) {
+#pragma unroll
+    for (int j = g * G; j < ((g + 1) * G < N ? (g + 1) * G : N); ++j) load(j);
+#pragma unroll
+    for (int j = g * G; j < ((g + 1) * G < N ? (g + 1) * G : N); ++j) use(j);
+  }
+}
+__device__ __forceinline__ void count_fence(int& c) { asm volatile("" : "+v"(c) : : "memory"); }
+__device__ __forceinline__ void count_fence(int4& c) {
+  asm volatile("" : "+v"(c.x), "+v"(c.y), "+v"(c.z), "+v"(c.w) : : "memory");
+}
+
+template <bool VEC4, bool FILT, bool REQ, bool PEN = false>
+__global__ __launch_bounds__(SMP_THREADS) __attribute__((amdgpu_waves_per_eu(4, PEN ? 4 : 8))) void sample_kernel(
     const float* __restrict__ logits, int V, int ld, float scale_log2, int top_k, float top_p, float min_p,
     uint64_t salt, const uint64_t* __restrict__ salt_dev, const int64_t* __restrict__ pos, int pos_stride,
     int64_t* __restrict__ tok, int64_t* __restrict__ gen, int gen_ld, int stop_token, int64_t* done,
-    int32_t* __restrict__ stats, const int64_t* __restrict__ row_key, const int64_t* __restrict__ end) {
+    int32_t* __restrict__ stats, const int64_t* __restrict__ row_key, const int64_t* __restrict__ end,
+    int32_t* counts, int cnt_ld, float rp, float pp, float fp) {
   __shared__ uint32_t redu[SMP_THREADS / 64];
   __shared__ float redf[SMP_THREADS / 64];
   __shared__ __attribute__((aligned(16))) uint32_t tmx[SMP_THREADS];
@@ -308,10 +365,46 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_kernel(
   // exit before the first barrier; done[b] is only ever written by this row's own block)
   if (done && done[b] != 0) return;
   const float* row = logits + (int64_t)b * ld;
+  // PEN: the row of the count table, read beside the logits and written once, by the thread that picks
+  int32_t* crow = PEN ? counts + (int64_t)b * cnt_ld : nullptr;
   // element j * 1024 + t stays in registers as an order-preserving key (key 0 = padding,
   // below every real key)
   uint32_t key[SMP_MAXC];
-  if (VEC4) {  // element 4 * (j * 1024 + t) + e: 13 coalesced 16-byte loads per thread
+  if (PEN && VEC4) {
+    // the logits as below, with the counts of the same four ids beside them (int4 beside float4,
+    // the same clamped index and live mask), group by group: a count register dies as soon as its
+    // key exists, and 13 count vectors beside 13 logit vectors would not fit 128 VGPRs
+    const float4* row4 = reinterpret_cast<const float4*>(row);
+    const int4* crow4 = reinterpret_cast<const int4*>(crow);
+    const int V4 = V / 4;
+    float4 v[SMP_MAXC / 4];
+    int4 c[SMP_MAXC / 4];
+    in_groups<SMP_PEN_GROUP, SMP_MAXC / 4>(
+        [&](int j) {
+          v[j] = row4[min(j * SMP_THREADS + t, V4 - 1)];
+          c[j] = crow4[min(j * SMP_THREADS + t, V4 - 1)];
+        },
+        [&](int j) {
+          count_fence(c[j]);
+          const uint32_t live = (uint32_t)((j * SMP_THREADS + t - V4) >> 31);
+          key[4 * j + 0] = fkey(penalize(v[j].x, c[j].x, rp, pp, fp)) & live;
+          key[4 * j + 1] = fkey(penalize(v[j].y, c[j].y, rp, pp, fp)) & live;
+          key[4 * j + 2] = fkey(penalize(v[j].z, c[j].z, rp, pp, fp)) & live;
+          key[4 * j + 3] = fkey(penalize(v[j].w, c[j].w, rp, pp, fp)) & live;
+        });
+  } else if (PEN) {
+    float v[SMP_MAXC];
+    int c[SMP_MAXC];
+    in_groups<4 * SMP_PEN_GROUP, SMP_MAXC>(
+        [&](int j) {
+          v[j] = row[min(j * SMP_THREADS + t, V - 1)];
+          c[j] = crow[min(j * SMP_THREADS + t, V - 1)];
+        },
+        [&](int j) {
+          count_fence(c[j]);
+          key[j] = fkey(penalize(v[j], c[j], rp, pp, fp)) & (uint32_t)((j * SMP_THREADS + t - V) >> 31);
+        });
+  } else if (VEC4) {  // element 4 * (j * 1024 + t) + e: 13 coalesced 16-byte loads per thread
     const float4* row4 = reinterpret_cast<const float4*>(row);
     const int V4 = V / 4;
 #pragma unroll
@@ -518,6 +611,7 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_kernel(
             if (ck[i] >= thr) pick = ci[i];
           tok[b] = pick;
           gen[(int64_t)b * gen_ld + p] = pick;
+          if (PEN && pick >= 0) crow[pick] = crow[pick] + 1;  // the row's only writer; its loads are behind a barrier
           // stop_token < 0: never (pick >= 0); end: the row's last position (read by the writer alone)
           if (done && (pick == stop_token || (REQ && end && (int64_t)p >= end[b]))) done[b] = 1;
         }
@@ -616,13 +710,14 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_kernel(
     }
     if (pick < 0) {  // no kept element in this thread (u >= total on the last one): any kept one
       for (int i = V - 1; i >= 0; --i)
-        if (fkey(row[i]) >= thr) {
+        if (fkey(PEN ? penalize(row[i], crow[i], rp, pp, fp) : row[i]) >= thr) {
           pick = i;
           break;
         }
     }
     tok[b] = pick;
     gen[(int64_t)b * gen_ld + p] = pick;
+    if (PEN && pick >= 0) crow[pick] = crow[pick] + 1;
     if (done && (pick == stop_token || (REQ && end && (int64_t)p >= end[b]))) done[b] = 1;
   }
 }
@@ -631,25 +726,58 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_kernel(
 hipError_t sample_launch(bool filt, const void* logits, int B, int V, int ld, float temperature, int top_k,
                          uint64_t salt, const void* salt_dev, const void* pos, int pos_stride, void* tok, void* gen,
                          int gen_ld, int stop_token, void* done, float top_p, float min_p, void* stats,
-                         const void* row_key, const void* end, hipStream_t s) {
+                         const void* row_key, const void* end, hipStream_t s, void* counts = nullptr, int cnt_ld = 0,
+                         float rp = 1.0f, float pp = 0.0f, float fp = 0.0f) {
   if (B < 1 || V < 1 || V > SMP_THREADS * SMP_MAXC || !(temperature > 0.0f)) return hipErrorInvalidValue;
   if (pos_stride != 0 && pos_stride != 1) return hipErrorInvalidValue;
   if (!(top_p > 0.0f && top_p <= 1.0f) || !(min_p >= 0.0f && min_p < 1.0f)) return hipErrorInvalidValue;
   if (end && !done) return hipErrorInvalidValue;  // an end position finishes a row through its flag
-  const bool vec4 = V % 4 == 0 && ld % 4 == 0 && ((uintptr_t)logits & 15) == 0;
+  bool vec4 = V % 4 == 0 && ld % 4 == 0 && ((uintptr_t)logits & 15) == 0;
+  if (counts) {  // the penalised sampler reads int4 counts beside the float4 logits
+    const auto finite = [](float x) { return x - x == 0.0f; };  // false for an infinity and for NaN
+    if (cnt_ld < V || !(rp > 0.0f) || !finite(rp) || !finite(pp) || !finite(fp)) return hipErrorInvalidValue;
+    vec4 = vec4 && cnt_ld % 4 == 0 && ((uintptr_t)counts & 15) == 0;
+  }
   // REQ (a row key or an end position is given) is an instantiation of its own: the four others
   // compile both away and keep their registers
   const bool req = row_key || end;
   const auto kernel =
-      req ? (filt ? (vec4 ? sample_kernel<true, true, true> : sample_kernel<false, true, true>)
-                  : (vec4 ? sample_kernel<true, false, true> : sample_kernel<false, false, true>))
-          : (filt ? (vec4 ? sample_kernel<true, true, false> : sample_kernel<false, true, false>)
-                  : (vec4 ? sample_kernel<true, false, false> : sample_kernel<false, false, false>));
+      counts ? (filt ? (vec4 ? sample_kernel<true, true, true, true> : sample_kernel<false, true, true, true>)
+                     : (vec4 ? sample_kernel<true, false, true, true> : sample_kernel<false, false, true, true>))
+      : req ? (filt ? (vec4 ? sample_kernel<true, true, true> : sample_kernel<false, true, true>)
+                    : (vec4 ? sample_kernel<true, false, true> : sample_kernel<false, false, true>))
+            : (filt ? (vec4 ? sample_kernel<true, true, false> : sample_kernel<false, true, false>)
+                    : (vec4 ? sample_kernel<true, false, false> : sample_kernel<false, false, false>));
   kernel<<<B, SMP_THREADS, 0, s>>>((const float*)logits, V, ld, 1.4426950408889634f / temperature, top_k, top_p, min_p,
                                    salt, (const uint64_t*)salt_dev, (const int64_t*)pos, pos_stride, (int64_t*)tok,
                                    (int64_t*)gen, gen_ld, stop_token, (int64_t*)done, (int32_t*)stats,
-                                   (const int64_t*)row_key, (const int64_t*)end);
+                                   (const int64_t*)row_key, (const int64_t*)end, (int32_t*)counts, cnt_ld, rp, pp, fp);
   return hipGetLastError();
+}
+
+// Token histograms for the count table: workgroup i counts the first lengths[i] (NULL: S) ids of
+// idx[i, :] into row rows[i] (NULL: i) of counts, after zeroing the row's V entries unless
+// accumulate is set.  Ids outside 0 .. V - 1 are not counted, and a row outside 0 .. B - 1 is left out.
+constexpr int CNT_THREADS = 256;
+
+__global__ __launch_bounds__(CNT_THREADS) void token_counts_kernel(
+    const int64_t* __restrict__ idx, int S, const int64_t* __restrict__ lengths, const int64_t* __restrict__ rows,
+    int32_t* __restrict__ counts, int B, int ld, int V, int accumulate) {
+  const int i = blockIdx.x, t = threadIdx.x;
+  const int64_t r = rows ? rows[i] : (int64_t)i;
+  if (r < 0 || r >= B) return;  // block-uniform, before the barrier
+  int32_t* crow = counts + r * ld;
+  if (!accumulate) {
+    for (int v = t; v < V; v += CNT_THREADS) crow[v] = 0;
+    __syncthreads();  // one workgroup owns the row: its zeros are in place before its adds
+  }
+  const int64_t len = lengths ? lengths[i] : (int64_t)S;
+  const int n = (int)(len < 0 ? 0 : len > S ? S : len);
+  const int64_t* src = idx + (int64_t)i * S;
+  for (int j = t; j < n; j += CNT_THREADS) {
+    const int64_t id = src[j];
+    if (id >= 0 && id < V) atomicAdd(crow + id, 1);
+  }
 }
 
 }  // namespace
@@ -699,4 +827,34 @@ NSA_API hipError_t nsa_sample_requests(const void* logits, int B, int V, int ld,
   if (!filt && (top_p != 1.0f || min_p != 0.0f || stats)) return hipErrorInvalidValue;
   return sample_launch(filt != 0, logits, B, V, ld, temperature, top_k, salt, salt_dev, pos, pos_stride, tok, gen,
                        gen_ld, stop_token, done, top_p, min_p, stats, row_key, end, s);
+}
+
+// The penalised sampler: nsa_sample_requests (row_key and end may be NULL) on logits that the
+// kernel penalises as it loads them.  counts (int32 [B, cnt_ld], cnt_ld >= V): counts[b, v] is how
+// often id v occurs in row b's text; with c = counts[b, v] and s = c > 0 a logit l is drawn as
+//   ((s ? (l > 0 ? l / rp : l * rp) : l) - fp * c) - (s ? pp : 0),
+// every operation rounded on its own (ops.penalize_logits), and the thread that writes the drawn
+// id adds 1 to counts[b, id].  A row with done[b] != 0 neither reads nor writes its counts.  rp
+// finite and > 0, pp and fp finite.
+NSA_API hipError_t nsa_sample_penalized(const void* logits, int B, int V, int ld, float temperature, int top_k,
+                                        int filt, float top_p, float min_p, uint64_t salt, const void* salt_dev,
+                                        const void* pos, int pos_stride, void* tok, void* gen, int gen_ld,
+                                        int stop_token, void* done, void* stats, const void* row_key, const void* end,
+                                        void* counts, int cnt_ld, float rp, float pp, float fp, hipStream_t s) {
+  if (!counts) return hipErrorInvalidValue;
+  if (!filt && (top_p != 1.0f || min_p != 0.0f || stats)) return hipErrorInvalidValue;
+  return sample_launch(filt != 0, logits, B, V, ld, temperature, top_k, salt, salt_dev, pos, pos_stride, tok, gen,
+                       gen_ld, stop_token, done, top_p, min_p, stats, row_key, end, s, counts, cnt_ld, rp, pp, fp);
+}
+
+// Histograms of n prompts idx [n, S] (int64) into rows of the count table counts (int32 [B, V], row
+// stride ld >= V): prompt i's first lengths[i] ids (int64 [n]; NULL: all S) into row rows[i]
+// (int64 [n], distinct; NULL: row i), which is zeroed first unless accumulate != 0.  One launch,
+// one workgroup per prompt.
+NSA_API hipError_t nsa_token_counts(const void* idx, int n, int S, const void* lengths, const void* rows, void* counts,
+                                    int B, int ld, int V, int accumulate, hipStream_t s) {
+  if (n < 1 || S < 1 || B < 1 || V < 1 || ld < V || !idx || !counts) return hipErrorInvalidValue;
+  token_counts_kernel<<<n, CNT_THREADS, 0, s>>>((const int64_t*)idx, S, (const int64_t*)lengths, (const int64_t*)rows,
+                                                (int32_t*)counts, B, ld, V, accumulate);
+  return hipGetLastError();
 }

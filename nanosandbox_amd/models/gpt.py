@@ -357,16 +357,29 @@ class GPT(nn.Module):
         return flops_achieved / peak_flops
 
     @torch.no_grad()
-    def generate(self, idx, max_new_tokens, temperature=1.0, top_k=None, top_p=None, min_p=None):
+    def generate(self, idx, max_new_tokens, temperature=1.0, top_k=None, top_p=None, min_p=None,
+                 repetition_penalty=None, presence_penalty=None, frequency_penalty=None):
         """Autoregressive sampling: crop context, last-token logits / temperature,
         optional top-k (None or 0: off), nucleus ``top_p`` and ``min_p``
-        (``ops.filter_logits``), softmax, multinomial, append."""
+        (``ops.filter_logits``), softmax, multinomial, append.  ``repetition_penalty`` /
+        ``presence_penalty`` / ``frequency_penalty`` (1, 0, 0 or None: off): the raw logits are
+        penalised first (``ops.penalize_logits``) with counts of the whole sequence so far, the
+        part cropped from the context included."""
         ops.check_sampling_filters(top_p, min_p)
+        ops.check_sampling_penalties(repetition_penalty, presence_penalty, frequency_penalty)
+        pen = (1.0 if repetition_penalty is None else float(repetition_penalty),
+               0.0 if presence_penalty is None else float(presence_penalty),
+               0.0 if frequency_penalty is None else float(frequency_penalty))
         for _ in range(max_new_tokens):
             # if the sequence context is growing too long we must crop it at block_size
             idx_cond = idx if idx.size(1) <= self.config.block_size else idx[:, -self.config.block_size:]
             logits, _ = self(idx_cond)
-            logits = logits[:, -1, :] / temperature
+            logits = logits[:, -1, :]
+            if pen != (1.0, 0.0, 0.0):
+                counts = torch.zeros(idx.size(0), logits.size(-1), dtype=torch.int32, device=idx.device)
+                counts.scatter_add_(1, idx, torch.ones_like(idx, dtype=torch.int32))
+                logits = ops.penalize_logits(logits, counts, *pen)
+            logits = logits / temperature
             if top_k:
                 v, _ = torch.topk(logits, min(top_k, logits.size(-1)))
                 logits[logits < v[:, [-1]]] = -float("Inf")
@@ -380,7 +393,8 @@ class GPT(nn.Module):
     @torch.no_grad()
     def generate_cached(self, idx, max_new_tokens, temperature=1.0, top_k=None, use_graph=None, decoder=None,
                         top_p=None, min_p=None, quantize=None, kv_quantize=None, shared_prompt=False,
-                        speculate=None, spec_ngram=3, spec_table=None):
+                        speculate=None, spec_ngram=3, spec_table=None, repetition_penalty=None,
+                        presence_penalty=None, frequency_penalty=None):
         """``generate`` with per-layer KV caches: the prompt is encoded once and every
         new token runs one position through the model (a replayed HIP graph on the GPU;
         ``runtime/decode.py``).  Same sampling; falls back to ``generate`` when prompt +
@@ -389,17 +403,21 @@ class GPT(nn.Module):
         block_size).  ``shared_prompt=True``: the rows of ``idx`` are one prompt, cached once
         for the whole batch (equal rows or ValueError; no fallback either).  ``speculate=K``:
         speculative decoding with K tokens drafted by ``spec_ngram``-gram lookup in the row's own
-        history (or read from ``spec_table``): the same tokens in fewer model passes."""
+        history (or read from ``spec_table``): the same tokens in fewer model passes.
+        ``repetition_penalty`` / ``presence_penalty`` / ``frequency_penalty``: as in ``generate``, applied
+        inside the device sampler's launch (a penalising decoder); not with ``speculate``."""
         from ..runtime.decode import generate_cached
         return generate_cached(self, idx, max_new_tokens, temperature=temperature, top_k=top_k, use_graph=use_graph,
                                decoder=decoder, top_p=top_p, min_p=min_p, quantize=quantize,
                                kv_quantize=kv_quantize, shared_prompt=shared_prompt, speculate=speculate,
-                               spec_ngram=spec_ngram, spec_table=spec_table)
+                               spec_ngram=spec_ngram, spec_table=spec_table, repetition_penalty=repetition_penalty,
+                               presence_penalty=presence_penalty, frequency_penalty=frequency_penalty)
 
     @torch.no_grad()
     def generate_batch(self, prompts, max_new_tokens, temperature=1.0, top_k=None, stop_token=None, use_graph=None,
                        decoder=None, top_p=None, min_p=None, quantize=None, kv_quantize=None, shared_prompt=False,
-                       shared_prefix=False, batch_size=None, speculate=None, spec_ngram=3, spec_table=None):
+                       shared_prefix=False, batch_size=None, speculate=None, spec_ngram=3, spec_table=None,
+                       repetition_penalty=None, presence_penalty=None, frequency_penalty=None):
         """``generate_cached`` for a list of 1-D prompts of unequal lengths, decoded as one
         batch with a position per row; returns a list of 1-D tensors (prompt + new tokens).
         A row that draws ``stop_token`` ends with it; the others get exactly
@@ -410,10 +428,12 @@ class GPT(nn.Module):
         ``max_new_tokens`` as one int per prompt): the prompts are a queue served in order through
         at most B rows, a finished row taking the next prompt; results in prompt order.
         ``speculate=K`` / ``spec_ngram`` / ``spec_table``: speculative decoding, as in
-        ``generate_cached``."""
+        ``generate_cached``.  ``repetition_penalty`` / ``presence_penalty`` / ``frequency_penalty``: as in
+        ``generate_cached``, every row by the counts of its own text."""
         from ..runtime.decode import generate_batch
         return generate_batch(self, prompts, max_new_tokens, temperature=temperature, top_k=top_k,
                               stop_token=stop_token, use_graph=use_graph, decoder=decoder, top_p=top_p, min_p=min_p,
                               quantize=quantize, kv_quantize=kv_quantize, shared_prompt=shared_prompt,
                               shared_prefix=shared_prefix, batch_size=batch_size, speculate=speculate,
-                              spec_ngram=spec_ngram, spec_table=spec_table)
+                              spec_ngram=spec_ngram, spec_table=spec_table, repetition_penalty=repetition_penalty,
+                              presence_penalty=presence_penalty, frequency_penalty=frequency_penalty)

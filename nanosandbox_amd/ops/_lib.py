@@ -87,6 +87,12 @@ _SIGNATURES = {
     "nsa_sample_requests": [c_void_p, c_int, c_int, c_int, c_float, c_int, c_int, c_float, c_float, c_uint64,
                             c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
                             c_void_p, c_void_p, c_void_p],
+    # the penalised sampler: nsa_sample_requests' arguments, then counts, its row stride and rp, pp, fp
+    "nsa_sample_penalized": [c_void_p, c_int, c_int, c_int, c_float, c_int, c_int, c_float, c_float, c_uint64,
+                             c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
+                             c_void_p, c_void_p, c_void_p, c_int, c_float, c_float, c_float, c_void_p],
+    # token histograms: idx, n, S, lengths, rows, counts, B, ld, V, accumulate
+    "nsa_token_counts": [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p],
     # row-mapped appends: qkv, caches, rows, pos0, n, B, S, H, D, Tmax
     "nsa_kv_append_rows": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                            c_void_p],

@@ -1585,8 +1585,74 @@ def filter_logits(z, top_k=None, top_p=None, min_p=None):
     return z.masked_fill(~keep, -float("Inf"))
 
 
+def check_sampling_penalties(repetition_penalty=None, presence_penalty=None, frequency_penalty=None):
+    """Validate the three penalties: ``repetition_penalty`` finite and > 0, ``presence_penalty`` and
+    ``frequency_penalty`` finite, or None."""
+    rp, pp, fp = repetition_penalty, presence_penalty, frequency_penalty
+    if rp is not None and not (math.isfinite(float(rp)) and float(rp) > 0.0):
+        raise ValueError(f"repetition_penalty must be finite and > 0, got {rp}")
+    if pp is not None and not math.isfinite(float(pp)):
+        raise ValueError(f"presence_penalty must be finite, got {pp}")
+    if fp is not None and not math.isfinite(float(fp)):
+        raise ValueError(f"frequency_penalty must be finite, got {fp}")
+
+
+def penalize_logits(logits, counts, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0):
+    """The repetition, frequency and presence penalties on raw logits [B, V] (before the
+    temperature), in torch and fp32.  ``counts`` [B, >= V] (integer): ``counts[b, v]`` is how often id
+    v occurs in row b's text so far, its prompt without padding (prefix plus suffix on a shared-prefix
+    decoder) and every token already drawn for it.  With c the count, s = c > 0 and l the logit::
+
+        x = s ? (l > 0 ? l / rp : l * rp) : l      # the CTRL / HuggingFace rule
+        y = x - fp * float(c)                      # frequency
+        z = y - (s ? pp : 0)                       # presence
+
+    every operation rounded to fp32 on its own (a true division, no fused multiply-add): the
+    sampling kernel forms the same bits as it loads a row.  Identity parameters (1, 0, 0) return
+    the logits' bits."""
+    check_sampling_penalties(repetition_penalty, presence_penalty, frequency_penalty)
+    lg = logits.float()
+    c = counts[..., :lg.shape[-1]]
+    s = c > 0
+    # tensors, not Python scalars: a scalar divisor may be applied as a multiplication by its reciprocal
+    rp = torch.full_like(lg, float(repetition_penalty))
+    pp = torch.full_like(lg, float(presence_penalty))
+    fp = torch.full_like(lg, float(frequency_penalty))
+    x = torch.where(s, torch.where(lg > 0, lg / rp, lg * rp), lg)
+    y = x - fp * c.to(torch.float32)
+    return y - torch.where(s, pp, torch.zeros_like(pp))
+
+
+def token_counts_(counts, idx, lengths=None, rows=None, accumulate=False):
+    """Token histograms into the count table ``counts`` (int32 [B, Vc], unit column stride): the
+    first ``lengths[i]`` (int64 [n]; None: all S) ids of ``idx[i]`` (int64 [n, S], ids < Vc) are
+    counted into row ``rows[i]`` (int64 [n], distinct; None: row i), which is zeroed first unless
+    ``accumulate``.  Every other row stays as it is.  One launch on the GPU for any n
+    (``nsa_token_counts``: one workgroup per prompt), torch elsewhere."""
+    n, S = idx.shape
+    assert counts.dim() == 2 and counts.dtype == torch.int32 and counts.stride(1) == 1
+    assert idx.dtype == torch.int64 and idx.device == counts.device
+    for t in (lengths, rows):
+        assert t is None or (t.numel() == n and t.dtype == torch.int64 and t.device == counts.device)
+    assert rows is not None or n <= counts.shape[0]
+    if counts.is_cuda:
+        _lib.call("nsa_token_counts", _lib.ptr(idx.contiguous()), n, S,
+                  _lib.ptr(None if lengths is None else lengths.contiguous()),
+                  _lib.ptr(None if rows is None else rows.contiguous()), _lib.ptr(counts), counts.shape[0],
+                  counts.stride(0), counts.shape[1], 1 if accumulate else 0, _lib.stream())
+        return counts
+    Vc = counts.shape[1]
+    for i in range(n):
+        ids = idx[i, :S if lengths is None else int(lengths[i])]
+        hist = torch.bincount(ids, minlength=Vc)[:Vc].to(torch.int32)
+        r = i if rows is None else int(rows[i])
+        counts[r] = counts[r] + hist if accumulate else hist
+    return counts
+
+
 def sample_topk_(logits, temperature: float, top_k, salt: int, pos, tok, gen, salt_dev=None, stop_token=None,
-                 done=None, top_p=None, min_p=None, stats=None, row_key=None, end=None):
+                 done=None, top_p=None, min_p=None, stats=None, row_key=None, end=None, counts=None,
+                 repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0):
     """Device-side nanoGPT sampling (logits / temperature, top-k, softmax, multinomial)
     of logits [B, V] fp32: the drawn ids go to ``tok`` [B, 1] and ``gen[:, pos]``
     (``pos``: int64 device tensor with one entry, or with B entries: row b writes
@@ -1609,9 +1675,25 @@ def sample_topk_(logits, temperature: float, top_k, salt: int, pos, tok, gen, sa
     ``row_key``: the hash takes ``row_key[b]`` where it takes the row index b, so a request
     draws the same stream in whatever row it is served.  It is accepted and ignored on the
     CPU, where the draw is ``torch.multinomial``.  ``end`` (needs ``done``): a row that has
-    written its id at position p sets ``done[b]`` if ``p >= end[b]``, as the stop token does."""
+    written its id at position p sets ``done[b]`` if ``p >= end[b]``, as the stop token does.
+
+    ``counts`` (int32 [B, >= V]; on the GPU a row stride that is a multiple of 4 and 16-byte aligned
+    keeps the vector loads): the penalised sampler.  The draw is made from
+    ``penalize_logits(logits, counts, repetition_penalty, presence_penalty, frequency_penalty)``,
+    formed by the kernel as it loads the row (``nsa_sample_penalized``, whatever the other
+    arguments: one launch, no copy of the logits), and every row that draws adds 1 to
+    ``counts[b, id]``; a skipped row's counts are neither read nor written.  Without ``counts`` the
+    penalties must be left off, and the call is what it always was."""
     B, V = logits.shape
     check_sampling_filters(top_p, min_p)
+    check_sampling_penalties(repetition_penalty, presence_penalty, frequency_penalty)
+    rp, pp, fp = float(repetition_penalty), float(presence_penalty), float(frequency_penalty)
+    if counts is None:
+        if (rp, pp, fp) != (1.0, 0.0, 0.0):
+            raise ValueError("sampling penalties need the count table: pass counts")
+    else:
+        assert counts.dim() == 2 and counts.shape[0] == B and counts.shape[1] >= V, "counts is int32 [B, >= V]"
+        assert counts.dtype == torch.int32 and counts.stride(1) == 1 and counts.device == logits.device
     filtered = top_p is not None or min_p is not None or stats is not None
     if stats is not None:
         assert stats.shape == (B, 2) and stats.dtype == torch.int32 and stats.is_contiguous()
@@ -1627,6 +1709,14 @@ def sample_topk_(logits, temperature: float, top_k, salt: int, pos, tok, gen, sa
     assert end is None or done is not None, "an end position finishes a row through its done flag"
     if logits.is_cuda:
         lg = logits if logits.dtype == F32 and logits.stride(1) == 1 else logits.float().contiguous()
+        if counts is not None:
+            _lib.call("nsa_sample_penalized", _lib.ptr(lg), B, V, lg.stride(0), float(temperature), k,
+                      1 if filtered else 0, 1.0 if top_p is None else float(top_p),
+                      0.0 if min_p is None else float(min_p), int(salt) & (2 ** 64 - 1), _lib.ptr(salt_dev),
+                      _lib.ptr(pos), 1 if per_row else 0, _lib.ptr(tok), _lib.ptr(gen), gen.stride(0), stop,
+                      _lib.ptr(done), _lib.ptr(stats), _lib.ptr(row_key), _lib.ptr(end), _lib.ptr(counts),
+                      counts.stride(0), rp, pp, fp, _lib.stream())
+            return
         if row_key is not None or end is not None:
             _lib.call("nsa_sample_requests", _lib.ptr(lg), B, V, lg.stride(0), float(temperature), k,
                       1 if filtered else 0, 1.0 if top_p is None else float(top_p),
@@ -1648,8 +1738,14 @@ def sample_topk_(logits, temperature: float, top_k, salt: int, pos, tok, gen, sa
         _lib.call("nsa_sample_topk", _lib.ptr(lg), B, V, lg.stride(0), float(temperature), k, int(salt) & (2 ** 64 - 1),
                   _lib.ptr(salt_dev), _lib.ptr(pos), _lib.ptr(tok), _lib.ptr(gen), gen.stride(0), _lib.stream())
         return
+    if counts is not None:
+        logits = penalize_logits(logits, counts, rp, pp, fp)
+        drew = torch.ones(B, dtype=torch.bool) if done is None else done.view(B) == 0  # before the draw ends a row
     lg = filter_logits(logits.float() / temperature, k, top_p, min_p)
     nxt = torch.multinomial(torch.softmax(lg, dim=-1), num_samples=1)
+    if counts is not None:  # the rows that draw: the one-hot of the drawn id
+        rws = drew.nonzero().view(-1)
+        counts[rws, nxt.view(B)[rws]] += 1
     if stats is not None:
         kept = lg > -float("Inf")
         low = logits.float().masked_fill(~kept, float("Inf")).min(dim=-1).values

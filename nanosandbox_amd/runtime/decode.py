@@ -106,6 +106,19 @@ the GPU B (K + 1) > 16 and a model without the fused decode kernels raise ValueE
 end of the cache have dead queries (positions >= block_size): they store nothing, come out as
 zeros and are never accepted.  With ``speculate`` unset nothing of this exists: every launch,
 graph key and result is what it was.
+``Decoder(..., penalize=True)`` is the mode for repetition, presence and frequency penalties
+(``ops.penalize_logits`` states the rule).  Such a decoder owns the count table ``cnt`` (int32 [B, V
+rounded up to 4]): ``cnt[b, v]`` is how often id v occurs in row b's text, its prompt without the
+padding (prefix plus suffix on a shared-prefix decoder) and every token drawn for it.  Every
+prefill form and ``admit`` rebuild the rows they start (``ops.token_counts_``: one launch; a
+shared_prompt decoder keeps its prompt's histogram as ``cnt0`` and copies it), and every draw goes
+through the penalised sampler (``ops.sample_topk_(counts=)``), which applies the penalties as it
+loads a row and counts the id it draws: the step keeps its launches, and with no penalty passed
+the parameters are the identity, so ``cnt`` never goes stale.  The graph key gains ``("pen", rp, pp,
+fp)``.  With per_row, ``stop_token``, ``top_p`` / ``min_p``, both quantizations, ``shared_prompt`` /
+``shared_prefix``, the queue and eager mode; ``speculate`` raises ValueError (a verified position's
+counts would have to include the drafts before it).  Without ``penalize`` there is no table
+(``cnt`` is None) and every launch, graph key and result is what it was.
 The caches hold at most ``block_size`` positions; ``GPT.generate_cached`` falls
 back to the recompute loop when prompt + new tokens exceed that (nanoGPT crops the
 context there, which a cache cannot do without re-encoding).
@@ -165,9 +178,12 @@ class Decoder:
     def __init__(self, model, batch_size: int, max_len: int | None = None, use_graph: bool | None = None,
                  per_row: bool = False, quantize: str | None = None, kv_quantize: str | None = None,
                  shared_prompt: bool = False, max_new: int | None = None, speculate: int | None = None,
-                 spec_ngram: int = 3):
+                 spec_ngram: int = 3, penalize: bool = False):
         _check_mode(quantize, kv_quantize, shared_prompt)
         self.K, self.N = _check_spec(speculate, spec_ngram, kv_quantize, shared_prompt)
+        if self.K and penalize:
+            raise ValueError("speculate cannot be combined with sampling penalties: a verified position's counts "
+                             "would have to include the drafts before it")
         per_row = per_row or bool(self.K)  # a speculating row advances by its own number of positions
         if shared_prompt and batch_size < 2:
             raise ValueError(f"shared_prompt needs at least 2 rows to share a prompt, got batch size {batch_size}")
@@ -269,6 +285,14 @@ class Decoder:
             self.spec_counts = torch.zeros(batch_size, 3, device=self.device, dtype=torch.int64)
             self.table = None  # set_draft_table: drafts read from a table instead of the n-gram lookup
         self._admit_logits = None  # [B, V] fp32: the admitted rows' logits at their own row indices
+        # penalize: how often every id occurs in a row's text (prompt and drawn tokens), int32 [B, V
+        # rounded up to 4] so that the sampler reads it in 16-byte vectors; cnt0 [1, same]: the
+        # histogram of a shared_prompt decoder's prompt
+        self.cnt = self.cnt0 = None
+        if penalize:
+            self.cnt = torch.zeros(batch_size, -(-cfg.vocab_size // 4) * 4, device=self.device, dtype=torch.int32)
+            if shared_prompt:
+                self.cnt0 = torch.zeros(1, self.cnt.shape[1], device=self.device, dtype=torch.int32)
         self.use_graph = (self.device.type == "cuda") if use_graph is None else use_graph
         if self.use_graph and not self.graph_capable(model):
             # the fused decode kernels cover head_dim 64, bf16 and V <= 53248; the fallback
@@ -302,15 +326,17 @@ class Decoder:
                 and cfg.vocab_size <= 53248)
 
     def fits(self, batch_size, per_row=False, quantize=None, kv_quantize=None, shared_prompt=False,
-             max_new=None, speculate=None, spec_ngram=3) -> bool:
+             max_new=None, speculate=None, spec_ngram=3, penalize=False) -> bool:
         """Whether a call that needs ``Decoder(model, batch_size, per_row=..., ...)`` can run on this
         one: the same rows and form, (shared) row caches of at least ``max_new`` slots, and the same
-        number of drafted tokens and n-gram length (speculative)."""
+        number of drafted tokens and n-gram length (speculative), and a count table if and only if
+        the call penalises."""
         K = int(speculate or 0)
         return (self.B == batch_size and self.per_row == bool(per_row or K) and self.quantize == quantize
                 and self.kv_quantize == kv_quantize and self.shared == bool(shared_prompt)
                 and (not self.shared or self.R >= (max_new or self.T))
-                and self.K == K and (not K or self.N == int(spec_ngram)))
+                and self.K == K and (not K or self.N == int(spec_ngram))
+                and (self.cnt is not None) == bool(penalize))
 
     def _quantize_weights(self):
         """int8 mode: quantize every linear weight and the tied lm_head / wte table, and point
@@ -523,6 +549,11 @@ class Decoder:
             lengths = torch.as_tensor(lengths, dtype=torch.int64).to(self.device).view(n)
             assert int(lengths.min()) >= 1 and int(lengths.max()) <= S
         h = self._encode(idx, first, rows)
+        if self.cnt is not None:
+            # the rows' histograms: rebuilt from the prompts, or (suffixes) the prefix's with the suffixes on top
+            if first:
+                self.cnt.copy_(self.cnt0.expand(self.B, -1))
+            ops.token_counts_(self.cnt, idx, lengths, rows, accumulate=bool(first))
         if first:
             self.plen.fill_(first)
         if rows is not None:
@@ -579,10 +610,14 @@ class Decoder:
             self._prompt_logits = ops.lm_head_logits(h[:, [-1], :], self.model.lm_head.weight)[:, 0].float()
             self._prompt = idx.clone()
             self.prefills += 1
+            if self.cnt is not None:
+                ops.token_counts_(self.cnt0, idx)
         self.plen.fill_(T0)
         self.pos.fill_(T0)
         if self.per_row:
             self.done.zero_()
+        if self.cnt is not None:
+            self.cnt.copy_(self.cnt0.expand(self.B, -1))
         return self._prompt_logits.expand(self.B, -1)
 
     @torch.no_grad()
@@ -615,7 +650,8 @@ class Decoder:
     def admit(self, rows, idx: torch.Tensor | None = None, lengths: torch.Tensor | None = None) -> torch.Tensor:
         """Start new prompts in the cache rows ``rows`` (n distinct indices) of a running per_row
         batch; returns their last-position logits [n, V].  Every other row's caches, ``pos``,
-        ``done``, ``tok`` and ``gen`` stay bit for bit as they were.
+        ``done``, ``tok``, ``gen`` and (penalising decoders) ``cnt`` stay bit for bit as they were; the
+        admitted rows' ``cnt`` becomes their prompts' histograms (shared_prompt: ``cnt0``).
 
         Ordinary decoder: ``idx`` [n, S] holds the right-padded prompts (``lengths``: int64 [n], as in
         ``prefill``; None: every prompt has S tokens); they run through the model as a batch of
@@ -634,11 +670,25 @@ class Decoder:
             assert self._prompt is not None, "admit follows prefill_shared(prompt)"
             self.pos.index_copy_(0, rows, self.plen.expand(n))
             self.done.index_fill_(0, rows, 0)
+            if self.cnt is not None:  # nothing of the row's previous request survives
+                self.cnt.index_copy_(0, rows, self.cnt0.expand(n, -1))
             return self._prompt_logits.expand(n, -1)
         assert idx is not None and idx.dim() == 2 and idx.shape[0] == n and 1 <= idx.shape[1] <= self.T
         if lengths is None:
             lengths = torch.full((n,), idx.shape[1], dtype=torch.int64, device=self.device)
         return self._prefill(idx.to(self.device), 0, lengths, rows)
+
+    def _pen(self, repetition_penalty=None, presence_penalty=None, frequency_penalty=None) -> dict:
+        """The sampler's penalty keywords for a draw on this decoder.  Penalising: the count table
+        and the three numbers, the identity where the call passes none, so every draw is counted.
+        Otherwise nothing, and a penalty that is on raises ValueError."""
+        pen = sampling_penalties(repetition_penalty, presence_penalty, frequency_penalty)
+        if self.cnt is None:
+            if pen is not None:
+                raise ValueError("sampling penalties need Decoder(..., penalize=True)")
+            return {}
+        rp, pp, fp = pen or (1.0, 0.0, 0.0)
+        return dict(counts=self.cnt, repetition_penalty=rp, presence_penalty=pp, frequency_penalty=fp)
 
     def _queue_state(self):
         """``key`` and ``end`` (allocated on first use): a row that serves no request keeps key 0
@@ -648,14 +698,16 @@ class Decoder:
             self.end = torch.full((self.B,), 2 ** 62, device=self.device, dtype=torch.int64)
 
     @torch.no_grad()
-    def sample_admitted(self, rows, logits, temperature, top_k, stop_token=None, top_p=None, min_p=None):
+    def sample_admitted(self, rows, logits, temperature, top_k, stop_token=None, top_p=None, min_p=None,
+                        repetition_penalty=None, presence_penalty=None, frequency_penalty=None):
         """Draw the first token of the just admitted rows ``rows`` from their ``logits`` [n, V]
         (what ``admit`` returned) into ``tok`` and ``gen[b, pos[b]]``, keyed and ended by ``key`` /
         ``end`` like the queue's steps.  The sampler runs over the whole batch with every other
-        row masked as finished, so those rows' ``tok``, ``gen`` and ``done`` stay untouched."""
+        row masked as finished, so those rows' ``tok``, ``gen``, ``done`` and ``cnt`` stay untouched."""
         assert self.per_row
         self._queue_state()
         top_p, min_p = sampling_filters(top_p, min_p)
+        pen = self._pen(repetition_penalty, presence_penalty, frequency_penalty)
         rows = self._row_index(rows)
         mask = torch.ones(self.B, device=self.device, dtype=torch.int64)
         mask.index_fill_(0, rows, 0)
@@ -667,12 +719,15 @@ class Decoder:
             full = self._admit_logits
             full.index_copy_(0, rows, logits.float())
         ops.sample_topk_(full, temperature, top_k, self.salt, self.pos, self.tok, self.gen, salt_dev=self.salt_dev,
-                         stop_token=stop_token, done=mask, top_p=top_p, min_p=min_p, row_key=self.key, end=self.end)
+                         stop_token=stop_token, done=mask, top_p=top_p, min_p=min_p, row_key=self.key, end=self.end,
+                         **pen)
         self.done.index_copy_(0, rows, mask[rows])
 
     @torch.no_grad()
     def serve(self, prompts, budgets, temperature: float = 1.0, top_k: int | None = None,
-              stop_token: int | None = None, top_p: float | None = None, min_p: float | None = None):
+              stop_token: int | None = None, top_p: float | None = None, min_p: float | None = None,
+              repetition_penalty: float | None = None, presence_penalty: float | None = None,
+              frequency_penalty: float | None = None):
         """Serve a queue of requests through the B rows of this per_row decoder, refilling a row as
         soon as its request is seen finished; returns every request's new tokens (1-D tensors, in
         request order: ``budgets[i]`` of them, or fewer, ending with ``stop_token``).
@@ -693,6 +748,8 @@ class Decoder:
             raise ValueError("a speculative decoder does not serve a queue")
         stop_token = _stop(stop_token)
         top_p, min_p = sampling_filters(top_p, min_p)
+        pen = _pen_kw(sampling_penalties(repetition_penalty, presence_penalty, frequency_penalty))
+        self._pen(**pen)  # a penalty on a decoder without the table: refused before anything runs
         nreq = len(prompts)
         budgets = [int(n) for n in budgets]
         lens = [int(p.numel()) for p in prompts]
@@ -730,7 +787,7 @@ class Decoder:
                 logits = self.admit(free)
             else:
                 logits = self.admit(free, *_right_pad([prompts[i] for i in reqs], self.device))
-            self.sample_admitted(free, logits, temperature, top_k, stop_token, top_p, min_p)
+            self.sample_admitted(free, logits, temperature, top_k, stop_token, top_p, min_p, **pen)
             for b, i in zip(free, reqs):
                 owner[b], left[b] = i, budgets[i] - 1
             stats["admissions"] += 1
@@ -740,7 +797,7 @@ class Decoder:
         while True:
             k = min(self.DONE_POLL, max(left[b] for b in range(B) if owner[b] is not None))
             if k > 0:
-                self.run(k, temperature, top_k, stop_token, top_p, min_p, queue=True)
+                self.run(k, temperature, top_k, stop_token, top_p, min_p, queue=True, **pen)
                 stats["steps"] += k
             done, pos = torch.stack([self.done, self.pos]).tolist()  # the one host look per poll
             for b in range(B):
@@ -782,6 +839,8 @@ class Decoder:
             pos, done = self.pos.clone(), self.done.clone()
         # a speculative warm-up step also accepts and drafts: its fed tokens and counters are put back too
         spec = [(t, t.clone()) for t in (self.stok, self.spos, self.cpos, self.spec_counts)] if self.K else []
+        if self.cnt is not None:  # a warm-up draw is counted: the table is put back as well
+            spec.append((self.cnt, self.cnt.clone()))
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
@@ -801,14 +860,18 @@ class Decoder:
             out = fn()
         return graph, out
 
-    def sample_into(self, logits, temperature, top_k, stop_token=None, top_p=None, min_p=None, queue=False):
+    def sample_into(self, logits, temperature, top_k, stop_token=None, top_p=None, min_p=None, queue=False,
+                    repetition_penalty=None, presence_penalty=None, frequency_penalty=None):
         """Draw the next token of every row from ``logits`` [B, V] into ``tok`` and
         ``gen[:, pos]`` (device kernel on the GPU: ``ops.sample_topk_``).  per_row: row b
         writes ``gen[b, pos[b]]``; a finished row draws nothing, and a row that draws
         ``stop_token`` is finished from then on.  ``top_p`` / ``min_p``: nucleus and min-p
         filters on top of the top-k (off: the top-k sampler's own launch).  ``queue``: the
-        serving queue's form, every row keyed by ``key`` and finished at ``end``."""
+        serving queue's form, every row keyed by ``key`` and finished at ``end``.  The three
+        penalties (penalising decoders; None: off): the draw is made from
+        ``ops.penalize_logits(logits, cnt, ...)`` and counted in ``cnt``, inside the same launch."""
         top_p, min_p = sampling_filters(top_p, min_p)
+        pen = self._pen(repetition_penalty, presence_penalty, frequency_penalty)
         if queue:
             assert self.per_row and self.key is not None, "the queue form needs a per_row decoder with key / end"
         if not self.per_row:
@@ -817,41 +880,49 @@ class Decoder:
         # picks its entry point from what is there
         ops.sample_topk_(logits, temperature, top_k, self.salt, self.pos, self.tok, self.gen, salt_dev=self.salt_dev,
                          stop_token=stop_token, done=self.done, top_p=top_p, min_p=min_p,
-                         row_key=self.key if queue else None, end=self.end if queue else None)
+                         row_key=self.key if queue else None, end=self.end if queue else None, **pen)
 
     def reseed(self):
         """A fresh sampling stream for the next generate call (torch.manual_seed governs)."""
         self.salt_dev.fill_(int(torch.randint(0, 2 ** 62, (1,)).item()))
 
-    def _step_sample_impl(self, temperature, top_k, stop_token=None, top_p=None, min_p=None, queue=False):
-        self.sample_into(self._step_impl(), temperature, top_k, stop_token, top_p, min_p, queue)  # pos is now p + 1
+    def _step_sample_impl(self, temperature, top_k, stop_token=None, top_p=None, min_p=None, queue=False, **pen):
+        self.sample_into(self._step_impl(), temperature, top_k, stop_token, top_p, min_p, queue, **pen)  # pos is now p + 1
 
     DONE_POLL = 16  # run(): replays between two host looks at the finished flags
 
     @torch.no_grad()
     def run(self, n: int, temperature: float = 1.0, top_k: int | None = None, stop_token: int | None = None,
-            top_p: float | None = None, min_p: float | None = None, queue: bool = False):
+            top_p: float | None = None, min_p: float | None = None, queue: bool = False,
+            repetition_penalty: float | None = None, presence_penalty: float | None = None,
+            frequency_penalty: float | None = None):
         """Decode n tokens starting from ``self.tok`` at ``self.pos``: each step feeds the
         token, samples the next one and feeds it back on the device (one graph replay per
         token on the GPU, no host round trip).  Results land in ``self.gen``.  With a
         ``stop_token`` (per_row decoders) the finished flags are read back every
         ``DONE_POLL`` steps and the loop ends early once every row has finished.  ``queue``
         (``serve``): the sampler reads ``key`` and ``end``, a graph of its own (the key gains
-        ``"queue"``); without it the graphs and their keys are the ones there always were."""
+        ``"queue"``); without it the graphs and their keys are the ones there always were.  The
+        three penalties: as in ``sample_into``; on a penalising decoder the key gains ``("pen", rp,
+        pp, fp)``, the identity (1, 0, 0) when none is passed."""
         stop_token = _stop(stop_token)
         assert stop_token is None or self.per_row, "a stop token needs Decoder(..., per_row=True)"
         top_p, min_p = sampling_filters(top_p, min_p)
+        pen = _pen_kw(sampling_penalties(repetition_penalty, presence_penalty, frequency_penalty))
+        drawn = self._pen(**pen)  # the sampler's keywords: refused here if this decoder has no table
         if self.K:
             if queue:
                 raise ValueError("a speculative decoder does not serve a queue")
             return self._run_spec(n, temperature, top_k, stop_token, top_p, min_p)
-        step = lambda: self._step_sample_impl(temperature, top_k, stop_token, top_p, min_p, queue)  # noqa: E731
+        step = lambda: self._step_sample_impl(temperature, top_k, stop_token, top_p, min_p, queue, **pen)  # noqa: E731
         if self.use_graph:
             key = (float(temperature), top_k, stop_token) if self.per_row else (float(temperature), top_k)
             if top_p is not None or min_p is not None:  # without them: the keys (and graphs) of the top-k sampler
                 key += (top_p, min_p)
             if queue:
                 key += ("queue",)
+            if drawn:
+                key += ("pen", drawn["repetition_penalty"], drawn["presence_penalty"], drawn["frequency_penalty"])
             if key not in self.sgraphs:
                 self.sgraphs[key], _ = self._capture(step)
             step = self.sgraphs[key].replay
@@ -915,12 +986,36 @@ def sampling_filters(top_p=None, min_p=None):
             None if min_p is None or float(min_p) <= 0.0 else float(min_p))
 
 
+def sampling_penalties(repetition_penalty=None, presence_penalty=None, frequency_penalty=None):
+    """Validated (repetition_penalty, presence_penalty, frequency_penalty) as floats, or None when
+    all three are off (1, 0 and 0, or None)."""
+    ops.check_sampling_penalties(repetition_penalty, presence_penalty, frequency_penalty)
+    pen = (1.0 if repetition_penalty is None else float(repetition_penalty),
+           0.0 if presence_penalty is None else float(presence_penalty),
+           0.0 if frequency_penalty is None else float(frequency_penalty))
+    return None if pen == (1.0, 0.0, 0.0) else pen
+
+
+def _pen_kw(pen) -> dict:
+    """``sampling_penalties``' result as the keywords of the sampling calls (off: none)."""
+    return {} if pen is None else dict(repetition_penalty=pen[0], presence_penalty=pen[1], frequency_penalty=pen[2])
+
+
 def sample_next(logits: torch.Tensor, temperature: float = 1.0, top_k: int | None = None,
                 generator: torch.Generator | None = None, top_p: float | None = None,
-                min_p: float | None = None) -> torch.Tensor:
+                min_p: float | None = None, counts: torch.Tensor | None = None,
+                repetition_penalty: float | None = None, presence_penalty: float | None = None,
+                frequency_penalty: float | None = None) -> torch.Tensor:
     """nanoGPT's sampling: logits / temperature, optional top-k (None or 0: off), nucleus
-    ``top_p`` and ``min_p`` (``ops.filter_logits``), softmax, multinomial -> [B, 1]."""
+    ``top_p`` and ``min_p`` (``ops.filter_logits``), softmax, multinomial -> [B, 1].  With
+    ``counts`` ([B, >= V]: how often every id occurs in the row's whole text) the raw logits are
+    penalised first (``ops.penalize_logits``); ``counts`` itself is the caller's to update."""
     top_p, min_p = sampling_filters(top_p, min_p)
+    pen = sampling_penalties(repetition_penalty, presence_penalty, frequency_penalty)
+    if pen is not None:
+        if counts is None:
+            raise ValueError("sampling penalties need counts")
+        logits = ops.penalize_logits(logits, counts, *pen)
     logits = logits.float() / temperature
     if top_k:
         v, _ = torch.topk(logits, min(top_k, logits.size(-1)))
@@ -931,15 +1026,21 @@ def sample_next(logits: torch.Tensor, temperature: float = 1.0, top_k: int | Non
     return torch.multinomial(probs, num_samples=1, generator=generator)
 
 
-def _mode(B, per_row=False, quantize=None, kv_quantize=None, slots=None, spec=(0, 3)) -> dict:
+def _mode(B, per_row=False, quantize=None, kv_quantize=None, slots=None, spec=(0, 3), penalize=False) -> dict:
     """The decoder a call needs, as ``Decoder``'s arguments (and ``Decoder.fits``'s): B rows, per_row
     or not, the two quantizations, ``slots``, the row-cache slots of a shared_prompt decoder
-    (None: an unshared one), and ``spec``, the (K, N) of ``_check_spec`` (K > 0: a speculative
-    one, which is per_row)."""
+    (None: an unshared one), ``spec``, the (K, N) of ``_check_spec`` (K > 0: a speculative
+    one, which is per_row), and ``penalize``: one with a count table, for a call with a penalty on
+    (which speculation does not compose with: ValueError)."""
     mode = dict(batch_size=B, per_row=per_row, quantize=quantize, kv_quantize=kv_quantize,
                 shared_prompt=slots is not None, max_new=slots)
     if spec[0]:
+        if penalize:
+            raise ValueError("speculate cannot be combined with sampling penalties: a verified position's counts "
+                             "would have to include the drafts before it")
         mode.update(per_row=True, speculate=spec[0], spec_ngram=spec[1])
+    if penalize:
+        mode.update(penalize=True)
     return mode
 
 
@@ -967,19 +1068,23 @@ def _nothing_to_share(sharing, L, N, T):
                       "and the recompute loop has nothing to share")
 
 
-def _cached_mode(model, idx, max_new_tokens, quantize, kv_quantize, shared_prompt, speculate=None, spec_ngram=3):
-    """The mode of the decoder ``generate_cached`` runs this call on (None: the recompute loop)."""
+def _cached_mode(model, idx, max_new_tokens, quantize, kv_quantize, shared_prompt, speculate=None, spec_ngram=3,
+                 penalize=False):
+    """The mode of the decoder ``generate_cached`` runs this call on (None: the recompute loop).
+    ``penalize``: the call has a penalty on."""
     B, T0 = idx.shape
     T = model.config.block_size
     _check_mode(quantize, kv_quantize, shared_prompt)
     spec = _check_spec(speculate, spec_ngram, kv_quantize, shared_prompt)
+    if spec[0] and penalize:
+        _mode(B, spec=spec, penalize=True)  # raises
     if shared_prompt:
         if not bool((idx == idx[:1]).all()):
             raise ValueError("shared_prompt needs every row of idx to be the same prompt")
         if B > 1:  # a single row goes the ordinary way
             if T0 + max_new_tokens > T:
                 raise _nothing_to_share("shared_prompt", T0, max_new_tokens, T)
-            return _mode(B, False, quantize, slots=max_new_tokens)
+            return _mode(B, False, quantize, slots=max_new_tokens, penalize=penalize)
     if T0 + max_new_tokens - 1 > T:
         if quantize:
             raise ValueError("quantize needs the KV-cache path: prompt + new tokens exceed block_size, and the "
@@ -991,19 +1096,22 @@ def _cached_mode(model, idx, max_new_tokens, quantize, kv_quantize, shared_promp
             raise ValueError("speculate needs the KV-cache path: prompt + new tokens exceed block_size, and the "
                              "recompute loop decodes one token per pass")
         return None
-    return _mode(B, False, quantize, kv_quantize, spec=spec)
+    return _mode(B, False, quantize, kv_quantize, spec=spec, penalize=penalize)
 
 
 def cached_decoder(model, idx, max_new_tokens, use_graph=None, quantize=None, kv_quantize=None, shared_prompt=False,
-                   speculate=None, spec_ngram=3):
+                   speculate=None, spec_ngram=3, repetition_penalty=None, presence_penalty=None,
+                   frequency_penalty=None):
     """The Decoder this ``generate_cached`` call would build, for a caller that keeps it across
     calls (``decoder=``) and releases it.  A call that runs on none (no new tokens, or the
     recompute loop) gets the ordinary one all the same, as ``sample.py`` always has: building it
-    draws from torch's generator, and a seeded run keeps its tokens."""
+    draws from torch's generator, and a seeded run keeps its tokens.  With a penalty on it is a
+    penalising one."""
+    pen = sampling_penalties(repetition_penalty, presence_penalty, frequency_penalty) is not None
     mode = max_new_tokens > 0 and _cached_mode(model, idx, max_new_tokens, quantize, kv_quantize, shared_prompt,
-                                               speculate, spec_ngram)
+                                               speculate, spec_ngram, pen)
     return _build(model, mode or _mode(idx.shape[0], False, quantize, kv_quantize,
-                                       spec=_check_spec(speculate, spec_ngram, kv_quantize)), use_graph)
+                                       spec=_check_spec(speculate, spec_ngram, kv_quantize), penalize=pen), use_graph)
 
 
 @torch.no_grad()
@@ -1012,8 +1120,16 @@ def generate_cached(model, idx: torch.Tensor, max_new_tokens: int, temperature: 
                     decoder: "Decoder | None" = None, top_p: float | None = None,
                     min_p: float | None = None, quantize: str | None = None,
                     kv_quantize: str | None = None, shared_prompt: bool = False,
-                    speculate: int | None = None, spec_ngram: int = 3, spec_table=None) -> torch.Tensor:
+                    speculate: int | None = None, spec_ngram: int = 3, spec_table=None,
+                    repetition_penalty: float | None = None, presence_penalty: float | None = None,
+                    frequency_penalty: float | None = None) -> torch.Tensor:
     """``model.generate`` with KV caches: same sampling, one token's forward per new token.
+
+    ``repetition_penalty`` / ``presence_penalty`` / ``frequency_penalty`` (``ops.penalize_logits``; 1, 0
+    and 0 or None: off): with one of them on the call runs on a penalising decoder
+    (``Decoder(..., penalize=True)``: built here, or ``decoder`` if it is one), whose sampler applies
+    them to the raw logits inside its one launch, from counts of the row's prompt and drawn tokens.
+    Past block_size the recompute loop applies the same rule.  ValueError with ``speculate``.
 
     ``speculate=K`` (1 .. 7): speculative decoding (``Decoder(..., speculate=K, spec_ngram=N)``). A
     step feeds every row's token and K continuations guessed by n-gram lookup in the row's own
@@ -1042,16 +1158,19 @@ def generate_cached(model, idx: torch.Tensor, max_new_tokens: int, temperature: 
     top_p, min_p = sampling_filters(top_p, min_p)
     if max_new_tokens <= 0:
         return idx
-    mode = _cached_mode(model, idx, max_new_tokens, quantize, kv_quantize, shared_prompt, speculate, spec_ngram)
+    pen = _pen_kw(sampling_penalties(repetition_penalty, presence_penalty, frequency_penalty))
+    mode = _cached_mode(model, idx, max_new_tokens, quantize, kv_quantize, shared_prompt, speculate, spec_ngram,
+                        bool(pen))
     if mode is None:
         # the caches hold block_size positions; nanoGPT crops the context beyond that
-        return model.generate(idx, max_new_tokens, temperature=temperature, top_k=top_k, top_p=top_p, min_p=min_p)
+        return model.generate(idx, max_new_tokens, temperature=temperature, top_k=top_k, top_p=top_p, min_p=min_p,
+                              **pen)
     with _borrow(model, mode, decoder, use_graph) as dec:
         if dec.K:
             dec.set_draft_table(spec_table)
         logits = dec.prefill_shared(idx[0]) if dec.shared else dec.prefill(idx)
-        dec.sample_into(logits, temperature, top_k, None, top_p, min_p)  # pos = T0: gen[:, T0]
-        dec.run(max_new_tokens - 1, temperature, top_k, None, top_p, min_p)
+        dec.sample_into(logits, temperature, top_k, None, top_p, min_p, **pen)  # pos = T0: gen[:, T0]
+        dec.run(max_new_tokens - 1, temperature, top_k, None, top_p, min_p, **pen)
         return torch.cat([idx, dec.gen[:, T0:T0 + max_new_tokens]], dim=1)
 
 
@@ -1085,7 +1204,7 @@ def common_prefix_len(prompts) -> int:
 
 
 def _batch_plan(model, prompts, max_new_tokens, quantize, kv_quantize, shared_prompt, shared_prefix, batch_size,
-                speculate=None, spec_ngram=3):
+                speculate=None, spec_ngram=3, penalize=False):
     """What ``generate_batch`` does with a call -> (prompts, budgets, queue, fit, P, mode): the
     flattened prompts on the model's device, every prompt's budget of new tokens, whether they are
     served as a queue, the indices of the prompts that share the decoder (the others go alone), the
@@ -1105,6 +1224,8 @@ def _batch_plan(model, prompts, max_new_tokens, quantize, kv_quantize, shared_pr
                 raise ValueError(f"every budget must be at least 1, got {budgets}")
     _check_mode(quantize, kv_quantize, shared_prompt, shared_prefix)
     spec = _check_spec(speculate, spec_ngram, kv_quantize, shared_prompt, shared_prefix, queue)
+    if spec[0] and penalize:
+        _mode(len(prompts), True, spec=spec, penalize=True)  # raises
     assert all(p.numel() >= 1 for p in prompts), "every prompt needs at least one token"
     device = model.lm_head.weight.device
     prompts = [p.view(-1).to(device) for p in prompts]
@@ -1132,20 +1253,22 @@ def _batch_plan(model, prompts, max_new_tokens, quantize, kv_quantize, shared_pr
     if sharing and B >= 2:  # a single row goes the ordinary way
         # a row's cache holds what follows the shared tokens: its suffix, if any, and its new tokens
         slots = max(budgets[i] + (prompts[i].numel() - P if P else 0) for i in fit)
-    return prompts, budgets, queue, fit, P, _mode(B, True, quantize, kv_quantize, slots, spec)
+    return prompts, budgets, queue, fit, P, _mode(B, True, quantize, kv_quantize, slots, spec, penalize)
 
 
 def batch_decoder(model, prompts, max_new_tokens, use_graph=None, quantize=None, kv_quantize=None,
-                  shared_prompt=False, shared_prefix=False, batch_size=None, speculate=None, spec_ngram=3):
+                  shared_prompt=False, shared_prefix=False, batch_size=None, speculate=None, spec_ngram=3,
+                  repetition_penalty=None, presence_penalty=None, frequency_penalty=None):
     """The Decoder this ``generate_batch`` call would build, for a caller that keeps it across
     calls (``decoder=``; a shared one then keeps the prompt or prefix too) and releases it.  A call
     that shares none (no new tokens, or no prompt that fits the cache) gets the ordinary one of a
-    row per prompt, for the reason ``cached_decoder`` gives."""
+    row per prompt, for the reason ``cached_decoder`` gives.  With a penalty on it is a penalising one."""
+    pen = sampling_penalties(repetition_penalty, presence_penalty, frequency_penalty) is not None
     plan = _batch_plan(model, prompts, max_new_tokens, quantize, kv_quantize, shared_prompt, shared_prefix, batch_size,
-                       speculate, spec_ngram)
+                       speculate, spec_ngram, pen)
     mode = plan and plan[-1]
     return _build(model, mode or _mode(len(prompts), True, quantize, kv_quantize,
-                                       spec=_check_spec(speculate, spec_ngram, kv_quantize)), use_graph)
+                                       spec=_check_spec(speculate, spec_ngram, kv_quantize), penalize=pen), use_graph)
 
 
 @torch.no_grad()
@@ -1155,8 +1278,13 @@ def generate_batch(model, prompts, max_new_tokens, temperature: float = 1.0, top
                    min_p: float | None = None, quantize: str | None = None,
                    kv_quantize: str | None = None, shared_prompt: bool = False,
                    shared_prefix: bool = False, batch_size: int | None = None, speculate: int | None = None,
-                   spec_ngram: int = 3, spec_table=None) -> list[torch.Tensor]:
+                   spec_ngram: int = 3, spec_table=None, repetition_penalty: float | None = None,
+                   presence_penalty: float | None = None, frequency_penalty: float | None = None) -> list[torch.Tensor]:
     """Generate for a list of prompts of unequal lengths as one batch.
+
+    ``repetition_penalty`` / ``presence_penalty`` / ``frequency_penalty``: as in ``generate_cached``; every
+    row is penalised by the counts of its own prompt (prefix and suffix) and drawn tokens, a queue's
+    row by those of the request it serves.  ValueError with ``speculate``.
 
     ``speculate=K`` / ``spec_ngram=N`` / ``spec_table``: speculative decoding, as in
     ``generate_cached`` (``spec_table``: one 1-D tensor of ids by position per prompt); every row
@@ -1210,8 +1338,9 @@ def generate_batch(model, prompts, max_new_tokens, temperature: float = 1.0, top
     ``generate_cached`` (``quantize`` / ``kv_quantize`` / ``shared_prompt``: ValueError).
     ``shared_prefix=True``, ``batch_size < 1`` and a budget list of the wrong length or with an
     entry < 1 raise ValueError.  With ``batch_size=None`` and an int budget nothing changes."""
+    pen = _pen_kw(sampling_penalties(repetition_penalty, presence_penalty, frequency_penalty))
     plan = _batch_plan(model, prompts, max_new_tokens, quantize, kv_quantize, shared_prompt, shared_prefix, batch_size,
-                       speculate, spec_ngram)
+                       speculate, spec_ngram, bool(pen))
     stop_token = _stop(stop_token)
     sampling = (temperature, top_k, stop_token, *sampling_filters(top_p, min_p))
     if plan is None:
@@ -1223,13 +1352,13 @@ def generate_batch(model, prompts, max_new_tokens, temperature: float = 1.0, top
             y = generate_cached(model, p[None], budgets[i], temperature=temperature, top_k=top_k, use_graph=use_graph,
                                 top_p=top_p, min_p=min_p, quantize=quantize, kv_quantize=kv_quantize,
                                 speculate=speculate, spec_ngram=spec_ngram,
-                                spec_table=None if spec_table is None else [spec_table[i]])[0]
+                                spec_table=None if spec_table is None else [spec_table[i]], **pen)[0]
             outs[i] = _result(p, y[p.numel():], stop_token)
     if not fit:
         return outs
     with _borrow(model, mode, decoder, use_graph) as dec:
         if queue:
-            news = dec.serve([prompts[i] for i in fit], [budgets[i] for i in fit], *sampling)
+            news = dec.serve([prompts[i] for i in fit], [budgets[i] for i in fit], *sampling, **pen)
         else:
             if P:
                 dec.prefill_shared(prompts[0][:P])
@@ -1240,8 +1369,8 @@ def generate_batch(model, prompts, max_new_tokens, temperature: float = 1.0, top
                 if dec.K:
                     dec.set_draft_table(None if spec_table is None else [spec_table[i] for i in fit])
                 logits = dec.prefill(*_right_pad([prompts[i] for i in fit], dec.device))
-            dec.sample_into(logits, *sampling)  # gen[b, its prompt's length]
-            dec.run(max_new_tokens - 1, *sampling)
+            dec.sample_into(logits, *sampling, **pen)  # gen[b, its prompt's length]
+            dec.run(max_new_tokens - 1, *sampling, **pen)
         for b, i in enumerate(fit):
             L = prompts[i].numel()
             outs[i] = (_result(prompts[i], news[b]) if queue else

@@ -34,6 +34,11 @@ model itself draws (``Decoder(speculate=K)``): the same samples for the same see
 tokens per pass.  It needs the KV-cache path, refuses ``--kv_quantize``, ``--shared_prompt``,
 ``--shared_prefix`` and ``--serve_batch`` and composes with ``--quantize``, ``--stop_token``,
 ``--top_p`` / ``--min_p``, ``--sample_batch`` and ``--prompts_file`` (rows * (K + 1) <= 16 on the GPU).
+``--repetition_penalty=1.3`` (> 0; divides the positive and multiplies the negative logits of the ids a
+sample's text already holds), ``--presence_penalty=0.5`` (subtracted from them once) and
+``--frequency_penalty=0.2`` (subtracted once per occurrence) discourage a sample from repeating itself
+(``ops.penalize_logits``: prompt and generated tokens count); on the GPU they are applied inside the
+sampling kernel's launch (``Decoder(penalize=True)``).  They compose with every mode but ``--speculate``.
 """
 
 from __future__ import annotations
@@ -46,7 +51,7 @@ import torch
 from .config import parse_argv
 from .data import load_meta, resolve_data_dir
 from .models import GPT, GPTConfig
-from .ops import check_sampling_filters
+from .ops import check_sampling_filters, check_sampling_penalties
 from .utils import load_checkpoint, load_model_state
 
 SAMPLE_DEFAULTS = dict(
@@ -59,6 +64,9 @@ SAMPLE_DEFAULTS = dict(
     top_k=200,  # keep the k most likely tokens; 0: off
     top_p=1.0,  # nucleus: the smallest set of most likely tokens whose mass reaches top_p; 1.0: off
     min_p=0.0,  # drop tokens less likely than min_p times the most likely one; 0.0: off
+    repetition_penalty=1.0,  # > 0: logits of ids the text already holds are divided (positive) or multiplied (negative) by it; 1.0: off
+    presence_penalty=0.0,  # subtracted from the logit of every id the text already holds; 0.0: off
+    frequency_penalty=0.0,  # subtracted from an id's logit once per occurrence in the text; 0.0: off
     seed=1337,
     device="cuda",
     dtype="bfloat16",
@@ -78,6 +86,11 @@ SAMPLE_DEFAULTS = dict(
 )
 
 
+def _penalties(c) -> dict:
+    """The three penalty keys as the front ends' keywords."""
+    return {k: c[k] for k in ("repetition_penalty", "presence_penalty", "frequency_penalty")}
+
+
 def _serve_queue(model, c, encode, decode, start, device):
     """serve_batch: every request (num_samples rounds of the prompts file, or num_samples copies
     of start) through one queue of ``serve_batch`` rows (``GPT.generate_batch(batch_size=)``)."""
@@ -91,7 +104,7 @@ def _serve_queue(model, c, encode, decode, start, device):
     ys = model.generate_batch(prompts, c["max_new_tokens"], temperature=c["temperature"], top_k=c["top_k"],
                               stop_token=stop, top_p=c["top_p"], min_p=c["min_p"], quantize=c["quantize"] or None,
                               kv_quantize=c["kv_quantize"] or None, shared_prompt=bool(c["shared_prompt"]),
-                              batch_size=c["serve_batch"])
+                              batch_size=c["serve_batch"], **_penalties(c))
     outs = []
     for p, y in zip(prompts, ys):
         new = y[p.numel():].tolist()
@@ -128,13 +141,14 @@ def _generate_batches(model, c, encode, decode, start, device):
                 mode = dict(quantize=quantize, kv_quantize=kv_quantize, shared_prompt=shared, shared_prefix=prefix)
                 if c["speculate"]:
                     mode.update(speculate=c["speculate"], spec_ngram=c["spec_ngram"])
+                mode.update(_penalties(c))
                 if B not in decs:  # a shared prompt / prefix stays cached in it: later rounds do not encode it again
                     decs[B] = batch_decoder(model, prompts, c["max_new_tokens"], **mode)
                 ys = model.generate_batch(prompts, c["max_new_tokens"], temperature=c["temperature"], top_k=c["top_k"],
                                           stop_token=stop, decoder=decs[B], top_p=c["top_p"], min_p=c["min_p"], **mode)
             else:
                 ys = [model.generate(p[None], c["max_new_tokens"], temperature=c["temperature"], top_k=c["top_k"],
-                                     top_p=c["top_p"], min_p=c["min_p"])[0] for p in prompts]
+                                     top_p=c["top_p"], min_p=c["min_p"], **_penalties(c))[0] for p in prompts]
             for p, y in zip(prompts, ys):
                 new = y[p.numel():].tolist()
                 if stop is not None and stop in new:
@@ -176,6 +190,7 @@ def _codec(checkpoint, data_dir):
 def main(argv=None):
     c = parse_argv(SAMPLE_DEFAULTS, sys.argv[1:] if argv is None else argv)
     check_sampling_filters(c["top_p"], c["min_p"])
+    check_sampling_penalties(c["repetition_penalty"], c["presence_penalty"], c["frequency_penalty"])
     if c["quantize"] not in ("", "int8"):
         raise ValueError(f"quantize must be '' or 'int8', got {c['quantize']!r}")
     if c["quantize"] and not c["kv_cache"]:
@@ -219,6 +234,9 @@ def main(argv=None):
         if not c["kv_cache"]:
             raise ValueError("--speculate needs the KV-cache path: the recompute loop (--kv_cache=False) decodes one "
                              "token per pass")
+        if _penalties(c) != dict(repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0):
+            raise ValueError("--speculate cannot be combined with --repetition_penalty / --presence_penalty / "
+                             "--frequency_penalty: a verified position's counts would have to include its drafts")
     spec = dict(speculate=c["speculate"], spec_ngram=c["spec_ngram"]) if c["speculate"] else {}
     quantize = c["quantize"] or None
     kv_quantize = c["kv_quantize"] or None
@@ -256,17 +274,18 @@ def main(argv=None):
         # one decoder for all samples: weight shadows and the captured step graph are
         # built once, not per sample
         from .runtime.decode import cached_decoder
-        dec = cached_decoder(model, x, c["max_new_tokens"], quantize=quantize, kv_quantize=kv_quantize, **spec)
+        dec = cached_decoder(model, x, c["max_new_tokens"], quantize=quantize, kv_quantize=kv_quantize, **spec,
+                             **_penalties(c))
     try:
         with torch.no_grad():
             for _ in range(c["num_samples"]):
                 if dec is not None:
                     y = model.generate_cached(x, c["max_new_tokens"], temperature=c["temperature"], top_k=c["top_k"],
                                               decoder=dec, top_p=c["top_p"], min_p=c["min_p"], quantize=quantize,
-                                              kv_quantize=kv_quantize, **spec)
+                                              kv_quantize=kv_quantize, **spec, **_penalties(c))
                 else:
                     y = model.generate(x, c["max_new_tokens"], temperature=c["temperature"], top_k=c["top_k"],
-                                       top_p=c["top_p"], min_p=c["min_p"])
+                                       top_p=c["top_p"], min_p=c["min_p"], **_penalties(c))
                 text = decode(y[0].tolist())
                 outs.append(text)
                 print(text)

@@ -51,6 +51,9 @@ read from a table holding the tokens the run will draw (every draft accepted: th
 tokens + 1 (none accepted: the cost of the wider step, the floor); the table comes from an untimed
 pass with the same sampling stream.  These lines carry the live ``steps`` per row, the drafts
 ``accepted`` / ``offered`` and their ratio.
+``--penalties RP,PP,FP`` adds ``graph_pen`` / ``rows_pen`` right after ``graph`` / ``rows``: the same
+settings on a ``Decoder(penalize=True)`` sampling with that repetition, presence and frequency
+penalty (the penalised sampler and its count table beside the plain step of the same run).
 """
 
 import argparse
@@ -66,22 +69,24 @@ from nanosandbox_amd.models import GPT, GPTConfig  # noqa: E402
 from nanosandbox_amd.runtime.decode import Decoder  # noqa: E402
 
 SMP = dict(top_k=200, top_p=None, min_p=None)  # the sampling settings of every mode (--top_k / --top_p / --min_p)
+PEN = {}  # --penalties: the three penalty keywords of the _pen modes
 DIMS = {"gpt2": (12, 12, 768), "gpt2-medium": (24, 16, 1024), "gpt2-large": (36, 20, 1280), "gpt2-xl": (48, 25, 1600)}
 
 
-def run_cached(model, idx, new, use_graph, quantize=None, kv_quantize=None):
+def run_cached(model, idx, new, use_graph, quantize=None, kv_quantize=None, pen=False):
     B = idx.shape[0]
-    dec = Decoder(model, B, use_graph=use_graph, quantize=quantize, kv_quantize=kv_quantize)
-    dec.sample_into(dec.prefill(idx), 0.8, **SMP)
+    dec = Decoder(model, B, use_graph=use_graph, quantize=quantize, kv_quantize=kv_quantize, penalize=pen)
+    smp = dict(SMP, **PEN) if pen else SMP
+    dec.sample_into(dec.prefill(idx), 0.8, **smp)
     if use_graph:
-        dec.run(1, 0.8, **SMP)  # capture outside the timed loop
+        dec.run(1, 0.8, **smp)  # capture outside the timed loop
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     if use_graph:
-        dec.run(new, 0.8, **SMP)  # step + sampling + feedback: one graph replay per token
+        dec.run(new, 0.8, **smp)  # step + sampling + feedback: one graph replay per token
     else:
         for _ in range(new):  # eager step + the same device sampling kernel
-            dec.sample_into(dec.step(dec.tok), 0.8, **SMP)
+            dec.sample_into(dec.step(dec.tok), 0.8, **smp)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     dec.release()
@@ -94,25 +99,29 @@ def ragged_lengths(B, prompt):
     return [prompt if B == 1 else lo + (prompt - lo) * b // (B - 1) for b in range(B)]
 
 
-def run_rows(model, idx, new, lengths=None, quantize=None, kv_quantize=None, shared=False):
+def run_rows(model, idx, new, lengths=None, quantize=None, kv_quantize=None, shared=False, pen=False):
     """The graph mode on a per_row decoder: equal lengths, or (lengths) a ragged batch; shared:
     a shared_prompt decoder, every row continuing idx[0].  Returns (seconds of the timed steps,
-    seconds from the start of the prefill to the first drawn token)."""
+    seconds from the start of the prefill to the first drawn token).  pen: a penalising decoder,
+    sampling with --penalties."""
     B = idx.shape[0]
     if shared:  # slots for the capture step and the timed ones
-        dec = Decoder(model, B, use_graph=True, per_row=True, quantize=quantize, shared_prompt=True, max_new=new + 1)
+        dec = Decoder(model, B, use_graph=True, per_row=True, quantize=quantize, shared_prompt=True, max_new=new + 1,
+                      penalize=pen)
     else:
-        dec = Decoder(model, B, use_graph=True, per_row=True, quantize=quantize, kv_quantize=kv_quantize)
+        dec = Decoder(model, B, use_graph=True, per_row=True, quantize=quantize, kv_quantize=kv_quantize,
+                      penalize=pen)
+    smp = dict(SMP, **PEN) if pen else SMP
     lens = None if lengths is None else torch.tensor(lengths, device=idx.device)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    dec.sample_into(dec.prefill_shared(idx[0]) if shared else dec.prefill(idx, lens), 0.8, **SMP)
+    dec.sample_into(dec.prefill_shared(idx[0]) if shared else dec.prefill(idx, lens), 0.8, **smp)
     torch.cuda.synchronize()
     ttft = time.perf_counter() - t0
-    dec.run(1, 0.8, **SMP)  # capture outside the timed loop
+    dec.run(1, 0.8, **smp)  # capture outside the timed loop
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    dec.run(new, 0.8, **SMP)
+    dec.run(new, 0.8, **smp)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     dec.release()
@@ -304,6 +313,8 @@ def main():
     ap.add_argument("--spec_ngram", type=int, default=3, help="--speculate: the longest n-gram looked up")
     ap.add_argument("--spec_table", default="", help="right, wrong or both: add table-drafted twins "
                                                      "(rows_specK_right: all accepted, rows_specK_wrong: none)")
+    ap.add_argument("--penalties", default="", help="RP,PP,FP: add penalised twins of the graph and rows modes "
+                                                    "(graph_pen, rows_pen) on a Decoder(penalize=True)")
     ap.add_argument("--top_k", type=int, default=200, help="0: no top-k")
     ap.add_argument("--top_p", type=float, default=1.0, help="nucleus mass; 1.0: off")
     ap.add_argument("--min_p", type=float, default=0.0, help="floor relative to the most likely token; 0.0: off")
@@ -328,6 +339,11 @@ def main():
         twins = [f"spec{int(k)}" + t for k in a.speculate.split(",")
                  for t in [""] + ["_" + x for x in a.spec_table.split(",") if x]]
         modes = [t for m in modes for t in ([m] + [f"{m}_{x}" for x in twins] if m in ("rows", "rows_int8") else [m])]
+    if a.penalties:  # each penalised twin right after its mode
+        rp, pp, fp = (float(x) for x in a.penalties.split(","))
+        PEN.update(repetition_penalty=rp, presence_penalty=pp, frequency_penalty=fp)
+        extra["penalties"] = a.penalties
+        modes = [t for m in modes for t in ([m, f"{m}_pen"] if m in ("graph", "rows") else [m])]
     if a.shared_prefix:
         modes = ["prefix_rows", "prefix_shared"]
     block_size = GPTConfig().block_size
@@ -391,8 +407,8 @@ def main():
                     elif base in ("rows", "ragged"):
                         n = a.new
                         lens = ragged_lengths(B, a.prompt) if base == "ragged" else None
-                        run_rows(model, idx, 4, lens, qz, kvq, "shared" in sfx)
-                        dt, t1 = run_rows(model, idx, n, lens, qz, kvq, "shared" in sfx)
+                        run_rows(model, idx, 4, lens, qz, kvq, "shared" in sfx, "pen" in sfx)
+                        dt, t1 = run_rows(model, idx, n, lens, qz, kvq, "shared" in sfx, "pen" in sfx)
                         if a.shared_prompt:
                             ttft = {"ttft_ms": round(t1 * 1e3, 3)}
                     elif mode == "recompute":
@@ -401,8 +417,8 @@ def main():
                         dt = run_recompute(model, idx, n)
                     else:
                         n = a.new
-                        run_cached(model, idx, 4, base == "graph", qz, kvq)
-                        dt = run_cached(model, idx, n, base == "graph", qz, kvq)
+                        run_cached(model, idx, 4, base == "graph", qz, kvq, "pen" in sfx)
+                        dt = run_cached(model, idx, n, base == "graph", qz, kvq, "pen" in sfx)
                     mem = ({"decoder_peak_mb": round((torch.cuda.max_memory_allocated() - mem0) / 2 ** 20, 1)}
                            if a.memory else {})
                     print(json.dumps({"model": name, "batch": B, "mode": mode, "prompt": a.prompt, "new_tokens": n,
