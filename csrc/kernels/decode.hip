@@ -640,6 +640,7 @@ NSA_API hipError_t nsa_skinny_ln_gemm(const void* res, const void* branch, void*
     return hipErrorInvalidValue;
   const unsigned grid = (unsigned)(N / 16);
   const size_t lds = (size_t)16 * (K + 8) * sizeof(bf16_t);
+  if (!branch) s_out = nullptr;  // s is res itself: nothing to write (as the single-row kernel)
 #define NSA_SKLN(A, F)                                                                                    \
   skinny_ln_gemm_kernel<A, F><<<grid, 256, lds, s>>>((const float*)res, (const bf16_t*)branch, (float*)s_out, \
                                                      (const bf16_t*)lw, (const bf16_t*)lb, eps, (const bf16_t*)W, \

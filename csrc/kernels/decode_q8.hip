@@ -623,6 +623,7 @@ NSA_API hipError_t nsa_skinny_ln_gemm_q8(const void* res, const void* branch, vo
                                          hipStream_t s) {
   if (rows < 1 || rows > 16 || K % 64 || K < 64 || K > 1920 || N < 1 || (act && out_f32) || (branch && !s_out))
     return hipErrorInvalidValue;
+  if (!branch) s_out = nullptr;  // s is res itself: nothing to write (as the single-row kernel)
   const unsigned grid = (unsigned)((N + 15) / 16);
   const size_t lds = (size_t)16 * (K + 8) * sizeof(bf16_t);
 #define NSA_SKLNQ(A, F)                                                                                         \

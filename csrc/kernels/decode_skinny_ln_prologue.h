@@ -12,7 +12,8 @@
 // Names it expects in scope:
 //   res     const float*: the residual stream, [M][K] fp32
 //   branch  const bf16_t*: the branch output added to it, [M][K], or null
-//   s_out   float*: where workgroup 0 writes s, [M][K], or null
+//   s_out   float*: where workgroup 0 writes s, [M][K], or null (the entry points pass null
+//           when there is no branch: s is res itself then and nothing is written)
 //   lw, lb  const bf16_t*: LayerNorm weight and bias [K] (lb may be null)
 //   eps     float: LayerNorm epsilon
 //   xs      bf16_t*: LDS, [16][KP]
