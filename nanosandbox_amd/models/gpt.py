@@ -358,13 +358,17 @@ class GPT(nn.Module):
 
     @torch.no_grad()
     def generate(self, idx, max_new_tokens, temperature=1.0, top_k=None, top_p=None, min_p=None,
-                 repetition_penalty=None, presence_penalty=None, frequency_penalty=None):
+                 repetition_penalty=None, presence_penalty=None, frequency_penalty=None, logprobs=None):
         """Autoregressive sampling: crop context, last-token logits / temperature,
         optional top-k (None or 0: off), nucleus ``top_p`` and ``min_p``
         (``ops.filter_logits``), softmax, multinomial, append.  ``repetition_penalty`` /
         ``presence_penalty`` / ``frequency_penalty`` (1, 0, 0 or None: off): the raw logits are
         penalised first (``ops.penalize_logits``) with counts of the whole sequence so far, the
-        part cropped from the context included."""
+        part cropped from the context included.  ``logprobs=N`` (0 .. 8; None: off): returns ``(tokens,
+        ops.LogProbs)`` over the new tokens, each token's log-probability under the raw logits and the
+        N most likely ids with theirs (``ops.token_logprobs``)."""
+        logprobs = ops.check_logprobs(logprobs)
+        recs = []
         ops.check_sampling_filters(top_p, min_p)
         ops.check_sampling_penalties(repetition_penalty, presence_penalty, frequency_penalty)
         pen = (1.0 if repetition_penalty is None else float(repetition_penalty),
@@ -374,7 +378,7 @@ class GPT(nn.Module):
             # if the sequence context is growing too long we must crop it at block_size
             idx_cond = idx if idx.size(1) <= self.config.block_size else idx[:, -self.config.block_size:]
             logits, _ = self(idx_cond)
-            logits = logits[:, -1, :]
+            logits = raw = logits[:, -1, :]
             if pen != (1.0, 0.0, 0.0):
                 counts = torch.zeros(idx.size(0), logits.size(-1), dtype=torch.int32, device=idx.device)
                 counts.scatter_add_(1, idx, torch.ones_like(idx, dtype=torch.int32))
@@ -387,14 +391,67 @@ class GPT(nn.Module):
                 logits = ops.filter_logits(logits.float(), None, top_p, min_p)
             probs = torch.softmax(logits, dim=-1)
             idx_next = torch.multinomial(probs, num_samples=1)
+            if logprobs is not None:
+                recs.append(ops.token_logprobs(raw, idx_next.view(-1), top=logprobs))
             idx = torch.cat((idx, idx_next), dim=1)
-        return idx
+        if logprobs is None:
+            return idx
+        if not recs:
+            return idx, ops.LogProbs(torch.zeros(idx.size(0), 0, device=idx.device),
+                                     torch.zeros(idx.size(0), 0, logprobs, dtype=torch.int32, device=idx.device),
+                                     torch.zeros(idx.size(0), 0, logprobs, device=idx.device))
+        return idx, ops.LogProbs(*(torch.stack(c, dim=1) for c in zip(*recs)))
+
+    @torch.no_grad()
+    def score(self, idx, lengths=None, top=0):
+        """Log-probabilities of a given text: ``ops.LogProbs`` over [B, T - 1], entry t the
+        log-probability of ``idx[b, t + 1]`` given ``idx[b, :t + 1]`` under the model's raw logits
+        (``ops.token_logprobs``: the quantity a decoder with ``logprobs`` records for drawn tokens), with
+        ``top`` = N (0 .. 8) also the N most likely ids at every place and theirs.  ``lengths`` (int64
+        [B]; None: every row has T tokens): row b's text is its first ``lengths[b]`` tokens, and the
+        entries at or past ``lengths[b] - 1`` are skipped: they hold NaN (``top_ids``: -1), which
+        ``LogProbs.perplexity()`` leaves out.
+
+        On the GPU in bf16 the trunk runs once and the padded bf16 result of the lm_head GEMM goes
+        straight into the kernel (row stride ``lm_head_rows(V)``, V columns): no fp32 copy of the
+        logits exists.  The GEMM runs over at most ``SCORE_CHUNK_ROWS`` = 2048 positions at a time, so
+        at most 2048 x 50304 x 2 bytes = 206 MB of logits are alive for GPT-2's vocabulary, whatever
+        B x T is (``forward_logits`` + cross-entropy hold 6 V bytes per position, all positions at
+        once).  Elsewhere: ``forward_logits`` and the same op."""
+        top = ops.check_logprobs(top)
+        B, T = idx.shape
+        assert 2 <= T <= self.config.block_size, f"score needs 2 .. {self.config.block_size} tokens per row, got {T}"
+        V = self.config.vocab_size
+        ids = idx[:, 1:].clone()
+        if lengths is not None:
+            lengths = torch.as_tensor(lengths, dtype=torch.int64).to(idx.device).view(B)
+            ids[torch.arange(1, T, device=idx.device)[None, :] >= lengths[:, None]] = -1
+        ids = ids.reshape(-1)
+        M = ids.numel()
+        out = ops.LogProbs(torch.full((M,), float("nan"), dtype=torch.float32, device=idx.device),
+                           torch.full((M, top), -1, dtype=torch.int32, device=idx.device),
+                           torch.full((M, top), float("nan"), dtype=torch.float32, device=idx.device))
+        if idx.is_cuda and self.compute_dtype == torch.bfloat16:
+            tr = self.transformer
+            x = ops.embedding(idx, tr.wte.weight, tr.wpe.weight, 0.0, False, dtype=self.residual_dtype,
+                              cdtype=self.compute_dtype)
+            h = self._trunk(x)[:, :-1].reshape(M, -1)  # the last position predicts nothing that is given
+            for r in range(0, M, self.SCORE_CHUNK_ROWS):
+                rows = slice(r, min(M, r + self.SCORE_CHUNK_ROWS))
+                logits = ops.lm_head_logits_padded(h[rows], self.lm_head.weight)  # bf16 [rows, Vpad]
+                ops.token_logprobs(logits, ids[rows], top=top, V=V, out=ops.LogProbs(*(t[rows] for t in out)))
+        else:
+            logits = self.forward_logits(idx)[:, :-1].reshape(M, -1)
+            ops.token_logprobs(logits, ids, top=top, V=V, out=out)
+        return ops.LogProbs(out.token.view(B, T - 1), out.top_ids.view(B, T - 1, top), out.top.view(B, T - 1, top))
+
+    SCORE_CHUNK_ROWS = 2048  # logit rows alive at a time in ``score`` (x Vpad x 2 bytes: 206 MB for GPT-2)
 
     @torch.no_grad()
     def generate_cached(self, idx, max_new_tokens, temperature=1.0, top_k=None, use_graph=None, decoder=None,
                         top_p=None, min_p=None, quantize=None, kv_quantize=None, shared_prompt=False,
                         speculate=None, spec_ngram=3, spec_table=None, repetition_penalty=None,
-                        presence_penalty=None, frequency_penalty=None):
+                        presence_penalty=None, frequency_penalty=None, logprobs=None):
         """``generate`` with per-layer KV caches: the prompt is encoded once and every
         new token runs one position through the model (a replayed HIP graph on the GPU;
         ``runtime/decode.py``).  Same sampling; falls back to ``generate`` when prompt +
@@ -405,19 +462,22 @@ class GPT(nn.Module):
         speculative decoding with K tokens drafted by ``spec_ngram``-gram lookup in the row's own
         history (or read from ``spec_table``): the same tokens in fewer model passes.
         ``repetition_penalty`` / ``presence_penalty`` / ``frequency_penalty``: as in ``generate``, applied
-        inside the device sampler's launch (a penalising decoder); not with ``speculate``."""
+        inside the device sampler's launch (a penalising decoder); not with ``speculate``.
+        ``logprobs=N`` (0 .. 8; None: off): returns ``(tokens, ops.LogProbs)`` over the new tokens, as
+        ``generate`` does, recorded by one more launch inside the captured step; not with ``speculate``."""
         from ..runtime.decode import generate_cached
+        lpk = {} if logprobs is None else dict(logprobs=logprobs)
         return generate_cached(self, idx, max_new_tokens, temperature=temperature, top_k=top_k, use_graph=use_graph,
                                decoder=decoder, top_p=top_p, min_p=min_p, quantize=quantize,
                                kv_quantize=kv_quantize, shared_prompt=shared_prompt, speculate=speculate,
                                spec_ngram=spec_ngram, spec_table=spec_table, repetition_penalty=repetition_penalty,
-                               presence_penalty=presence_penalty, frequency_penalty=frequency_penalty)
+                               presence_penalty=presence_penalty, frequency_penalty=frequency_penalty, **lpk)
 
     @torch.no_grad()
     def generate_batch(self, prompts, max_new_tokens, temperature=1.0, top_k=None, stop_token=None, use_graph=None,
                        decoder=None, top_p=None, min_p=None, quantize=None, kv_quantize=None, shared_prompt=False,
                        shared_prefix=False, batch_size=None, speculate=None, spec_ngram=3, spec_table=None,
-                       repetition_penalty=None, presence_penalty=None, frequency_penalty=None):
+                       repetition_penalty=None, presence_penalty=None, frequency_penalty=None, logprobs=None):
         """``generate_cached`` for a list of 1-D prompts of unequal lengths, decoded as one
         batch with a position per row; returns a list of 1-D tensors (prompt + new tokens).
         A row that draws ``stop_token`` ends with it; the others get exactly
@@ -429,11 +489,13 @@ class GPT(nn.Module):
         at most B rows, a finished row taking the next prompt; results in prompt order.
         ``speculate=K`` / ``spec_ngram`` / ``spec_table``: speculative decoding, as in
         ``generate_cached``.  ``repetition_penalty`` / ``presence_penalty`` / ``frequency_penalty``: as in
-        ``generate_cached``, every row by the counts of its own text."""
+        ``generate_cached``, every row by the counts of its own text.  ``logprobs=N``: returns ``(results,
+        records)``, one ``ops.LogProbs`` per prompt over exactly its new tokens, the stop token included."""
         from ..runtime.decode import generate_batch
+        lpk = {} if logprobs is None else dict(logprobs=logprobs)
         return generate_batch(self, prompts, max_new_tokens, temperature=temperature, top_k=top_k,
                               stop_token=stop_token, use_graph=use_graph, decoder=decoder, top_p=top_p, min_p=min_p,
                               quantize=quantize, kv_quantize=kv_quantize, shared_prompt=shared_prompt,
                               shared_prefix=shared_prefix, batch_size=batch_size, speculate=speculate,
                               spec_ngram=spec_ngram, spec_table=spec_table, repetition_penalty=repetition_penalty,
-                              presence_penalty=presence_penalty, frequency_penalty=frequency_penalty)
+                              presence_penalty=presence_penalty, frequency_penalty=frequency_penalty, **lpk)

@@ -93,6 +93,10 @@ _SIGNATURES = {
                              c_void_p, c_void_p, c_void_p, c_int, c_float, c_float, c_float, c_void_p],
     # token histograms: idx, n, S, lengths, rows, counts, B, ld, V, accumulate
     "nsa_token_counts": [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p],
+    # log-probabilities (csrc/kernels/logprob.hip): logits, bf16, M, V, ld, ids, tok, pos, pos_stride, last, lp,
+    # top_ids, top_lp, out_ld, N
+    "nsa_token_logprobs": [c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                           c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p],
     # row-mapped appends: qkv, caches, rows, pos0, n, B, S, H, D, Tmax
     "nsa_kv_append_rows": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                            c_void_p],

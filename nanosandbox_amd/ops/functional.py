@@ -1765,6 +1765,134 @@ def sample_topk_(logits, temperature: float, top_k, salt: int, pos, tok, gen, sa
         done.view(B)[live & (pos.view(-1).expand(B) >= end.view(B))] = 1
 
 
+LOGPROB_MAX_TOP = 8  # alternatives per token (csrc/kernels/logprob.hip LP_MAX_TOP)
+
+
+class LogProbs(NamedTuple):
+    """Log-probabilities of tokens under the model's own distribution (``token_logprobs`` states
+    the rule): ``token`` [..., n] fp32, the log-probability of every token; ``top_ids`` [..., n, N]
+    int32 and ``top`` [..., n, N] fp32, the N most likely ids at that place and their
+    log-probabilities (N = 0: empty).  A place that was skipped holds NaN (``top_ids``: -1)."""
+    token: torch.Tensor
+    top_ids: torch.Tensor
+    top: torch.Tensor
+
+    def perplexity(self) -> torch.Tensor:
+        """exp(-mean log-probability) over the last dimension, skipped (NaN) places left out."""
+        ok = ~torch.isnan(self.token)
+        total = torch.where(ok, self.token, torch.zeros_like(self.token)).sum(-1)
+        return torch.exp(-total / ok.sum(-1).clamp(min=1))
+
+
+def check_logprobs(logprobs):
+    """Validate a ``logprobs`` setting: None (off) or a number of alternatives in 0 .. 8 -> None or int."""
+    if logprobs is None:
+        return None
+    if isinstance(logprobs, bool) or int(logprobs) != logprobs or not 0 <= int(logprobs) <= LOGPROB_MAX_TOP:
+        raise ValueError(f"logprobs must be None or an int in 0 .. {LOGPROB_MAX_TOP} alternatives, got {logprobs!r}")
+    return int(logprobs)
+
+
+def _logprob_rule(l, ids, top):
+    """The rule of ``token_logprobs`` on fp32 ``l`` [M, V] for in-range ``ids`` -> (lp, top_ids, top_lp)."""
+    M, V = l.shape
+    m = l.max(dim=-1, keepdim=True).values
+    lse = torch.log(torch.exp(l - m).sum(dim=-1, keepdim=True))
+    lp = ((l.gather(1, ids.view(M, 1)) - m) - lse).view(M)
+    top_ids = torch.full((M, top), -1, dtype=torch.int32, device=l.device)
+    top_lp = torch.full((M, top), -float("Inf"), dtype=torch.float32, device=l.device)
+    if top:
+        ls, order = torch.sort(l, dim=-1, descending=True, stable=True)
+        n = min(top, V)
+        top_ids[:, :n] = order[:, :n].to(torch.int32)
+        top_lp[:, :n] = (ls[:, :n] - m) - lse
+    return lp, top_ids, top_lp
+
+
+def token_logprobs(logits, ids, top: int = 0, V: int | None = None, out=None) -> LogProbs:
+    """Log-probabilities of given tokens under raw logits.  ``logits`` [M, >= V] (fp32 or bf16 on
+    the kernel's path, unit column stride, any row stride), ``ids`` int64 [M], ``V`` the number of
+    columns that are ids (default: all; the lm_head's padding columns are not ids).  For every row
+    r with ``0 <= ids[r] < V``, with l the row's first V logits in fp32 and m = max_j l[j]::
+
+        token[r] = (l[ids[r]] - m) - log(sum_j exp(l[j] - m))
+
+    and, with ``top`` = N (0 .. 8), ``top_ids[r, :N]`` (int32) are the N most likely ids in the order
+    (logit descending, id ascending), which is ``torch.sort(l, descending=True, stable=True)``: logits
+    compare as floats, so -0.0 ties with 0.0 and the lower id wins; ``top[r, :N]`` are their
+    log-probabilities by the same formula.  Slots past V (N > V) hold id -1 and -inf.  A row whose id
+    is out of range (-1, in the manner of ``ignore_index``) is skipped: nothing of its outputs is
+    written (``out``: a ``LogProbs`` of [M], [M, N] and [M, N] buffers to write into; without it
+    fresh ones, where a skipped row holds NaN and id -1).  -inf logits are allowed as long as the
+    row's maximum is finite; NaN is not supported.
+
+    These are the raw logits the sampler is handed, before penalties, temperature and the top-k /
+    top-p / min-p filters: the model's own distribution.  It does not depend on how one samples,
+    and it is the same quantity ``GPT.score`` returns for a given text.
+
+    On the GPU one launch of ``nsa_token_logprobs`` (a workgroup per row, one fixed summation
+    order, so equal rows give equal bits whatever the launch); on the CPU, and for other dtypes,
+    this rule in torch, in fp32."""
+    top = check_logprobs(top)
+    assert logits.dim() == 2 and ids.dim() == 1 and ids.shape[0] == logits.shape[0] and ids.dtype == torch.int64
+    M = logits.shape[0]
+    V = logits.shape[1] if V is None else int(V)
+    assert 1 <= V <= logits.shape[1]
+    if out is None:
+        out = LogProbs(torch.full((M,), float("nan"), dtype=F32, device=logits.device),
+                       torch.full((M, top), -1, dtype=torch.int32, device=logits.device),
+                       torch.full((M, top), float("nan"), dtype=F32, device=logits.device))
+    lp, top_ids, top_lp = out
+    assert lp.shape == (M,) and lp.dtype == F32 and lp.is_contiguous()
+    assert top_ids.shape == (M, top) and top_ids.dtype == torch.int32 and top_ids.is_contiguous()
+    assert top_lp.shape == (M, top) and top_lp.dtype == F32 and top_lp.is_contiguous()
+    if M == 0:
+        return LogProbs(lp, top_ids, top_lp)
+    if logits.is_cuda and logits.dtype in (F32, BF16) and logits.stride(1) == 1:
+        _lib.call("nsa_token_logprobs", _lib.ptr(logits), 1 if logits.dtype == BF16 else 0, M, V, logits.stride(0),
+                  _lib.ptr(ids.contiguous()), None, None, 0, None, _lib.ptr(lp), _lib.ptr(top_ids) if top else None,
+                  _lib.ptr(top_lp) if top else None, 1, top, _lib.stream())
+        return LogProbs(lp, top_ids, top_lp)
+    rows = ((ids >= 0) & (ids < V)).nonzero().view(-1)
+    if rows.numel():
+        a, b, c = _logprob_rule(logits[rows, :V].float(), ids[rows], top)
+        lp[rows], top_ids[rows], top_lp[rows] = a, b, c
+    return LogProbs(lp, top_ids, top_lp)
+
+
+def token_logprobs_step_(logits, tok, pos, last, lp, top_ids, top_lp, V: int | None = None):
+    """The decoder's form of ``token_logprobs``, run right after the sampler: row b's token is
+    ``tok[b]`` and its place ``p = pos[b]`` (``pos``: int64 with B entries, or one shared entry), and
+    ``lp[b, p]``, ``top_ids[b, p, :]`` and ``top_lp[b, p, :]`` (fp32 [B, L], int32 / fp32 [B, L, N]: shaped
+    and indexed like ``gen``) receive what ``token_logprobs`` gives for (``logits[b]``, ``tok[b]``).
+    ``last`` (int64 [B]) is the place every row recorded last: a row with ``last[b] == p`` records
+    nothing (it was finished before this sampler call, so neither its place nor its token
+    moved) and every other row sets ``last[b] = p``; a text's (row, place) pairs are sampled once
+    each, so a row that finishes in this call still records its last token.  One launch on the
+    GPU (graph-capturable), torch elsewhere."""
+    B = logits.shape[0]
+    V = logits.shape[1] if V is None else int(V)
+    N = top_ids.shape[-1]
+    assert lp.dim() == 2 and lp.shape[0] == B and lp.dtype == F32 and lp.is_contiguous()
+    assert top_ids.shape == (*lp.shape, N) and top_ids.dtype == torch.int32 and top_ids.is_contiguous()
+    assert top_lp.shape == top_ids.shape and top_lp.dtype == F32 and top_lp.is_contiguous()
+    assert tok.numel() == B and tok.dtype == torch.int64 and tok.is_contiguous()
+    assert last.numel() == B and last.dtype == torch.int64 and last.is_contiguous()
+    assert pos.numel() in (1, B) and pos.dtype == torch.int64 and 0 <= N <= LOGPROB_MAX_TOP
+    if logits.is_cuda:
+        lg = logits if logits.dtype in (F32, BF16) and logits.stride(1) == 1 else logits.float().contiguous()
+        _lib.call("nsa_token_logprobs", _lib.ptr(lg), 1 if lg.dtype == BF16 else 0, B, V, lg.stride(0), None,
+                  _lib.ptr(tok), _lib.ptr(pos), 1 if pos.numel() > 1 else 0, _lib.ptr(last), _lib.ptr(lp),
+                  _lib.ptr(top_ids) if N else None, _lib.ptr(top_lp) if N else None, lp.shape[1], N, _lib.stream())
+        return
+    p = pos.view(-1).expand(B)
+    rows = (last.view(B) != p).nonzero().view(-1)
+    if rows.numel():
+        a, b, c = _logprob_rule(logits[rows, :V].float(), tok.view(B)[rows], N)
+        lp[rows, p[rows]], top_ids[rows, p[rows]], top_lp[rows, p[rows]] = a, b, c
+        last.view(B)[rows] = p[rows]
+
+
 def advance_pos_(pos, done):
     """The per-row decode step's position update: ``pos[b] += 1`` for every row with
     ``done[b] == 0`` (int64 [B] each); a finished row stays where it is.  One tiny kernel
@@ -2078,3 +2206,11 @@ def lm_head_logits(x, w):
         return y[:, :V].float().view(*x.shape[:-1], V)
     wc = compute_weight(w, x.dtype)
     return (x @ wc.t()).float()
+
+
+def lm_head_logits_padded(x, w):
+    """The lm_head GEMM's own result for bf16 ``x`` [M, C] on the GPU: bf16 [M, lm_head_rows(V)], the
+    padding columns included and nothing converted (``lm_head_logits`` slices and widens this)."""
+    assert x.is_cuda and x.dtype == BF16 and x.dim() == 2
+    wp, _ = _lm_weight(w)
+    return _gd.fwd(x.contiguous(), wp)

@@ -119,6 +119,21 @@ fp)``.  With per_row, ``stop_token``, ``top_p`` / ``min_p``, both quantizations,
 ``shared_prefix``, the queue and eager mode; ``speculate`` raises ValueError (a verified position's
 counts would have to include the drafts before it).  Without ``penalize`` there is no table
 (``cnt`` is None) and every launch, graph key and result is what it was.
+``Decoder(..., logprobs=N)`` (0 .. 8; None: off) records how likely the model found every token it
+drew: ``lp[b, p]`` (fp32 [B, block_size + 1], indexed like ``gen``) is the log-probability of ``gen[b, p]``
+under the raw logits the sampler was handed, before penalties, temperature and filters: the model's
+own distribution, the quantity ``GPT.score`` returns for a given text (``ops.token_logprobs`` states
+the rule), and with N > 0 ``top_ids[b, p, :]`` / ``top_lp[b, p, :]`` hold the N most likely ids there and
+their log-probabilities.  One more launch per draw, right after the sampler inside ``sample_into``
+(``ops.token_logprobs_step_``), so the prefill's first token, the eager step and every captured graph
+record alike, and ``sample_admitted`` does the same.  ``lp_last`` (int64 [B]) is the position every row
+recorded last; a row whose position has not moved since (it was finished before this sampler call)
+records nothing, a row that finishes in this call still records its last token, and every prefill
+form and ``admit`` put the rows they start back to -1.  The graph key gains ``("lp", N)``.  With
+per_row, ``stop_token``, ``top_p`` / ``min_p``, the penalties, both quantizations, ``shared_prompt`` /
+``shared_prefix``, the queue and eager mode; ``speculate`` raises ValueError (a verified position can
+be written by more than one step).  Without ``logprobs`` there are no buffers (``lp`` is None) and
+every launch, graph key and result is what it was.
 The caches hold at most ``block_size`` positions; ``GPT.generate_cached`` falls
 back to the recompute loop when prompt + new tokens exceed that (nanoGPT crops the
 context there, which a cache cannot do without re-encoding).
@@ -169,6 +184,15 @@ def _check_spec(speculate, spec_ngram=3, kv_quantize=None, shared_prompt=False, 
     return K, N
 
 
+def _check_logprobs(logprobs, speculate=None):
+    """``logprobs`` validated (None: off; 0 .. 8 alternatives); ValueError with speculation."""
+    logprobs = ops.check_logprobs(logprobs)
+    if logprobs is not None and int(speculate or 0):
+        raise ValueError("speculate cannot be combined with logprobs: a verified position can be written by more "
+                         "than one step")
+    return logprobs
+
+
 def _stop(stop_token):
     """A stop token < 0 means none."""
     return None if stop_token is None or stop_token < 0 else stop_token
@@ -178,8 +202,9 @@ class Decoder:
     def __init__(self, model, batch_size: int, max_len: int | None = None, use_graph: bool | None = None,
                  per_row: bool = False, quantize: str | None = None, kv_quantize: str | None = None,
                  shared_prompt: bool = False, max_new: int | None = None, speculate: int | None = None,
-                 spec_ngram: int = 3, penalize: bool = False):
+                 spec_ngram: int = 3, penalize: bool = False, logprobs: int | None = None):
         _check_mode(quantize, kv_quantize, shared_prompt)
+        logprobs = _check_logprobs(logprobs, speculate)
         self.K, self.N = _check_spec(speculate, spec_ngram, kv_quantize, shared_prompt)
         if self.K and penalize:
             raise ValueError("speculate cannot be combined with sampling penalties: a verified position's counts "
@@ -293,6 +318,16 @@ class Decoder:
             self.cnt = torch.zeros(batch_size, -(-cfg.vocab_size // 4) * 4, device=self.device, dtype=torch.int32)
             if shared_prompt:
                 self.cnt0 = torch.zeros(1, self.cnt.shape[1], device=self.device, dtype=torch.int32)
+        # logprobs: the drawn tokens' log-probabilities and the N alternatives, indexed like gen, and the
+        # position every row recorded last (-1: none yet)
+        self.logprobs = logprobs
+        self.lp = self.top_ids = self.top_lp = self.lp_last = None
+        if logprobs is not None:
+            self.lp = torch.full((batch_size, self.T + 1), float("nan"), device=self.device, dtype=torch.float32)
+            self.top_ids = torch.full((batch_size, self.T + 1, logprobs), -1, device=self.device, dtype=torch.int32)
+            self.top_lp = torch.full((batch_size, self.T + 1, logprobs), float("nan"), device=self.device,
+                                     dtype=torch.float32)
+            self.lp_last = torch.full((batch_size,), -1, device=self.device, dtype=torch.int64)
         self.use_graph = (self.device.type == "cuda") if use_graph is None else use_graph
         if self.use_graph and not self.graph_capable(model):
             # the fused decode kernels cover head_dim 64, bf16 and V <= 53248; the fallback
@@ -326,17 +361,17 @@ class Decoder:
                 and cfg.vocab_size <= 53248)
 
     def fits(self, batch_size, per_row=False, quantize=None, kv_quantize=None, shared_prompt=False,
-             max_new=None, speculate=None, spec_ngram=3, penalize=False) -> bool:
+             max_new=None, speculate=None, spec_ngram=3, penalize=False, logprobs=None) -> bool:
         """Whether a call that needs ``Decoder(model, batch_size, per_row=..., ...)`` can run on this
         one: the same rows and form, (shared) row caches of at least ``max_new`` slots, and the same
         number of drafted tokens and n-gram length (speculative), and a count table if and only if
-        the call penalises."""
+        the call penalises, and the log-probability buffers of the call's N alternatives, or none."""
         K = int(speculate or 0)
         return (self.B == batch_size and self.per_row == bool(per_row or K) and self.quantize == quantize
                 and self.kv_quantize == kv_quantize and self.shared == bool(shared_prompt)
                 and (not self.shared or self.R >= (max_new or self.T))
                 and self.K == K and (not K or self.N == int(spec_ngram))
-                and (self.cnt is not None) == bool(penalize))
+                and (self.cnt is not None) == bool(penalize) and self.logprobs == logprobs)
 
     def _quantize_weights(self):
         """int8 mode: quantize every linear weight and the tied lm_head / wte table, and point
@@ -556,6 +591,7 @@ class Decoder:
             ops.token_counts_(self.cnt, idx, lengths, rows, accumulate=bool(first))
         if first:
             self.plen.fill_(first)
+        self._lp_reset(rows)
         if rows is not None:
             self.pos.index_copy_(0, rows, lengths)
             self.done.index_fill_(0, rows, 0)
@@ -571,6 +607,16 @@ class Decoder:
         else:
             last = h[torch.arange(n, device=self.device), lengths - 1].unsqueeze(1)  # [n, 1, C]
         return ops.lm_head_logits(last, self.model.lm_head.weight)[:, 0]
+
+    def _lp_reset(self, rows=None):
+        """The rows' texts start over (``rows``: those rows, else all): nothing recorded yet."""
+        if self.lp is None:
+            return
+        for t, v in ((self.lp, float("nan")), (self.top_ids, -1), (self.top_lp, float("nan")), (self.lp_last, -1)):
+            if rows is None:
+                t.fill_(v)
+            else:
+                t.index_fill_(0, rows, v)
 
     @torch.no_grad()
     def prefill(self, idx: torch.Tensor, lengths: torch.Tensor | None = None) -> torch.Tensor:
@@ -616,6 +662,7 @@ class Decoder:
         self.pos.fill_(T0)
         if self.per_row:
             self.done.zero_()
+        self._lp_reset()
         if self.cnt is not None:
             self.cnt.copy_(self.cnt0.expand(self.B, -1))
         return self._prompt_logits.expand(self.B, -1)
@@ -670,6 +717,7 @@ class Decoder:
             assert self._prompt is not None, "admit follows prefill_shared(prompt)"
             self.pos.index_copy_(0, rows, self.plen.expand(n))
             self.done.index_fill_(0, rows, 0)
+            self._lp_reset(rows)
             if self.cnt is not None:  # nothing of the row's previous request survives
                 self.cnt.index_copy_(0, rows, self.cnt0.expand(n, -1))
             return self._prompt_logits.expand(n, -1)
@@ -721,6 +769,7 @@ class Decoder:
         ops.sample_topk_(full, temperature, top_k, self.salt, self.pos, self.tok, self.gen, salt_dev=self.salt_dev,
                          stop_token=stop_token, done=mask, top_p=top_p, min_p=min_p, row_key=self.key, end=self.end,
                          **pen)
+        self._record(full)  # the admitted rows alone: every other row's position is the one it recorded last
         self.done.index_copy_(0, rows, mask[rows])
 
     @torch.no_grad()
@@ -742,7 +791,8 @@ class Decoder:
         prompts go into all freed rows in one ``admit`` call.  Request i samples with ``key`` i, so
         its draws depend on neither the row nor the schedule, and ends at position ``L_i + N_i -
         1`` (``end``).  ``queue_stats``: ``steps`` run, ``admissions`` (admit calls) and requests
-        ``admitted``."""
+        ``admitted``.  A decoder with ``logprobs=N`` returns ``(tokens, records)``: every request's
+        ``ops.LogProbs`` is harvested with its ids, ``records[i]`` covering exactly ``tokens[i]``."""
         assert self.per_row, "serve needs Decoder(..., per_row=True)"
         if self.K:
             raise ValueError("a speculative decoder does not serve a queue")
@@ -761,13 +811,16 @@ class Decoder:
         self.queue_stats = stats = {"steps": 0, "admissions": 0, "admitted": 0}
         outs: list = [None] * nreq
         if not nreq:
-            return outs
+            return outs if self.lp is None else (outs, [])
         B = self.B
         if self.shared:
             self.prefill_shared(prompts[0])  # every row at the prompt's end: a valid place to idle
         else:
             self.pos.zero_()
         self.done.fill_(1)  # no row serves a request yet; an idle row is a frozen one
+        if self.lp is not None:
+            self.lp_last.copy_(self.pos)  # ... and records nothing until it is admitted
+        lps: list = [None] * nreq
         owner = [None] * B  # the request a row serves
         left = [0] * B      # an upper bound of the steps the row still needs
         nxt = 0
@@ -806,12 +859,14 @@ class Decoder:
                     continue
                 if done[b]:
                     outs[i] = self.gen[b, lens[i]:pos[b] + 1].clone()
+                    if self.lp is not None:
+                        lps[i] = self.records(b, lens[i], pos[b] + 1)
                     owner[b] = None
                 else:
                     left[b] = lens[i] + budgets[i] - 1 - pos[b]
             fill()
             if all(o is None for o in owner):
-                return outs
+                return outs if self.lp is None else (outs, lps)
 
     def _step_impl(self):
         return self._decode_layers()[:, 0]  # also advances pos
@@ -841,6 +896,8 @@ class Decoder:
         spec = [(t, t.clone()) for t in (self.stok, self.spos, self.cpos, self.spec_counts)] if self.K else []
         if self.cnt is not None:  # a warm-up draw is counted: the table is put back as well
             spec.append((self.cnt, self.cnt.clone()))
+        if self.lp is not None:  # a warm-up draw is recorded: the records and the marker are put back too
+            spec += [(t, t.clone()) for t in (self.lp, self.top_ids, self.top_lp, self.lp_last)]
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
@@ -881,6 +938,14 @@ class Decoder:
         ops.sample_topk_(logits, temperature, top_k, self.salt, self.pos, self.tok, self.gen, salt_dev=self.salt_dev,
                          stop_token=stop_token, done=self.done, top_p=top_p, min_p=min_p,
                          row_key=self.key if queue else None, end=self.end if queue else None, **pen)
+        self._record(logits)
+
+    def _record(self, logits):
+        """logprobs: the log-probability of the token every row has just drawn from the raw ``logits``
+        [B, V], and the alternatives, at ``pos`` (``ops.token_logprobs_step_``: one launch)."""
+        if self.lp is not None:
+            ops.token_logprobs_step_(logits, self.tok, self.pos, self.lp_last, self.lp, self.top_ids, self.top_lp,
+                                     V=self.model.config.vocab_size)
 
     def reseed(self):
         """A fresh sampling stream for the next generate call (torch.manual_seed governs)."""
@@ -904,7 +969,8 @@ class Decoder:
         (``serve``): the sampler reads ``key`` and ``end``, a graph of its own (the key gains
         ``"queue"``); without it the graphs and their keys are the ones there always were.  The
         three penalties: as in ``sample_into``; on a penalising decoder the key gains ``("pen", rp,
-        pp, fp)``, the identity (1, 0, 0) when none is passed."""
+        pp, fp)``, the identity (1, 0, 0) when none is passed.  A decoder with ``logprobs=N`` records
+        every draw (``lp`` / ``top_ids`` / ``top_lp``) and its key gains ``("lp", N)``."""
         stop_token = _stop(stop_token)
         assert stop_token is None or self.per_row, "a stop token needs Decoder(..., per_row=True)"
         top_p, min_p = sampling_filters(top_p, min_p)
@@ -923,6 +989,8 @@ class Decoder:
                 key += ("queue",)
             if drawn:
                 key += ("pen", drawn["repetition_penalty"], drawn["presence_penalty"], drawn["frequency_penalty"])
+            if self.logprobs is not None:
+                key += ("lp", self.logprobs)
             if key not in self.sgraphs:
                 self.sgraphs[key], _ = self._capture(step)
             step = self.sgraphs[key].replay
@@ -967,6 +1035,12 @@ class Decoder:
             left = max([e - p for d, p, e in zip(done, pos, end) if not d], default=0)
         if self.use_graph:
             self.replays += ran
+
+    def records(self, rows, first: int, stop: int) -> "ops.LogProbs":
+        """A copy of what was recorded for positions first .. stop - 1 of ``rows`` (an index or a slice)."""
+        assert self.lp is not None, "records needs Decoder(..., logprobs=N)"
+        return ops.LogProbs(self.lp[rows, first:stop].clone(), self.top_ids[rows, first:stop].clone(),
+                            self.top_lp[rows, first:stop].clone())
 
     @property
     def position(self) -> int:
@@ -1026,12 +1100,15 @@ def sample_next(logits: torch.Tensor, temperature: float = 1.0, top_k: int | Non
     return torch.multinomial(probs, num_samples=1, generator=generator)
 
 
-def _mode(B, per_row=False, quantize=None, kv_quantize=None, slots=None, spec=(0, 3), penalize=False) -> dict:
+def _mode(B, per_row=False, quantize=None, kv_quantize=None, slots=None, spec=(0, 3), penalize=False,
+          logprobs=None) -> dict:
     """The decoder a call needs, as ``Decoder``'s arguments (and ``Decoder.fits``'s): B rows, per_row
     or not, the two quantizations, ``slots``, the row-cache slots of a shared_prompt decoder
     (None: an unshared one), ``spec``, the (K, N) of ``_check_spec`` (K > 0: a speculative
     one, which is per_row), and ``penalize``: one with a count table, for a call with a penalty on
-    (which speculation does not compose with: ValueError)."""
+    (which speculation does not compose with: ValueError), and ``logprobs``: one with the
+    log-probability buffers of that many alternatives (None: without; with speculation: ValueError)."""
+    logprobs = _check_logprobs(logprobs, spec[0])
     mode = dict(batch_size=B, per_row=per_row, quantize=quantize, kv_quantize=kv_quantize,
                 shared_prompt=slots is not None, max_new=slots)
     if spec[0]:
@@ -1041,6 +1118,8 @@ def _mode(B, per_row=False, quantize=None, kv_quantize=None, slots=None, spec=(0
         mode.update(per_row=True, speculate=spec[0], spec_ngram=spec[1])
     if penalize:
         mode.update(penalize=True)
+    if logprobs is not None:
+        mode.update(logprobs=logprobs)
     return mode
 
 
@@ -1069,9 +1148,10 @@ def _nothing_to_share(sharing, L, N, T):
 
 
 def _cached_mode(model, idx, max_new_tokens, quantize, kv_quantize, shared_prompt, speculate=None, spec_ngram=3,
-                 penalize=False):
+                 penalize=False, logprobs=None):
     """The mode of the decoder ``generate_cached`` runs this call on (None: the recompute loop).
-    ``penalize``: the call has a penalty on."""
+    ``penalize``: the call has a penalty on; ``logprobs``: it wants the log-probabilities."""
+    logprobs = _check_logprobs(logprobs, speculate)
     B, T0 = idx.shape
     T = model.config.block_size
     _check_mode(quantize, kv_quantize, shared_prompt)
@@ -1084,7 +1164,7 @@ def _cached_mode(model, idx, max_new_tokens, quantize, kv_quantize, shared_promp
         if B > 1:  # a single row goes the ordinary way
             if T0 + max_new_tokens > T:
                 raise _nothing_to_share("shared_prompt", T0, max_new_tokens, T)
-            return _mode(B, False, quantize, slots=max_new_tokens, penalize=penalize)
+            return _mode(B, False, quantize, slots=max_new_tokens, penalize=penalize, logprobs=logprobs)
     if T0 + max_new_tokens - 1 > T:
         if quantize:
             raise ValueError("quantize needs the KV-cache path: prompt + new tokens exceed block_size, and the "
@@ -1096,22 +1176,23 @@ def _cached_mode(model, idx, max_new_tokens, quantize, kv_quantize, shared_promp
             raise ValueError("speculate needs the KV-cache path: prompt + new tokens exceed block_size, and the "
                              "recompute loop decodes one token per pass")
         return None
-    return _mode(B, False, quantize, kv_quantize, spec=spec, penalize=penalize)
+    return _mode(B, False, quantize, kv_quantize, spec=spec, penalize=penalize, logprobs=logprobs)
 
 
 def cached_decoder(model, idx, max_new_tokens, use_graph=None, quantize=None, kv_quantize=None, shared_prompt=False,
                    speculate=None, spec_ngram=3, repetition_penalty=None, presence_penalty=None,
-                   frequency_penalty=None):
+                   frequency_penalty=None, logprobs=None):
     """The Decoder this ``generate_cached`` call would build, for a caller that keeps it across
     calls (``decoder=``) and releases it.  A call that runs on none (no new tokens, or the
     recompute loop) gets the ordinary one all the same, as ``sample.py`` always has: building it
     draws from torch's generator, and a seeded run keeps its tokens.  With a penalty on it is a
-    penalising one."""
+    penalising one, with ``logprobs`` one that records them."""
     pen = sampling_penalties(repetition_penalty, presence_penalty, frequency_penalty) is not None
     mode = max_new_tokens > 0 and _cached_mode(model, idx, max_new_tokens, quantize, kv_quantize, shared_prompt,
-                                               speculate, spec_ngram, pen)
+                                               speculate, spec_ngram, pen, logprobs)
     return _build(model, mode or _mode(idx.shape[0], False, quantize, kv_quantize,
-                                       spec=_check_spec(speculate, spec_ngram, kv_quantize), penalize=pen), use_graph)
+                                       spec=_check_spec(speculate, spec_ngram, kv_quantize), penalize=pen,
+                                       logprobs=logprobs), use_graph)
 
 
 @torch.no_grad()
@@ -1122,8 +1203,16 @@ def generate_cached(model, idx: torch.Tensor, max_new_tokens: int, temperature: 
                     kv_quantize: str | None = None, shared_prompt: bool = False,
                     speculate: int | None = None, spec_ngram: int = 3, spec_table=None,
                     repetition_penalty: float | None = None, presence_penalty: float | None = None,
-                    frequency_penalty: float | None = None) -> torch.Tensor:
+                    frequency_penalty: float | None = None, logprobs: int | None = None):
     """``model.generate`` with KV caches: same sampling, one token's forward per new token.
+
+    ``logprobs=N`` (0 .. 8; None: off): the call returns ``(tokens, ops.LogProbs)``, the second covering
+    exactly the new tokens: ``token`` [B, n] is the log-probability of every drawn token under the
+    model's raw logits (before penalties, temperature and filters; ``ops.token_logprobs``), ``top_ids`` /
+    ``top`` [B, n, N] the N most likely ids and theirs.  It runs on a decoder that records them
+    (``Decoder(..., logprobs=N)``: one more launch per token, inside the captured step; the tokens are
+    those of the call without it), past block_size the recompute loop fills it through the same op.
+    ValueError with ``speculate``.  Without the keyword the return value is the tokens alone.
 
     ``repetition_penalty`` / ``presence_penalty`` / ``frequency_penalty`` (``ops.penalize_logits``; 1, 0
     and 0 or None: off): with one of them on the call runs on a penalising decoder
@@ -1156,22 +1245,31 @@ def generate_cached(model, idx: torch.Tensor, max_new_tokens: int, temperature: 
     with one that does not fit, a temporary decoder is built and released here."""
     T0 = idx.shape[1]
     top_p, min_p = sampling_filters(top_p, min_p)
+    logprobs = _check_logprobs(logprobs, speculate)
     if max_new_tokens <= 0:
-        return idx
+        return idx if logprobs is None else (idx, _no_records(idx.shape[0], logprobs, idx.device))
     pen = _pen_kw(sampling_penalties(repetition_penalty, presence_penalty, frequency_penalty))
     mode = _cached_mode(model, idx, max_new_tokens, quantize, kv_quantize, shared_prompt, speculate, spec_ngram,
-                        bool(pen))
+                        bool(pen), logprobs)
     if mode is None:
         # the caches hold block_size positions; nanoGPT crops the context beyond that
+        lpk = {} if logprobs is None else dict(logprobs=logprobs)
         return model.generate(idx, max_new_tokens, temperature=temperature, top_k=top_k, top_p=top_p, min_p=min_p,
-                              **pen)
+                              **pen, **lpk)
     with _borrow(model, mode, decoder, use_graph) as dec:
         if dec.K:
             dec.set_draft_table(spec_table)
         logits = dec.prefill_shared(idx[0]) if dec.shared else dec.prefill(idx)
         dec.sample_into(logits, temperature, top_k, None, top_p, min_p, **pen)  # pos = T0: gen[:, T0]
         dec.run(max_new_tokens - 1, temperature, top_k, None, top_p, min_p, **pen)
-        return torch.cat([idx, dec.gen[:, T0:T0 + max_new_tokens]], dim=1)
+        out = torch.cat([idx, dec.gen[:, T0:T0 + max_new_tokens]], dim=1)
+        return out if logprobs is None else (out, dec.records(slice(None), T0, T0 + max_new_tokens))
+
+
+def _no_records(B, N, device) -> "ops.LogProbs":
+    """The records of no new tokens."""
+    return ops.LogProbs(torch.zeros(B, 0, device=device), torch.zeros(B, 0, N, dtype=torch.int32, device=device),
+                        torch.zeros(B, 0, N, device=device))
 
 
 def _right_pad(prompts, device):
@@ -1204,7 +1302,7 @@ def common_prefix_len(prompts) -> int:
 
 
 def _batch_plan(model, prompts, max_new_tokens, quantize, kv_quantize, shared_prompt, shared_prefix, batch_size,
-                speculate=None, spec_ngram=3, penalize=False):
+                speculate=None, spec_ngram=3, penalize=False, logprobs=None):
     """What ``generate_batch`` does with a call -> (prompts, budgets, queue, fit, P, mode): the
     flattened prompts on the model's device, every prompt's budget of new tokens, whether they are
     served as a queue, the indices of the prompts that share the decoder (the others go alone), the
@@ -1224,6 +1322,7 @@ def _batch_plan(model, prompts, max_new_tokens, quantize, kv_quantize, shared_pr
                 raise ValueError(f"every budget must be at least 1, got {budgets}")
     _check_mode(quantize, kv_quantize, shared_prompt, shared_prefix)
     spec = _check_spec(speculate, spec_ngram, kv_quantize, shared_prompt, shared_prefix, queue)
+    logprobs = _check_logprobs(logprobs, spec[0])
     if spec[0] and penalize:
         _mode(len(prompts), True, spec=spec, penalize=True)  # raises
     assert all(p.numel() >= 1 for p in prompts), "every prompt needs at least one token"
@@ -1253,22 +1352,23 @@ def _batch_plan(model, prompts, max_new_tokens, quantize, kv_quantize, shared_pr
     if sharing and B >= 2:  # a single row goes the ordinary way
         # a row's cache holds what follows the shared tokens: its suffix, if any, and its new tokens
         slots = max(budgets[i] + (prompts[i].numel() - P if P else 0) for i in fit)
-    return prompts, budgets, queue, fit, P, _mode(B, True, quantize, kv_quantize, slots, spec, penalize)
+    return prompts, budgets, queue, fit, P, _mode(B, True, quantize, kv_quantize, slots, spec, penalize, logprobs)
 
 
 def batch_decoder(model, prompts, max_new_tokens, use_graph=None, quantize=None, kv_quantize=None,
                   shared_prompt=False, shared_prefix=False, batch_size=None, speculate=None, spec_ngram=3,
-                  repetition_penalty=None, presence_penalty=None, frequency_penalty=None):
+                  repetition_penalty=None, presence_penalty=None, frequency_penalty=None, logprobs=None):
     """The Decoder this ``generate_batch`` call would build, for a caller that keeps it across
     calls (``decoder=``; a shared one then keeps the prompt or prefix too) and releases it.  A call
     that shares none (no new tokens, or no prompt that fits the cache) gets the ordinary one of a
     row per prompt, for the reason ``cached_decoder`` gives.  With a penalty on it is a penalising one."""
     pen = sampling_penalties(repetition_penalty, presence_penalty, frequency_penalty) is not None
     plan = _batch_plan(model, prompts, max_new_tokens, quantize, kv_quantize, shared_prompt, shared_prefix, batch_size,
-                       speculate, spec_ngram, pen)
+                       speculate, spec_ngram, pen, logprobs)
     mode = plan and plan[-1]
     return _build(model, mode or _mode(len(prompts), True, quantize, kv_quantize,
-                                       spec=_check_spec(speculate, spec_ngram, kv_quantize), penalize=pen), use_graph)
+                                       spec=_check_spec(speculate, spec_ngram, kv_quantize), penalize=pen,
+                                       logprobs=logprobs), use_graph)
 
 
 @torch.no_grad()
@@ -1279,8 +1379,14 @@ def generate_batch(model, prompts, max_new_tokens, temperature: float = 1.0, top
                    kv_quantize: str | None = None, shared_prompt: bool = False,
                    shared_prefix: bool = False, batch_size: int | None = None, speculate: int | None = None,
                    spec_ngram: int = 3, spec_table=None, repetition_penalty: float | None = None,
-                   presence_penalty: float | None = None, frequency_penalty: float | None = None) -> list[torch.Tensor]:
+                   presence_penalty: float | None = None, frequency_penalty: float | None = None,
+                   logprobs: int | None = None):
     """Generate for a list of prompts of unequal lengths as one batch.
+
+    ``logprobs=N`` (0 .. 8; None: off): as in ``generate_cached``; the call returns ``(results, records)``,
+    ``records[i]`` the ``ops.LogProbs`` of prompt i's new tokens (``token`` [n_i], ``top_ids`` / ``top`` [n_i, N]),
+    trimmed through the stop token as the ids are, so the stop token's own log-probability is its
+    last entry.  A queue harvests a request's records with its ids.  ValueError with ``speculate``.
 
     ``repetition_penalty`` / ``presence_penalty`` / ``frequency_penalty``: as in ``generate_cached``; every
     row is penalised by the counts of its own prompt (prefix and suffix) and drawn tokens, a queue's
@@ -1339,26 +1445,35 @@ def generate_batch(model, prompts, max_new_tokens, temperature: float = 1.0, top
     ``shared_prefix=True``, ``batch_size < 1`` and a budget list of the wrong length or with an
     entry < 1 raise ValueError.  With ``batch_size=None`` and an int budget nothing changes."""
     pen = _pen_kw(sampling_penalties(repetition_penalty, presence_penalty, frequency_penalty))
+    logprobs = _check_logprobs(logprobs, speculate)
     plan = _batch_plan(model, prompts, max_new_tokens, quantize, kv_quantize, shared_prompt, shared_prefix, batch_size,
-                       speculate, spec_ngram, bool(pen))
+                       speculate, spec_ngram, bool(pen), logprobs)
     stop_token = _stop(stop_token)
     sampling = (temperature, top_k, stop_token, *sampling_filters(top_p, min_p))
     if plan is None:
-        return [p.view(-1) for p in prompts]
+        outs = [p.view(-1) for p in prompts]
+        return outs if logprobs is None else (outs, [_row(_no_records(1, logprobs, p.device), 0, 0) for p in outs])
     prompts, budgets, queue, fit, P, mode = plan
     outs: list = [None] * len(prompts)
+    lps: list = [None] * len(prompts)
     for i, p in enumerate(prompts):
         if i not in fit:  # alone through ``generate_cached``: the recompute loop, or a decoder of its own
             y = generate_cached(model, p[None], budgets[i], temperature=temperature, top_k=top_k, use_graph=use_graph,
                                 top_p=top_p, min_p=min_p, quantize=quantize, kv_quantize=kv_quantize,
                                 speculate=speculate, spec_ngram=spec_ngram,
-                                spec_table=None if spec_table is None else [spec_table[i]], **pen)[0]
-            outs[i] = _result(p, y[p.numel():], stop_token)
+                                spec_table=None if spec_table is None else [spec_table[i]], logprobs=logprobs, **pen)
+            if logprobs is not None:
+                y, rec = y
+            outs[i] = _result(p, y[0][p.numel():], stop_token)
+            if logprobs is not None:
+                lps[i] = _row(rec, 0, outs[i].numel() - p.numel())
     if not fit:
-        return outs
+        return outs if logprobs is None else (outs, lps)
     with _borrow(model, mode, decoder, use_graph) as dec:
         if queue:
             news = dec.serve([prompts[i] for i in fit], [budgets[i] for i in fit], *sampling, **pen)
+            if logprobs is not None:
+                news, recs = news
         else:
             if P:
                 dec.prefill_shared(prompts[0][:P])
@@ -1375,6 +1490,13 @@ def generate_batch(model, prompts, max_new_tokens, temperature: float = 1.0, top
             L = prompts[i].numel()
             outs[i] = (_result(prompts[i], news[b]) if queue else
                        _result(prompts[i], dec.gen[b, L:L + max_new_tokens], stop_token))
-    return outs
+            if logprobs is not None:  # exactly the new tokens, through the stop token
+                lps[i] = recs[b] if queue else dec.records(b, L, outs[i].numel())
+    return outs if logprobs is None else (outs, lps)
+
+
+def _row(rec, b, n) -> "ops.LogProbs":
+    """Row b of batched records, its first n entries."""
+    return ops.LogProbs(rec.token[b, :n], rec.top_ids[b, :n], rec.top[b, :n])
 
 

@@ -39,6 +39,12 @@ sample's text already holds), ``--presence_penalty=0.5`` (subtracted from them o
 ``--frequency_penalty=0.2`` (subtracted once per occurrence) discourage a sample from repeating itself
 (``ops.penalize_logits``: prompt and generated tokens count); on the GPU they are applied inside the
 sampling kernel's launch (``Decoder(penalize=True)``).  They compose with every mode but ``--speculate``.
+``--logprobs=N`` (0 .. 8; -1: off) prints under each sample the summed log-probability of its new tokens
+under the model's own distribution (the raw logits, before penalties, temperature and filters) and their
+perplexity, and with N > 0 every new token with its N most likely alternatives
+(``Decoder(logprobs=N)``: recorded by one more launch inside the decode step); every mode but
+``--speculate``.  ``--score=True`` with ``--prompts_file`` generates nothing: every line is scored
+(``GPT.score``) and printed with its summed log-probability, token count and perplexity.
 """
 
 from __future__ import annotations
@@ -51,7 +57,7 @@ import torch
 from .config import parse_argv
 from .data import load_meta, resolve_data_dir
 from .models import GPT, GPTConfig
-from .ops import check_sampling_filters, check_sampling_penalties
+from .ops import check_logprobs, check_sampling_filters, check_sampling_penalties
 from .utils import load_checkpoint, load_model_state
 
 SAMPLE_DEFAULTS = dict(
@@ -83,12 +89,56 @@ SAMPLE_DEFAULTS = dict(
     serve_batch=0,  # N > 0: all requests as one queue through N decoder rows, finished rows refilled (Decoder.serve); 0: off
     speculate=0,  # K > 0: speculative decoding, K tokens drafted per model pass (Decoder(speculate=K)); 0: off
     spec_ngram=3,  # speculate: the longest n-gram looked up in the row's own text for a draft
+    logprobs=-1,  # N >= 0: print each sample's log-probability and perplexity, N > 0 (<= 8): and N alternatives per token; -1: off
+    score=False,  # with prompts_file: score every line (GPT.score) instead of generating
 )
 
 
 def _penalties(c) -> dict:
     """The three penalty keys as the front ends' keywords."""
     return {k: c[k] for k in ("repetition_penalty", "presence_penalty", "frequency_penalty")}
+
+
+def _logprobs(c) -> dict:
+    """The ``logprobs`` keyword of the front ends (off: none, and they return the tokens alone)."""
+    return dict(logprobs=c["logprobs"]) if c["logprobs"] >= 0 else {}
+
+
+def _print_logprobs(rec, new, decode):
+    """Under a sample: the summed log-probability and perplexity of the ``new`` tokens that were printed
+    (``rec``: their ``ops.LogProbs``, possibly longer: a stop token is not printed), then every token
+    with its alternatives."""
+    n = len(new)
+    if not n:
+        return
+    tok = rec.token[:n].double()
+    print(f"logprob {float(tok.sum()):.4f} over {n} tokens, perplexity {float(torch.exp(-tok.mean())):.4f}")
+    if rec.top_ids.shape[-1]:
+        for i, t in enumerate(new):
+            alts = ", ".join(f"{decode([a])!r} {lp:.3f}" for a, lp in zip(rec.top_ids[i].tolist(), rec.top[i].tolist())
+                             if a >= 0)
+            print(f"  {decode([t])!r} {float(rec.token[i]):.3f} | {alts}")
+
+
+def _score_file(model, c, encode, device):
+    """score: every line of prompts_file through ``GPT.score`` as one right-padded batch."""
+    with open(c["prompts_file"], "r", encoding="utf-8") as f:
+        texts = [ln.rstrip("\n") for ln in f if ln.strip()]
+    ids = [encode(t) for t in texts]
+    if min(len(i) for i in ids) < 2:
+        raise ValueError("--score needs at least 2 tokens per line: the first token is given, not predicted")
+    idx = torch.zeros(len(ids), max(len(i) for i in ids), dtype=torch.long, device=device)
+    for b, i in enumerate(ids):
+        idx[b, :len(i)] = torch.tensor(i, dtype=torch.long)
+    rec = model.score(idx, lengths=[len(i) for i in ids], top=max(c["logprobs"], 0))
+    outs = []
+    for b, (t, i) in enumerate(zip(texts, ids)):
+        tok = rec.token[b, :len(i) - 1].double()
+        outs.append((float(tok.sum()), len(i) - 1, float(torch.exp(-tok.mean()))))
+        print(t)
+        print(f"logprob {outs[-1][0]:.4f} over {outs[-1][1]} tokens, perplexity {outs[-1][2]:.4f}")
+        print("---------------")
+    return outs
 
 
 def _serve_queue(model, c, encode, decode, start, device):
@@ -104,14 +154,17 @@ def _serve_queue(model, c, encode, decode, start, device):
     ys = model.generate_batch(prompts, c["max_new_tokens"], temperature=c["temperature"], top_k=c["top_k"],
                               stop_token=stop, top_p=c["top_p"], min_p=c["min_p"], quantize=c["quantize"] or None,
                               kv_quantize=c["kv_quantize"] or None, shared_prompt=bool(c["shared_prompt"]),
-                              batch_size=c["serve_batch"], **_penalties(c))
+                              batch_size=c["serve_batch"], **_penalties(c), **_logprobs(c))
+    ys, recs = ys if _logprobs(c) else (ys, None)
     outs = []
-    for p, y in zip(prompts, ys):
+    for i, (p, y) in enumerate(zip(prompts, ys)):
         new = y[p.numel():].tolist()
         if stop is not None and stop in new:
             new = new[:new.index(stop)]
         outs.append(decode(p.tolist() + new))
         print(outs[-1])
+        if recs is not None:
+            _print_logprobs(recs[i], new, decode)
         print("---------------")
     return outs
 
@@ -142,20 +195,27 @@ def _generate_batches(model, c, encode, decode, start, device):
                 if c["speculate"]:
                     mode.update(speculate=c["speculate"], spec_ngram=c["spec_ngram"])
                 mode.update(_penalties(c))
+                mode.update(_logprobs(c))
                 if B not in decs:  # a shared prompt / prefix stays cached in it: later rounds do not encode it again
                     decs[B] = batch_decoder(model, prompts, c["max_new_tokens"], **mode)
                 ys = model.generate_batch(prompts, c["max_new_tokens"], temperature=c["temperature"], top_k=c["top_k"],
                                           stop_token=stop, decoder=decs[B], top_p=c["top_p"], min_p=c["min_p"], **mode)
+                ys, recs = ys if _logprobs(c) else (ys, None)
             else:
                 ys = [model.generate(p[None], c["max_new_tokens"], temperature=c["temperature"], top_k=c["top_k"],
-                                     top_p=c["top_p"], min_p=c["min_p"], **_penalties(c))[0] for p in prompts]
-            for p, y in zip(prompts, ys):
+                                     top_p=c["top_p"], min_p=c["min_p"], **_penalties(c), **_logprobs(c))
+                      for p in prompts]
+                recs = [type(r)(*(t[0] for t in r)) for _, r in ys] if _logprobs(c) else None
+                ys = [(y[0] if _logprobs(c) else y)[0] for y in ys]
+            for i, (p, y) in enumerate(zip(prompts, ys)):
                 new = y[p.numel():].tolist()
                 if stop is not None and stop in new:
                     new = new[:new.index(stop)]
                 text = decode(p.tolist() + new)
                 outs.append(text)
                 print(text)
+                if recs is not None:
+                    _print_logprobs(recs[i], new, decode)
                 print("---------------")
     finally:
         for d in decs.values():
@@ -218,6 +278,13 @@ def main(argv=None):
                              "cache to share")
         if c["kv_quantize"]:
             raise ValueError("--shared_prefix keeps bf16 caches: it cannot be combined with --kv_quantize")
+    if c["logprobs"] != -1:
+        check_logprobs(c["logprobs"])
+        if c["speculate"]:
+            raise ValueError("--logprobs cannot be combined with --speculate: a verified position can be written by "
+                             "more than one step")
+    if c["score"] and not c["prompts_file"]:
+        raise ValueError("--score scores the lines of --prompts_file: pass one")
     if c["serve_batch"] < 0:
         raise ValueError(f"serve_batch must be >= 0, got {c['serve_batch']}")
     if c["serve_batch"]:
@@ -261,6 +328,9 @@ def main(argv=None):
     if start.startswith("FILE:"):
         with open(start[5:], "r", encoding="utf-8") as f:
             start = f.read()
+    if c["score"]:
+        with torch.no_grad():
+            return _score_file(model, c, encode, device)
     if c["serve_batch"]:
         with torch.no_grad():
             return _serve_queue(model, c, encode, decode, start, device)
@@ -275,20 +345,23 @@ def main(argv=None):
         # built once, not per sample
         from .runtime.decode import cached_decoder
         dec = cached_decoder(model, x, c["max_new_tokens"], quantize=quantize, kv_quantize=kv_quantize, **spec,
-                             **_penalties(c))
+                             **_penalties(c), **_logprobs(c))
     try:
         with torch.no_grad():
             for _ in range(c["num_samples"]):
                 if dec is not None:
                     y = model.generate_cached(x, c["max_new_tokens"], temperature=c["temperature"], top_k=c["top_k"],
                                               decoder=dec, top_p=c["top_p"], min_p=c["min_p"], quantize=quantize,
-                                              kv_quantize=kv_quantize, **spec, **_penalties(c))
+                                              kv_quantize=kv_quantize, **spec, **_penalties(c), **_logprobs(c))
                 else:
                     y = model.generate(x, c["max_new_tokens"], temperature=c["temperature"], top_k=c["top_k"],
-                                       top_p=c["top_p"], min_p=c["min_p"], **_penalties(c))
+                                       top_p=c["top_p"], min_p=c["min_p"], **_penalties(c), **_logprobs(c))
+                y, rec = y if _logprobs(c) else (y, None)
                 text = decode(y[0].tolist())
                 outs.append(text)
                 print(text)
+                if rec is not None:
+                    _print_logprobs(type(rec)(*(t[0] for t in rec)), y[0, x.shape[1]:].tolist(), decode)
                 print("---------------")
     finally:
         if dec is not None:

@@ -54,6 +54,9 @@ pass with the same sampling stream.  These lines carry the live ``steps`` per ro
 ``--penalties RP,PP,FP`` adds ``graph_pen`` / ``rows_pen`` right after ``graph`` / ``rows``: the same
 settings on a ``Decoder(penalize=True)`` sampling with that repetition, presence and frequency
 penalty (the penalised sampler and its count table beside the plain step of the same run).
+``--logprobs N[,N ...]`` adds ``graph_lpN`` / ``rows_lpN`` right after ``graph`` / ``rows``: the same settings on
+a ``Decoder(logprobs=N)``, whose step records every drawn token's log-probability and N alternatives
+(one more launch per step beside the plain step of the same run).
 """
 
 import argparse
@@ -73,9 +76,10 @@ PEN = {}  # --penalties: the three penalty keywords of the _pen modes
 DIMS = {"gpt2": (12, 12, 768), "gpt2-medium": (24, 16, 1024), "gpt2-large": (36, 20, 1280), "gpt2-xl": (48, 25, 1600)}
 
 
-def run_cached(model, idx, new, use_graph, quantize=None, kv_quantize=None, pen=False):
+def run_cached(model, idx, new, use_graph, quantize=None, kv_quantize=None, pen=False, lp=None):
     B = idx.shape[0]
-    dec = Decoder(model, B, use_graph=use_graph, quantize=quantize, kv_quantize=kv_quantize, penalize=pen)
+    dec = Decoder(model, B, use_graph=use_graph, quantize=quantize, kv_quantize=kv_quantize, penalize=pen,
+                  logprobs=lp)
     smp = dict(SMP, **PEN) if pen else SMP
     dec.sample_into(dec.prefill(idx), 0.8, **smp)
     if use_graph:
@@ -99,18 +103,18 @@ def ragged_lengths(B, prompt):
     return [prompt if B == 1 else lo + (prompt - lo) * b // (B - 1) for b in range(B)]
 
 
-def run_rows(model, idx, new, lengths=None, quantize=None, kv_quantize=None, shared=False, pen=False):
+def run_rows(model, idx, new, lengths=None, quantize=None, kv_quantize=None, shared=False, pen=False, lp=None):
     """The graph mode on a per_row decoder: equal lengths, or (lengths) a ragged batch; shared:
     a shared_prompt decoder, every row continuing idx[0].  Returns (seconds of the timed steps,
     seconds from the start of the prefill to the first drawn token).  pen: a penalising decoder,
-    sampling with --penalties."""
+    sampling with --penalties.  lp: a decoder that records log-probabilities and lp alternatives."""
     B = idx.shape[0]
     if shared:  # slots for the capture step and the timed ones
         dec = Decoder(model, B, use_graph=True, per_row=True, quantize=quantize, shared_prompt=True, max_new=new + 1,
-                      penalize=pen)
+                      penalize=pen, logprobs=lp)
     else:
         dec = Decoder(model, B, use_graph=True, per_row=True, quantize=quantize, kv_quantize=kv_quantize,
-                      penalize=pen)
+                      penalize=pen, logprobs=lp)
     smp = dict(SMP, **PEN) if pen else SMP
     lens = None if lengths is None else torch.tensor(lengths, device=idx.device)
     torch.cuda.synchronize()
@@ -315,6 +319,8 @@ def main():
                                                      "(rows_specK_right: all accepted, rows_specK_wrong: none)")
     ap.add_argument("--penalties", default="", help="RP,PP,FP: add penalised twins of the graph and rows modes "
                                                     "(graph_pen, rows_pen) on a Decoder(penalize=True)")
+    ap.add_argument("--logprobs", default="", help="N[,N ...]: add twins of the graph and rows modes that record "
+                                                   "log-probabilities and N alternatives (graph_lpN, rows_lpN)")
     ap.add_argument("--top_k", type=int, default=200, help="0: no top-k")
     ap.add_argument("--top_p", type=float, default=1.0, help="nucleus mass; 1.0: off")
     ap.add_argument("--min_p", type=float, default=0.0, help="floor relative to the most likely token; 0.0: off")
@@ -344,6 +350,9 @@ def main():
         PEN.update(repetition_penalty=rp, presence_penalty=pp, frequency_penalty=fp)
         extra["penalties"] = a.penalties
         modes = [t for m in modes for t in ([m, f"{m}_pen"] if m in ("graph", "rows") else [m])]
+    if a.logprobs:  # the recording twins right after their mode
+        twins = [f"lp{int(n)}" for n in a.logprobs.split(",")]
+        modes = [t for m in modes for t in ([m] + [f"{m}_{x}" for x in twins] if m in ("graph", "rows") else [m])]
     if a.shared_prefix:
         modes = ["prefix_rows", "prefix_shared"]
     block_size = GPTConfig().block_size
@@ -385,6 +394,7 @@ def main():
                     kvq = "int8" if "kv8" in sfx else None
                     ttft = {}
                     spec = next((int(x[4:]) for x in sfx if x.startswith("spec")), 0)
+                    lp = next((int(x[2:]) for x in sfx if x.startswith("lp")), None)
                     if a.memory:
                         torch.cuda.synchronize()
                         torch.cuda.reset_peak_memory_stats()
@@ -407,8 +417,8 @@ def main():
                     elif base in ("rows", "ragged"):
                         n = a.new
                         lens = ragged_lengths(B, a.prompt) if base == "ragged" else None
-                        run_rows(model, idx, 4, lens, qz, kvq, "shared" in sfx, "pen" in sfx)
-                        dt, t1 = run_rows(model, idx, n, lens, qz, kvq, "shared" in sfx, "pen" in sfx)
+                        run_rows(model, idx, 4, lens, qz, kvq, "shared" in sfx, "pen" in sfx, lp)
+                        dt, t1 = run_rows(model, idx, n, lens, qz, kvq, "shared" in sfx, "pen" in sfx, lp)
                         if a.shared_prompt:
                             ttft = {"ttft_ms": round(t1 * 1e3, 3)}
                     elif mode == "recompute":
@@ -417,8 +427,8 @@ def main():
                         dt = run_recompute(model, idx, n)
                     else:
                         n = a.new
-                        run_cached(model, idx, 4, base == "graph", qz, kvq, "pen" in sfx)
-                        dt = run_cached(model, idx, n, base == "graph", qz, kvq, "pen" in sfx)
+                        run_cached(model, idx, 4, base == "graph", qz, kvq, "pen" in sfx, lp)
+                        dt = run_cached(model, idx, n, base == "graph", qz, kvq, "pen" in sfx, lp)
                     mem = ({"decoder_peak_mb": round((torch.cuda.max_memory_allocated() - mem0) / 2 ** 20, 1)}
                            if a.memory else {})
                     print(json.dumps({"model": name, "batch": B, "mode": mode, "prompt": a.prompt, "new_tokens": n,
