@@ -367,19 +367,17 @@ class GPT(nn.Module):
         part cropped from the context included.  ``logprobs=N`` (0 .. 8; None: off): returns ``(tokens,
         ops.LogProbs)`` over the new tokens, each token's log-probability under the raw logits and the
         N most likely ids with theirs (``ops.token_logprobs``)."""
+        from ..runtime.decode import _no_records, sampling
         logprobs = ops.check_logprobs(logprobs)
         recs = []
-        ops.check_sampling_filters(top_p, min_p)
-        ops.check_sampling_penalties(repetition_penalty, presence_penalty, frequency_penalty)
-        pen = (1.0 if repetition_penalty is None else float(repetition_penalty),
-               0.0 if presence_penalty is None else float(presence_penalty),
-               0.0 if frequency_penalty is None else float(frequency_penalty))
+        _, _, _, top_p, min_p, pen = sampling(temperature, top_k, None, top_p, min_p, repetition_penalty,
+                                              presence_penalty, frequency_penalty)
         for _ in range(max_new_tokens):
             # if the sequence context is growing too long we must crop it at block_size
             idx_cond = idx if idx.size(1) <= self.config.block_size else idx[:, -self.config.block_size:]
             logits, _ = self(idx_cond)
             logits = raw = logits[:, -1, :]
-            if pen != (1.0, 0.0, 0.0):
+            if pen is not None:
                 counts = torch.zeros(idx.size(0), logits.size(-1), dtype=torch.int32, device=idx.device)
                 counts.scatter_add_(1, idx, torch.ones_like(idx, dtype=torch.int32))
                 logits = ops.penalize_logits(logits, counts, *pen)
@@ -387,7 +385,7 @@ class GPT(nn.Module):
             if top_k:
                 v, _ = torch.topk(logits, min(top_k, logits.size(-1)))
                 logits[logits < v[:, [-1]]] = -float("Inf")
-            if (top_p is not None and top_p < 1.0) or (min_p is not None and min_p > 0.0):
+            if top_p is not None or min_p is not None:
                 logits = ops.filter_logits(logits.float(), None, top_p, min_p)
             probs = torch.softmax(logits, dim=-1)
             idx_next = torch.multinomial(probs, num_samples=1)
@@ -397,9 +395,7 @@ class GPT(nn.Module):
         if logprobs is None:
             return idx
         if not recs:
-            return idx, ops.LogProbs(torch.zeros(idx.size(0), 0, device=idx.device),
-                                     torch.zeros(idx.size(0), 0, logprobs, dtype=torch.int32, device=idx.device),
-                                     torch.zeros(idx.size(0), 0, logprobs, device=idx.device))
+            return idx, _no_records(idx.size(0), logprobs, idx.device)
         return idx, ops.LogProbs(*(torch.stack(c, dim=1) for c in zip(*recs)))
 
     @torch.no_grad()

@@ -142,14 +142,83 @@ context there, which a cache cannot do without re-encoding).
 from __future__ import annotations
 
 import contextlib
+from typing import NamedTuple
 
 import torch
 
 from .. import ops
 
 
-def _check_mode(quantize, kv_quantize, shared_prompt=False, shared_prefix=False):
-    """The mode combinations a decoder and the front ends accept: ValueError for any other."""
+class Sampling(NamedTuple):
+    """The sampling settings of a call, normalised once (``sampling``): what is off is None."""
+    temperature: float = 1.0
+    top_k: int | None = None
+    stop_token: int | None = None
+    top_p: float | None = None
+    min_p: float | None = None
+    penalties: tuple | None = None  # (repetition_penalty, presence_penalty, frequency_penalty) as floats
+
+
+def sampling(temperature=1.0, top_k=None, stop_token=None, top_p=None, min_p=None, repetition_penalty=None,
+             presence_penalty=None, frequency_penalty=None) -> Sampling:
+    """The ``Sampling`` of a call's raw arguments, validated (``ops.check_sampling_filters``,
+    ``ops.check_sampling_penalties``: ValueError): a stop token < 0 means none, a filter that is off
+    (``top_p`` >= 1, ``min_p`` 0) and penalties that are all off (1, 0 and 0, or None) are None.
+    ``top_k`` stays as given (None or 0: off).  A ``Sampling`` in ``temperature``'s place is the
+    value itself, whatever follows it: the public entry points build it once and hand it on so."""
+    if isinstance(temperature, Sampling):
+        return temperature
+    ops.check_sampling_filters(top_p, min_p)
+    ops.check_sampling_penalties(repetition_penalty, presence_penalty, frequency_penalty)
+    pen = (1.0 if repetition_penalty is None else float(repetition_penalty),
+           0.0 if presence_penalty is None else float(presence_penalty),
+           0.0 if frequency_penalty is None else float(frequency_penalty))
+    return Sampling(temperature, top_k, None if stop_token is None or stop_token < 0 else stop_token,
+                    None if top_p is None or float(top_p) >= 1.0 else float(top_p),
+                    None if min_p is None or float(min_p) <= 0.0 else float(min_p),
+                    None if pen == (1.0, 0.0, 0.0) else pen)
+
+
+def sampling_filters(top_p=None, min_p=None):
+    """Validated (top_p, min_p) with a filter that is off (``top_p`` >= 1, ``min_p`` 0) as None."""
+    return sampling(top_p=top_p, min_p=min_p)[3:5]
+
+
+def sampling_penalties(repetition_penalty=None, presence_penalty=None, frequency_penalty=None):
+    """Validated (repetition_penalty, presence_penalty, frequency_penalty) as floats, or None when
+    all three are off (1, 0 and 0, or None)."""
+    return sampling(repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
+                    frequency_penalty=frequency_penalty).penalties
+
+
+def graph_key(smp: Sampling, per_row=False, queue=False, spec=None, table=False, penalize=False,
+              logprobs=None) -> tuple:
+    """The key of a captured sampling step in ``Decoder.sgraphs``: (temperature, top_k), then the stop
+    token (a ``per_row`` decoder: None included), (top_p, min_p) if either is on (without them: the
+    keys of the top-k sampler), ``"queue"``, ``("spec", K, N)`` (``spec`` = (K, N)) and ``"table"`` (a
+    draft table is set), ``("pen", rp, pp, fp)`` on a penalising decoder (the identity (1, 0, 0) when
+    the call passes none) and ``("lp", N)`` on one that records log-probabilities."""
+    key = (float(smp.temperature), smp.top_k) + ((smp.stop_token,) if per_row else ())
+    if smp.top_p is not None or smp.min_p is not None:
+        key += (smp.top_p, smp.min_p)
+    if queue:
+        key += ("queue",)
+    if spec:
+        key += ("spec", *spec) + (("table",) if table else ())
+    if penalize:
+        key += ("pen", *(smp.penalties or (1.0, 0.0, 0.0)))
+    if logprobs is not None:
+        key += ("lp", logprobs)
+    return key
+
+
+def _check(quantize=None, kv_quantize=None, shared_prompt=False, shared_prefix=False, queue=False, speculate=None,
+           spec_ngram=3, penalize=False, logprobs=None, rows=None, max_new=None):
+    """Every rule on a mode that depends on neither the model nor the device, for ``Decoder`` and the
+    front ends alike: ValueError for what does not compose, never a silent plain step -> (K, N,
+    logprobs), the drafted tokens and n-gram length of a speculative call (K = 0: none) and
+    ``logprobs`` validated (None: off; 0 .. 8 alternatives).  ``penalize``: a count table, or a call
+    with a penalty on; ``rows`` / ``max_new``: a decoder's own (a front end plans them afterwards)."""
     if quantize not in (None, "int8"):
         raise ValueError(f"quantize must be None or 'int8', got {quantize!r}")
     if kv_quantize not in (None, "int8"):
@@ -160,42 +229,33 @@ def _check_mode(quantize, kv_quantize, shared_prompt=False, shared_prefix=False)
         raise ValueError("shared_prefix and shared_prompt are two forms of sharing: pass one of them")
     if shared_prefix and kv_quantize:
         raise ValueError("shared_prefix keeps bf16 caches: it cannot be combined with kv_quantize")
-
-
-def _check_spec(speculate, spec_ngram=3, kv_quantize=None, shared_prompt=False, shared_prefix=False, queue=False):
-    """(K, N) of a speculative call, validated (K = 0: none); ValueError for what speculation does not
-    compose with, never a silent plain step."""
-    K = int(speculate or 0)
-    if not K:
-        return 0, 3
-    N = 3 if spec_ngram is None else int(spec_ngram)
-    if not 1 <= K <= ops.functional.SPEC_MAX_DRAFTS:
-        raise ValueError(f"speculate must be in 1 .. {ops.functional.SPEC_MAX_DRAFTS} drafted tokens, "
-                         f"got {speculate!r}")
-    if N < 1:
-        raise ValueError(f"spec_ngram must be at least 1, got {spec_ngram!r}")
-    if kv_quantize:
-        raise ValueError("speculate keeps bf16 caches: it cannot be combined with kv_quantize")
-    if shared_prompt or shared_prefix:
-        raise ValueError("speculate decodes every row against its own cache: it cannot be combined with "
-                         "shared_prompt / shared_prefix")
-    if queue:
-        raise ValueError("speculative batches are not served as a queue: drop batch_size / per-prompt budgets")
-    return K, N
-
-
-def _check_logprobs(logprobs, speculate=None):
-    """``logprobs`` validated (None: off; 0 .. 8 alternatives); ValueError with speculation."""
     logprobs = ops.check_logprobs(logprobs)
-    if logprobs is not None and int(speculate or 0):
-        raise ValueError("speculate cannot be combined with logprobs: a verified position can be written by more "
-                         "than one step")
-    return logprobs
-
-
-def _stop(stop_token):
-    """A stop token < 0 means none."""
-    return None if stop_token is None or stop_token < 0 else stop_token
+    K, N = int(speculate or 0), 3
+    if K:
+        N = 3 if spec_ngram is None else int(spec_ngram)
+        if logprobs is not None:
+            raise ValueError("speculate cannot be combined with logprobs: a verified position can be written by more "
+                             "than one step")
+        if not 1 <= K <= ops.functional.SPEC_MAX_DRAFTS:
+            raise ValueError(f"speculate must be in 1 .. {ops.functional.SPEC_MAX_DRAFTS} drafted tokens, "
+                             f"got {speculate!r}")
+        if N < 1:
+            raise ValueError(f"spec_ngram must be at least 1, got {spec_ngram!r}")
+        if kv_quantize:
+            raise ValueError("speculate keeps bf16 caches: it cannot be combined with kv_quantize")
+        if shared_prompt or shared_prefix:
+            raise ValueError("speculate decodes every row against its own cache: it cannot be combined with "
+                             "shared_prompt / shared_prefix")
+        if queue:
+            raise ValueError("speculative batches are not served as a queue: drop batch_size / per-prompt budgets")
+        if penalize:
+            raise ValueError("speculate cannot be combined with sampling penalties: a verified position's counts "
+                             "would have to include the drafts before it")
+    if shared_prompt and rows is not None and rows < 2:
+        raise ValueError(f"shared_prompt needs at least 2 rows to share a prompt, got batch size {rows}")
+    if max_new is not None and not shared_prompt:
+        raise ValueError("max_new sizes the row caches of a shared_prompt decoder")
+    return K, N, logprobs
 
 
 class Decoder:
@@ -203,17 +263,10 @@ class Decoder:
                  per_row: bool = False, quantize: str | None = None, kv_quantize: str | None = None,
                  shared_prompt: bool = False, max_new: int | None = None, speculate: int | None = None,
                  spec_ngram: int = 3, penalize: bool = False, logprobs: int | None = None):
-        _check_mode(quantize, kv_quantize, shared_prompt)
-        logprobs = _check_logprobs(logprobs, speculate)
-        self.K, self.N = _check_spec(speculate, spec_ngram, kv_quantize, shared_prompt)
-        if self.K and penalize:
-            raise ValueError("speculate cannot be combined with sampling penalties: a verified position's counts "
-                             "would have to include the drafts before it")
+        self.K, self.N, logprobs = _check(quantize, kv_quantize, shared_prompt, speculate=speculate,
+                                          spec_ngram=spec_ngram, penalize=penalize, logprobs=logprobs,
+                                          rows=batch_size, max_new=max_new)
         per_row = per_row or bool(self.K)  # a speculating row advances by its own number of positions
-        if shared_prompt and batch_size < 2:
-            raise ValueError(f"shared_prompt needs at least 2 rows to share a prompt, got batch size {batch_size}")
-        if max_new is not None and not shared_prompt:
-            raise ValueError("max_new sizes the row caches of a shared_prompt decoder")
         self.model = model
         self.per_row = per_row
         self.quantize = quantize
@@ -449,9 +502,12 @@ class Decoder:
             x, h = ops.add_layer_norm(x, y, nxt.weight, nxt.bias)
         return h  # ln_f(x)
 
-    def _decode_layers(self):
-        """The token ``tok`` at position ``pos`` through the embedding, every block and the
-        head -> fp32 logits [B, 1, V].
+    def _layers(self, tok, pos, attend, pos_inc=None):
+        """The tokens ``tok`` [rows, 1] at the positions ``pos`` through the embedding, every block and
+        the head -> fp32 logits [rows, 1, V].  ``attend(i, qkv)``: layer i's attention over its caches,
+        the K / V append included -> c_proj's input [rows, 1, C]; ``pos_inc``: the position tensor the
+        head kernel advances (None: the caller moves the positions).  Row-generic: a plain step
+        feeds B rows, a speculative one B * (K + 1).
 
         Each linear's producer rides in its prologue at batch 1: the embedding and ln_1 in
         c_attn's (``ops.decode_embed_linear_ln``), the residual add + LayerNorm in c_attn /
@@ -466,73 +522,57 @@ class Decoder:
             attn, mlp = block.attn, block.mlp
             ln1, ln2 = block.ln_1, block.ln_2
             if i == 0:
-                x, qkv = ops.decode_embed_linear_ln(self.tok, self.pos, tr.wte.weight, tr.wpe.weight, ln1.weight,
-                                                    ln1.bias, W(attn.c_attn.weight), attn.c_attn.bias, dtype=self.dtype,
+                x, qkv = ops.decode_embed_linear_ln(tok, pos, tr.wte.weight, tr.wpe.weight, ln1.weight, ln1.bias,
+                                                    W(attn.c_attn.weight), attn.c_attn.bias, dtype=self.dtype,
                                                     res_dtype=self.rdtype, out_dtype=ln1.out_dtype)
             else:
                 x, qkv = ops.decode_linear_ln(x, branch, ln1.weight, ln1.bias, W(attn.c_attn.weight), attn.c_attn.bias,
                                               out_dtype=ln1.out_dtype)
-            if self.shared:
-                y = ops.decode_attention_shared(qkv, self.pkc[i], self.pvc[i], self.kc[i], self.vc[i], self.plen,
-                                                self.pos, attn.n_head, append=True)
-            else:
-                y = ops.decode_attention(qkv, self.kc[i], self.vc[i], self.pos, attn.n_head, append=True,
-                                         combine=False)
-            y = ops.decode_linear(y, W(attn.c_proj.weight), attn.c_proj.bias)
+            y = ops.decode_linear(attend(i, qkv), W(attn.c_proj.weight), attn.c_proj.bias)
             x, u = ops.decode_linear_ln(x, y, ln2.weight, ln2.bias, W(mlp.c_fc.weight), mlp.c_fc.bias, gelu=True,
                                         out_dtype=ln2.out_dtype)
             branch = ops.decode_linear(u, W(mlp.c_proj.weight), mlp.c_proj.bias)
         lnf = tr.ln_f
         _, logits = ops.decode_linear_ln(x, branch, lnf.weight, lnf.bias, W(self.model.lm_head.weight), None,
-                                         out_f32=True, out_dtype=lnf.out_dtype,
-                                         pos_inc=None if self.per_row else self.pos)
-        if self.per_row:
-            ops.advance_pos_(self.pos, self.done)  # unfinished rows move on, finished rows stay
-        return logits  # pos has advanced (by the head kernel itself on the fused path)
+                                         out_f32=True, out_dtype=lnf.out_dtype, pos_inc=pos_inc)
+        return logits
 
-    def _spec_layers(self):
-        """A speculative step's model pass: the B * (K + 1) fed tokens ``stok`` at the positions ``spos``
-        through the same embedding and linear ops as ``_decode_layers`` (row-generic: the skinny
-        kernels on the GPU), with ``ops.decode_attention_spec`` in place of the single-query attention
-        -> fp32 logits [B * (K + 1), V], row (b, j) for position ``pos[b] + j + 1``.  ``pos`` does not move
-        here: ``ops.spec_accept_`` advances every row by what it keeps."""
-        tr = self.model.transformer
-        W = self._w
-        B, S = self.B, self.K + 1
-        rows = B * S
-        branch = None
-        for i, block in enumerate(tr.h):
-            attn, mlp = block.attn, block.mlp
-            ln1, ln2 = block.ln_1, block.ln_2
-            if i == 0:
-                x, qkv = ops.decode_embed_linear_ln(self.stok.view(rows, 1), self.spos.view(rows), tr.wte.weight,
-                                                    tr.wpe.weight, ln1.weight, ln1.bias, W(attn.c_attn.weight),
-                                                    attn.c_attn.bias, dtype=self.dtype, res_dtype=self.rdtype,
-                                                    out_dtype=ln1.out_dtype)
-            else:
-                x, qkv = ops.decode_linear_ln(x, branch, ln1.weight, ln1.bias, W(attn.c_attn.weight), attn.c_attn.bias,
-                                              out_dtype=ln1.out_dtype)
-            y = ops.decode_attention_spec(qkv.view(B, S, -1), self.kc[i], self.vc[i], self.pos, attn.n_head)
-            y = ops.decode_linear(y.view(rows, 1, -1), W(attn.c_proj.weight), attn.c_proj.bias)
-            x, u = ops.decode_linear_ln(x, y, ln2.weight, ln2.bias, W(mlp.c_fc.weight), mlp.c_fc.bias, gelu=True,
-                                        out_dtype=ln2.out_dtype)
-            branch = ops.decode_linear(u, W(mlp.c_proj.weight), mlp.c_proj.bias)
-        lnf = tr.ln_f
-        _, logits = ops.decode_linear_ln(x, branch, lnf.weight, lnf.bias, W(self.model.lm_head.weight), None,
-                                         out_f32=True, out_dtype=lnf.out_dtype)
+    def _step_impl(self):
+        """The token ``tok`` at position ``pos`` through the model (``_layers``) -> fp32 logits [B, V];
+        ``pos`` has advanced: by the head kernel itself, or (per_row) the unfinished rows move on and
+        the finished rows stay."""
+        if self.shared:
+            def attend(i, qkv):
+                return ops.decode_attention_shared(qkv, self.pkc[i], self.pvc[i], self.kc[i], self.vc[i], self.plen,
+                                                   self.pos, self.H, append=True)
+        else:
+            def attend(i, qkv):
+                return ops.decode_attention(qkv, self.kc[i], self.vc[i], self.pos, self.H, append=True, combine=False)
+        logits = self._layers(self.tok, self.pos, attend, None if self.per_row else self.pos)
+        if self.per_row:
+            ops.advance_pos_(self.pos, self.done)
         return logits[:, 0]
 
-    def _spec_step_impl(self, temperature, top_k, stop_token=None, top_p=None, min_p=None):
-        """One speculative step: the model pass over every row's token and its K drafts, one draw per
+    def _spec_step_impl(self, smp):
+        """One speculative step.  The model pass: the B * (K + 1) fed tokens ``stok`` at the positions
+        ``spos`` through the same embedding and linear ops as ``_step_impl`` (``_layers``; the skinny
+        kernels on the GPU), with ``ops.decode_attention_spec`` in place of the single-query attention
+        -> fp32 logits [B * (K + 1), V], row (b, j) for position ``pos[b] + j + 1``.  Then one draw per
         fed position with the stream the plain per-row decoder uses for it (row (b, j) hashes (b,
         pos[b] + j + 1): the sampler's ``row_key`` form over B * (K + 1) rows, into scratch), then
         ``ops.spec_accept_``: the drafts that equal their draws are kept, ``pos`` / ``tok`` / ``gen`` /
-        ``done`` move on and the next step's drafts are made.  No ``advance_pos_`` and no ``pos_inc``."""
-        logits = self._spec_layers()
-        ops.sample_topk_(logits, temperature, top_k, self.salt, self.cpos.view(-1), self.ctok, self.cgen,
-                         salt_dev=self.salt_dev, top_p=top_p, min_p=min_p, row_key=self.rkey)
-        ops.spec_accept_(self.ctok.view(self.B, self.K + 1), self.stok, self.spos, self.cpos, self.gen, self.pos,
-                         self.tok, self.done, self.end, T=self.T, N=self.N, stop_token=stop_token, table=self.table,
+        ``done`` move on (``pos`` does not move before: every row advances by what it keeps) and the
+        next step's drafts are made.  No ``advance_pos_`` and no ``pos_inc``."""
+        B, S = self.B, self.K + 1
+
+        def attend(i, qkv):
+            y = ops.decode_attention_spec(qkv.view(B, S, -1), self.kc[i], self.vc[i], self.pos, self.H)
+            return y.view(B * S, 1, -1)
+        logits = self._layers(self.stok.view(B * S, 1), self.spos.view(B * S), attend)[:, 0]
+        ops.sample_topk_(logits, smp.temperature, smp.top_k, self.salt, self.cpos.view(-1), self.ctok, self.cgen,
+                         salt_dev=self.salt_dev, top_p=smp.top_p, min_p=smp.min_p, row_key=self.rkey)
+        ops.spec_accept_(self.ctok.view(B, S), self.stok, self.spos, self.cpos, self.gen, self.pos, self.tok,
+                         self.done, self.end, T=self.T, N=self.N, stop_token=smp.stop_token, table=self.table,
                          stats=self.spec_counts)
 
     def set_draft_table(self, table=None):
@@ -726,16 +766,15 @@ class Decoder:
             lengths = torch.full((n,), idx.shape[1], dtype=torch.int64, device=self.device)
         return self._prefill(idx.to(self.device), 0, lengths, rows)
 
-    def _pen(self, repetition_penalty=None, presence_penalty=None, frequency_penalty=None) -> dict:
+    def _pen(self, smp) -> dict:
         """The sampler's penalty keywords for a draw on this decoder.  Penalising: the count table
         and the three numbers, the identity where the call passes none, so every draw is counted.
         Otherwise nothing, and a penalty that is on raises ValueError."""
-        pen = sampling_penalties(repetition_penalty, presence_penalty, frequency_penalty)
         if self.cnt is None:
-            if pen is not None:
+            if smp.penalties is not None:
                 raise ValueError("sampling penalties need Decoder(..., penalize=True)")
             return {}
-        rp, pp, fp = pen or (1.0, 0.0, 0.0)
+        rp, pp, fp = smp.penalties or (1.0, 0.0, 0.0)
         return dict(counts=self.cnt, repetition_penalty=rp, presence_penalty=pp, frequency_penalty=fp)
 
     def _queue_state(self):
@@ -754,8 +793,9 @@ class Decoder:
         row masked as finished, so those rows' ``tok``, ``gen``, ``done`` and ``cnt`` stay untouched."""
         assert self.per_row
         self._queue_state()
-        top_p, min_p = sampling_filters(top_p, min_p)
-        pen = self._pen(repetition_penalty, presence_penalty, frequency_penalty)
+        smp = sampling(temperature, top_k, stop_token, top_p, min_p, repetition_penalty, presence_penalty,
+                       frequency_penalty)
+        pen = self._pen(smp)
         rows = self._row_index(rows)
         mask = torch.ones(self.B, device=self.device, dtype=torch.int64)
         mask.index_fill_(0, rows, 0)
@@ -766,9 +806,9 @@ class Decoder:
                 self._admit_logits = torch.zeros(self.B, logits.shape[1], device=self.device, dtype=torch.float32)
             full = self._admit_logits
             full.index_copy_(0, rows, logits.float())
-        ops.sample_topk_(full, temperature, top_k, self.salt, self.pos, self.tok, self.gen, salt_dev=self.salt_dev,
-                         stop_token=stop_token, done=mask, top_p=top_p, min_p=min_p, row_key=self.key, end=self.end,
-                         **pen)
+        ops.sample_topk_(full, smp.temperature, smp.top_k, self.salt, self.pos, self.tok, self.gen,
+                         salt_dev=self.salt_dev, stop_token=smp.stop_token, done=mask, top_p=smp.top_p, min_p=smp.min_p,
+                         row_key=self.key, end=self.end, **pen)
         self._record(full)  # the admitted rows alone: every other row's position is the one it recorded last
         self.done.index_copy_(0, rows, mask[rows])
 
@@ -796,10 +836,9 @@ class Decoder:
         assert self.per_row, "serve needs Decoder(..., per_row=True)"
         if self.K:
             raise ValueError("a speculative decoder does not serve a queue")
-        stop_token = _stop(stop_token)
-        top_p, min_p = sampling_filters(top_p, min_p)
-        pen = _pen_kw(sampling_penalties(repetition_penalty, presence_penalty, frequency_penalty))
-        self._pen(**pen)  # a penalty on a decoder without the table: refused before anything runs
+        smp = sampling(temperature, top_k, stop_token, top_p, min_p, repetition_penalty, presence_penalty,
+                       frequency_penalty)
+        self._pen(smp)  # a penalty on a decoder without the table: refused before anything runs
         nreq = len(prompts)
         budgets = [int(n) for n in budgets]
         lens = [int(p.numel()) for p in prompts]
@@ -811,7 +850,7 @@ class Decoder:
         self.queue_stats = stats = {"steps": 0, "admissions": 0, "admitted": 0}
         outs: list = [None] * nreq
         if not nreq:
-            return outs if self.lp is None else (outs, [])
+            return _with_records(outs, self.logprobs, [])
         B = self.B
         if self.shared:
             self.prefill_shared(prompts[0])  # every row at the prompt's end: a valid place to idle
@@ -840,7 +879,7 @@ class Decoder:
                 logits = self.admit(free)
             else:
                 logits = self.admit(free, *_right_pad([prompts[i] for i in reqs], self.device))
-            self.sample_admitted(free, logits, temperature, top_k, stop_token, top_p, min_p, **pen)
+            self.sample_admitted(free, logits, smp, None)
             for b, i in zip(free, reqs):
                 owner[b], left[b] = i, budgets[i] - 1
             stats["admissions"] += 1
@@ -850,7 +889,7 @@ class Decoder:
         while True:
             k = min(self.DONE_POLL, max(left[b] for b in range(B) if owner[b] is not None))
             if k > 0:
-                self.run(k, temperature, top_k, stop_token, top_p, min_p, queue=True, **pen)
+                self.run(k, smp, queue=True)
                 stats["steps"] += k
             done, pos = torch.stack([self.done, self.pos]).tolist()  # the one host look per poll
             for b in range(B):
@@ -866,10 +905,7 @@ class Decoder:
                     left[b] = lens[i] + budgets[i] - 1 - pos[b]
             fill()
             if all(o is None for o in owner):
-                return outs if self.lp is None else (outs, lps)
-
-    def _step_impl(self):
-        return self._decode_layers()[:, 0]  # also advances pos
+                return _with_records(outs, self.logprobs, lps)
 
     @torch.no_grad()
     def step(self, tok: torch.Tensor) -> torch.Tensor:
@@ -888,34 +924,32 @@ class Decoder:
         """Warm ``fn`` (a step, with or without sampling) up and record it -> (graph, what fn returned)."""
         # the warm-up: outside any graph (lazy library init, GEMM tuner decisions for M = B), at the
         # current position without advancing it or changing the fed token: the captured
-        # step rewrites the same cache rows when it runs
-        tok = self.tok.clone()
-        if self.per_row:  # a warm-up draw may hit the stop token: positions and flags are put back
-            pos, done = self.pos.clone(), self.done.clone()
-        # a speculative warm-up step also accepts and drafts: its fed tokens and counters are put back too
-        spec = [(t, t.clone()) for t in (self.stok, self.spos, self.cpos, self.spec_counts)] if self.K else []
-        if self.cnt is not None:  # a warm-up draw is counted: the table is put back as well
-            spec.append((self.cnt, self.cnt.clone()))
-        if self.lp is not None:  # a warm-up draw is recorded: the records and the marker are put back too
-            spec += [(t, t.clone()) for t in (self.lp, self.top_ids, self.top_lp, self.lp_last)]
+        # step rewrites the same cache rows when it runs, and whatever else a step writes
+        # (``_written``) is put back
+        saved = [(t, t.clone()) for t in self._written()]
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
             for _ in range(2):
                 fn()
-                if self.per_row:
-                    self.pos.copy_(pos)
-                    self.done.copy_(done)
-                else:
-                    self.pos.sub_(1)
-                self.tok.copy_(tok)
-                for t, saved in spec:
-                    t.copy_(saved)
+                for t, was in saved:
+                    t.copy_(was)
         torch.cuda.current_stream().wait_stream(side)
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):  # recorded, not executed: pos is unchanged
             out = fn()
         return graph, out
+
+    def _written(self) -> list:
+        """The tensors a step, with or without sampling, writes beside the caches and ``gen``, for this
+        decoder's mode: the fed token and the position; the finished flags (a warm-up draw may hit the
+        stop token); a speculative step also accepts and drafts (its fed tokens, their positions and
+        the counters); a penalising decoder counts the draw (the table) and one with ``logprobs``
+        records it (the records and the marker)."""
+        return ([self.tok, self.pos] + ([self.done] if self.per_row else [])
+                + ([self.stok, self.spos, self.cpos, self.spec_counts] if self.K else [])
+                + ([self.cnt] if self.cnt is not None else [])
+                + ([self.lp, self.top_ids, self.top_lp, self.lp_last] if self.lp is not None else []))
 
     def sample_into(self, logits, temperature, top_k, stop_token=None, top_p=None, min_p=None, queue=False,
                     repetition_penalty=None, presence_penalty=None, frequency_penalty=None):
@@ -927,17 +961,17 @@ class Decoder:
         serving queue's form, every row keyed by ``key`` and finished at ``end``.  The three
         penalties (penalising decoders; None: off): the draw is made from
         ``ops.penalize_logits(logits, cnt, ...)`` and counted in ``cnt``, inside the same launch."""
-        top_p, min_p = sampling_filters(top_p, min_p)
-        pen = self._pen(repetition_penalty, presence_penalty, frequency_penalty)
+        smp = sampling(temperature, top_k, stop_token, top_p, min_p, repetition_penalty, presence_penalty,
+                       frequency_penalty)
         if queue:
             assert self.per_row and self.key is not None, "the queue form needs a per_row decoder with key / end"
-        if not self.per_row:
-            assert stop_token is None, "a stop token needs Decoder(..., per_row=True)"
+        assert smp.stop_token is None or self.per_row, "a stop token needs Decoder(..., per_row=True)"
         # ``done`` is None without per_row, ``key`` / ``end`` are passed by the queue only: the sampler
         # picks its entry point from what is there
-        ops.sample_topk_(logits, temperature, top_k, self.salt, self.pos, self.tok, self.gen, salt_dev=self.salt_dev,
-                         stop_token=stop_token, done=self.done, top_p=top_p, min_p=min_p,
-                         row_key=self.key if queue else None, end=self.end if queue else None, **pen)
+        ops.sample_topk_(logits, smp.temperature, smp.top_k, self.salt, self.pos, self.tok, self.gen,
+                         salt_dev=self.salt_dev, stop_token=smp.stop_token, done=self.done, top_p=smp.top_p,
+                         min_p=smp.min_p, row_key=self.key if queue else None, end=self.end if queue else None,
+                         **self._pen(smp))
         self._record(logits)
 
     def _record(self, logits):
@@ -951,8 +985,19 @@ class Decoder:
         """A fresh sampling stream for the next generate call (torch.manual_seed governs)."""
         self.salt_dev.fill_(int(torch.randint(0, 2 ** 62, (1,)).item()))
 
-    def _step_sample_impl(self, temperature, top_k, stop_token=None, top_p=None, min_p=None, queue=False, **pen):
-        self.sample_into(self._step_impl(), temperature, top_k, stop_token, top_p, min_p, queue, **pen)  # pos is now p + 1
+    def _step_sample_impl(self, smp, queue=False):
+        self.sample_into(self._step_impl(), smp, None, queue=queue)  # pos is now p + 1
+
+    def _replay(self, step, smp, queue=False):
+        """What ``run`` calls per token: ``step`` itself (eager), or the replay of its captured graph,
+        captured on first use under the step's ``graph_key``."""
+        if not self.use_graph:
+            return step
+        key = graph_key(smp, self.per_row, queue, (self.K, self.N) if self.K else None,
+                        bool(self.K) and self.table is not None, self.cnt is not None, self.logprobs)
+        if key not in self.sgraphs:
+            self.sgraphs[key], _ = self._capture(step)
+        return self.sgraphs[key].replay
 
     DONE_POLL = 16  # run(): replays between two host looks at the finished flags
 
@@ -971,29 +1016,16 @@ class Decoder:
         three penalties: as in ``sample_into``; on a penalising decoder the key gains ``("pen", rp,
         pp, fp)``, the identity (1, 0, 0) when none is passed.  A decoder with ``logprobs=N`` records
         every draw (``lp`` / ``top_ids`` / ``top_lp``) and its key gains ``("lp", N)``."""
-        stop_token = _stop(stop_token)
-        assert stop_token is None or self.per_row, "a stop token needs Decoder(..., per_row=True)"
-        top_p, min_p = sampling_filters(top_p, min_p)
-        pen = _pen_kw(sampling_penalties(repetition_penalty, presence_penalty, frequency_penalty))
-        drawn = self._pen(**pen)  # the sampler's keywords: refused here if this decoder has no table
+        smp = sampling(temperature, top_k, stop_token, top_p, min_p, repetition_penalty, presence_penalty,
+                       frequency_penalty)
+        assert smp.stop_token is None or self.per_row, "a stop token needs Decoder(..., per_row=True)"
+        self._pen(smp)  # a penalty on a decoder without the table: refused here, whatever n and the mode
         if self.K:
             if queue:
                 raise ValueError("a speculative decoder does not serve a queue")
-            return self._run_spec(n, temperature, top_k, stop_token, top_p, min_p)
-        step = lambda: self._step_sample_impl(temperature, top_k, stop_token, top_p, min_p, queue, **pen)  # noqa: E731
-        if self.use_graph:
-            key = (float(temperature), top_k, stop_token) if self.per_row else (float(temperature), top_k)
-            if top_p is not None or min_p is not None:  # without them: the keys (and graphs) of the top-k sampler
-                key += (top_p, min_p)
-            if queue:
-                key += ("queue",)
-            if drawn:
-                key += ("pen", drawn["repetition_penalty"], drawn["presence_penalty"], drawn["frequency_penalty"])
-            if self.logprobs is not None:
-                key += ("lp", self.logprobs)
-            if key not in self.sgraphs:
-                self.sgraphs[key], _ = self._capture(step)
-            step = self.sgraphs[key].replay
+            return self._run_spec(n, smp)
+        step = self._replay(lambda: self._step_sample_impl(smp, queue), smp, queue)
+        stop_token = smp.stop_token
         ran = 0
         while ran < n:
             if stop_token is not None and ran and ran % self.DONE_POLL == 0 and bool(self.done.all()):
@@ -1003,7 +1035,7 @@ class Decoder:
         if self.use_graph:
             self.replays += ran
 
-    def _run_spec(self, n, temperature, top_k, stop_token, top_p, min_p):
+    def _run_spec(self, n, smp):
         """``run`` on a speculative decoder: every unfinished row gets n more tokens (``end`` = its
         position + n), the first drafts are made, and the step (``_spec_step_impl``, captured once per
         sampling key with ``("spec", K, N)`` added) is replayed until every row is done, looked for
@@ -1013,15 +1045,7 @@ class Decoder:
         self.end.copy_(torch.clamp(self.pos + n, max=self.T))
         ops.ngram_draft(self.gen, self.pos, self.tok, self.K, self.N, self.T, self.table,
                         out=(self.stok, self.spos, self.cpos))
-        step = lambda: self._spec_step_impl(temperature, top_k, stop_token, top_p, min_p)  # noqa: E731
-        if self.use_graph:
-            key = (float(temperature), top_k, stop_token)
-            if top_p is not None or min_p is not None:
-                key += (top_p, min_p)
-            key += ("spec", self.K, self.N) + (("table",) if self.table is not None else ())
-            if key not in self.sgraphs:
-                self.sgraphs[key], _ = self._capture(step)
-            step = self.sgraphs[key].replay
+        step = self._replay(lambda: self._spec_step_impl(smp), smp)
         # between two host looks: DONE_POLL replays, or fewer when the rows cannot need that many (a row
         # that is ``left`` tokens short needs at least ceil(left / (K + 1)) more steps), so the tail of a
         # well-drafted run is not padded with idle replays
@@ -1053,28 +1077,6 @@ class Decoder:
         return p if self.per_row else p * self.B
 
 
-def sampling_filters(top_p=None, min_p=None):
-    """Validated (top_p, min_p) with a filter that is off (``top_p`` >= 1, ``min_p`` 0) as None."""
-    ops.check_sampling_filters(top_p, min_p)
-    return (None if top_p is None or float(top_p) >= 1.0 else float(top_p),
-            None if min_p is None or float(min_p) <= 0.0 else float(min_p))
-
-
-def sampling_penalties(repetition_penalty=None, presence_penalty=None, frequency_penalty=None):
-    """Validated (repetition_penalty, presence_penalty, frequency_penalty) as floats, or None when
-    all three are off (1, 0 and 0, or None)."""
-    ops.check_sampling_penalties(repetition_penalty, presence_penalty, frequency_penalty)
-    pen = (1.0 if repetition_penalty is None else float(repetition_penalty),
-           0.0 if presence_penalty is None else float(presence_penalty),
-           0.0 if frequency_penalty is None else float(frequency_penalty))
-    return None if pen == (1.0, 0.0, 0.0) else pen
-
-
-def _pen_kw(pen) -> dict:
-    """``sampling_penalties``' result as the keywords of the sampling calls (off: none)."""
-    return {} if pen is None else dict(repetition_penalty=pen[0], presence_penalty=pen[1], frequency_penalty=pen[2])
-
-
 def sample_next(logits: torch.Tensor, temperature: float = 1.0, top_k: int | None = None,
                 generator: torch.Generator | None = None, top_p: float | None = None,
                 min_p: float | None = None, counts: torch.Tensor | None = None,
@@ -1084,8 +1086,8 @@ def sample_next(logits: torch.Tensor, temperature: float = 1.0, top_k: int | Non
     ``top_p`` and ``min_p`` (``ops.filter_logits``), softmax, multinomial -> [B, 1].  With
     ``counts`` ([B, >= V]: how often every id occurs in the row's whole text) the raw logits are
     penalised first (``ops.penalize_logits``); ``counts`` itself is the caller's to update."""
-    top_p, min_p = sampling_filters(top_p, min_p)
-    pen = sampling_penalties(repetition_penalty, presence_penalty, frequency_penalty)
+    _, _, _, top_p, min_p, pen = sampling(temperature, top_k, None, top_p, min_p, repetition_penalty, presence_penalty,
+                                          frequency_penalty)
     if pen is not None:
         if counts is None:
             raise ValueError("sampling penalties need counts")
@@ -1104,23 +1106,14 @@ def _mode(B, per_row=False, quantize=None, kv_quantize=None, slots=None, spec=(0
           logprobs=None) -> dict:
     """The decoder a call needs, as ``Decoder``'s arguments (and ``Decoder.fits``'s): B rows, per_row
     or not, the two quantizations, ``slots``, the row-cache slots of a shared_prompt decoder
-    (None: an unshared one), ``spec``, the (K, N) of ``_check_spec`` (K > 0: a speculative
-    one, which is per_row), and ``penalize``: one with a count table, for a call with a penalty on
-    (which speculation does not compose with: ValueError), and ``logprobs``: one with the
-    log-probability buffers of that many alternatives (None: without; with speculation: ValueError)."""
-    logprobs = _check_logprobs(logprobs, spec[0])
-    mode = dict(batch_size=B, per_row=per_row, quantize=quantize, kv_quantize=kv_quantize,
-                shared_prompt=slots is not None, max_new=slots)
-    if spec[0]:
-        if penalize:
-            raise ValueError("speculate cannot be combined with sampling penalties: a verified position's counts "
-                             "would have to include the drafts before it")
-        mode.update(per_row=True, speculate=spec[0], spec_ngram=spec[1])
-    if penalize:
-        mode.update(penalize=True)
-    if logprobs is not None:
-        mode.update(logprobs=logprobs)
-    return mode
+    (None: an unshared one), ``spec``, the (K, N) of ``_check`` (K > 0: a speculative one, which
+    is per_row), ``penalize``: one with a count table, for a call with a penalty on, and ``logprobs``:
+    one with the log-probability buffers of that many alternatives (None: without).  ``_check`` has
+    refused what does not compose."""
+    K, N = spec
+    return dict(batch_size=B, per_row=per_row or bool(K), quantize=quantize, kv_quantize=kv_quantize,
+                shared_prompt=slots is not None, max_new=slots, speculate=K or None, spec_ngram=N,
+                penalize=bool(penalize), logprobs=logprobs)
 
 
 def _build(model, mode, use_graph=None):
@@ -1149,22 +1142,24 @@ def _nothing_to_share(sharing, L, N, T):
 
 def _cached_mode(model, idx, max_new_tokens, quantize, kv_quantize, shared_prompt, speculate=None, spec_ngram=3,
                  penalize=False, logprobs=None):
-    """The mode of the decoder ``generate_cached`` runs this call on (None: the recompute loop).
-    ``penalize``: the call has a penalty on; ``logprobs``: it wants the log-probabilities."""
-    logprobs = _check_logprobs(logprobs, speculate)
+    """``generate_cached``'s plan -> (mode, cached): the mode of the decoder the call runs on, validated
+    (``_check``), or ``cached`` False: no new tokens, or the recompute loop, and ``mode`` is the
+    ordinary decoder's all the same.  ``penalize``: the call has a penalty on; ``logprobs``: it wants the
+    log-probabilities."""
+    K, N, logprobs = _check(quantize, kv_quantize, shared_prompt, speculate=speculate, spec_ngram=spec_ngram,
+                            penalize=penalize, logprobs=logprobs)
     B, T0 = idx.shape
     T = model.config.block_size
-    _check_mode(quantize, kv_quantize, shared_prompt)
-    spec = _check_spec(speculate, spec_ngram, kv_quantize, shared_prompt)
-    if spec[0] and penalize:
-        _mode(B, spec=spec, penalize=True)  # raises
+    plain = _mode(B, False, quantize, kv_quantize, spec=(K, N), penalize=penalize, logprobs=logprobs)
+    if max_new_tokens <= 0:
+        return plain, False
     if shared_prompt:
         if not bool((idx == idx[:1]).all()):
             raise ValueError("shared_prompt needs every row of idx to be the same prompt")
         if B > 1:  # a single row goes the ordinary way
             if T0 + max_new_tokens > T:
                 raise _nothing_to_share("shared_prompt", T0, max_new_tokens, T)
-            return _mode(B, False, quantize, slots=max_new_tokens, penalize=penalize, logprobs=logprobs)
+            return _mode(B, False, quantize, slots=max_new_tokens, penalize=penalize, logprobs=logprobs), True
     if T0 + max_new_tokens - 1 > T:
         if quantize:
             raise ValueError("quantize needs the KV-cache path: prompt + new tokens exceed block_size, and the "
@@ -1172,11 +1167,11 @@ def _cached_mode(model, idx, max_new_tokens, quantize, kv_quantize, shared_promp
         if kv_quantize:
             raise ValueError("kv_quantize needs the KV-cache path: prompt + new tokens exceed block_size, and the "
                              "recompute loop has no cache to quantize")
-        if spec[0]:
+        if K:
             raise ValueError("speculate needs the KV-cache path: prompt + new tokens exceed block_size, and the "
                              "recompute loop decodes one token per pass")
-        return None
-    return _mode(B, False, quantize, kv_quantize, spec=spec, penalize=penalize, logprobs=logprobs)
+        return plain, False
+    return plain, True
 
 
 def cached_decoder(model, idx, max_new_tokens, use_graph=None, quantize=None, kv_quantize=None, shared_prompt=False,
@@ -1188,11 +1183,8 @@ def cached_decoder(model, idx, max_new_tokens, use_graph=None, quantize=None, kv
     draws from torch's generator, and a seeded run keeps its tokens.  With a penalty on it is a
     penalising one, with ``logprobs`` one that records them."""
     pen = sampling_penalties(repetition_penalty, presence_penalty, frequency_penalty) is not None
-    mode = max_new_tokens > 0 and _cached_mode(model, idx, max_new_tokens, quantize, kv_quantize, shared_prompt,
-                                               speculate, spec_ngram, pen, logprobs)
-    return _build(model, mode or _mode(idx.shape[0], False, quantize, kv_quantize,
-                                       spec=_check_spec(speculate, spec_ngram, kv_quantize), penalize=pen,
-                                       logprobs=logprobs), use_graph)
+    return _build(model, _cached_mode(model, idx, max_new_tokens, quantize, kv_quantize, shared_prompt, speculate,
+                                      spec_ngram, pen, logprobs)[0], use_graph)
 
 
 @torch.no_grad()
@@ -1244,26 +1236,32 @@ def generate_cached(model, idx: torch.Tensor, max_new_tokens: int, temperature: 
     ``sample.py``'s num_samples loop captures once.  The caller releases it; without one, or
     with one that does not fit, a temporary decoder is built and released here."""
     T0 = idx.shape[1]
-    top_p, min_p = sampling_filters(top_p, min_p)
-    logprobs = _check_logprobs(logprobs, speculate)
+    smp = sampling(temperature, top_k, None, top_p, min_p, repetition_penalty, presence_penalty, frequency_penalty)
+    mode, cached = _cached_mode(model, idx, max_new_tokens, quantize, kv_quantize, shared_prompt, speculate, spec_ngram,
+                                smp.penalties is not None, logprobs)
+    logprobs = mode["logprobs"]
     if max_new_tokens <= 0:
-        return idx if logprobs is None else (idx, _no_records(idx.shape[0], logprobs, idx.device))
-    pen = _pen_kw(sampling_penalties(repetition_penalty, presence_penalty, frequency_penalty))
-    mode = _cached_mode(model, idx, max_new_tokens, quantize, kv_quantize, shared_prompt, speculate, spec_ngram,
-                        bool(pen), logprobs)
-    if mode is None:
+        return _with_records(idx, logprobs, lambda: _no_records(idx.shape[0], logprobs, idx.device))
+    if not cached:
         # the caches hold block_size positions; nanoGPT crops the context beyond that
-        lpk = {} if logprobs is None else dict(logprobs=logprobs)
-        return model.generate(idx, max_new_tokens, temperature=temperature, top_k=top_k, top_p=top_p, min_p=min_p,
-                              **pen, **lpk)
+        rp, pp, fp = smp.penalties or (None, None, None)
+        return model.generate(idx, max_new_tokens, temperature=smp.temperature, top_k=smp.top_k, top_p=smp.top_p,
+                              min_p=smp.min_p, repetition_penalty=rp, presence_penalty=pp, frequency_penalty=fp,
+                              logprobs=logprobs)
     with _borrow(model, mode, decoder, use_graph) as dec:
         if dec.K:
             dec.set_draft_table(spec_table)
         logits = dec.prefill_shared(idx[0]) if dec.shared else dec.prefill(idx)
-        dec.sample_into(logits, temperature, top_k, None, top_p, min_p, **pen)  # pos = T0: gen[:, T0]
-        dec.run(max_new_tokens - 1, temperature, top_k, None, top_p, min_p, **pen)
+        dec.sample_into(logits, smp, None)  # pos = T0: gen[:, T0]
+        dec.run(max_new_tokens - 1, smp)
         out = torch.cat([idx, dec.gen[:, T0:T0 + max_new_tokens]], dim=1)
-        return out if logprobs is None else (out, dec.records(slice(None), T0, T0 + max_new_tokens))
+        return _with_records(out, logprobs, lambda: dec.records(slice(None), T0, T0 + max_new_tokens))
+
+
+def _with_records(out, logprobs, records):
+    """What a call returns: ``out`` if ``logprobs`` is off, otherwise ``(out, records)``; ``records`` may be a
+    function that makes them, called only then."""
+    return out if logprobs is None else (out, records() if callable(records) else records)
 
 
 def _no_records(B, N, device) -> "ops.LogProbs":
@@ -1306,8 +1304,9 @@ def _batch_plan(model, prompts, max_new_tokens, quantize, kv_quantize, shared_pr
     """What ``generate_batch`` does with a call -> (prompts, budgets, queue, fit, P, mode): the
     flattened prompts on the model's device, every prompt's budget of new tokens, whether they are
     served as a queue, the indices of the prompts that share the decoder (the others go alone), the
-    length of the prefix they share through ``prefill_suffixes`` (0: none) and the decoder's mode
-    (None: no prompt fits).  None: there is nothing to generate."""
+    length of the prefix they share through ``prefill_suffixes`` (0: none) and the decoder's mode,
+    validated (``_check``; no prompt fits: the ordinary one of a row per prompt all the same).  ``budgets``
+    None: there is nothing to generate."""
     queue = batch_size is not None or not isinstance(max_new_tokens, int)
     if queue:
         if batch_size is not None and (not isinstance(batch_size, int) or batch_size < 1):
@@ -1320,11 +1319,9 @@ def _batch_plan(model, prompts, max_new_tokens, quantize, kv_quantize, shared_pr
                 raise ValueError(f"{len(budgets)} budgets for {len(prompts)} prompts")
             if any(n < 1 for n in budgets):
                 raise ValueError(f"every budget must be at least 1, got {budgets}")
-    _check_mode(quantize, kv_quantize, shared_prompt, shared_prefix)
-    spec = _check_spec(speculate, spec_ngram, kv_quantize, shared_prompt, shared_prefix, queue)
-    logprobs = _check_logprobs(logprobs, spec[0])
-    if spec[0] and penalize:
-        _mode(len(prompts), True, spec=spec, penalize=True)  # raises
+    *spec, logprobs = _check(quantize, kv_quantize, shared_prompt, shared_prefix, queue, speculate, spec_ngram,
+                             penalize, logprobs)
+    plain = _mode(len(prompts), True, quantize, kv_quantize, spec=spec, penalize=penalize, logprobs=logprobs)
     assert all(p.numel() >= 1 for p in prompts), "every prompt needs at least one token"
     device = model.lm_head.weight.device
     prompts = [p.view(-1).to(device) for p in prompts]
@@ -1332,7 +1329,7 @@ def _batch_plan(model, prompts, max_new_tokens, quantize, kv_quantize, shared_pr
         raise ValueError("shared_prompt needs every prompt to be the same")
     if isinstance(max_new_tokens, int):
         if max_new_tokens <= 0:
-            return None
+            return prompts, None, queue, [], 0, plain
         budgets = [max_new_tokens] * len(prompts)
     T = model.config.block_size
     P = common_prefix_len(prompts) if shared_prefix and len(prompts) > 1 else 0  # one prompt, no prefix: ordinary
@@ -1346,7 +1343,7 @@ def _batch_plan(model, prompts, max_new_tokens, quantize, kv_quantize, shared_pr
             if i not in fit:
                 raise _nothing_to_share(sharing, p.numel(), budgets[i], T)
     if not fit:
-        return prompts, budgets, queue, fit, P, None
+        return prompts, budgets, queue, fit, P, plain
     B = len(fit) if batch_size is None else min(batch_size, len(fit))
     slots = None
     if sharing and B >= 2:  # a single row goes the ordinary way
@@ -1363,12 +1360,9 @@ def batch_decoder(model, prompts, max_new_tokens, use_graph=None, quantize=None,
     that shares none (no new tokens, or no prompt that fits the cache) gets the ordinary one of a
     row per prompt, for the reason ``cached_decoder`` gives.  With a penalty on it is a penalising one."""
     pen = sampling_penalties(repetition_penalty, presence_penalty, frequency_penalty) is not None
-    plan = _batch_plan(model, prompts, max_new_tokens, quantize, kv_quantize, shared_prompt, shared_prefix, batch_size,
-                       speculate, spec_ngram, pen, logprobs)
-    mode = plan and plan[-1]
-    return _build(model, mode or _mode(len(prompts), True, quantize, kv_quantize,
-                                       spec=_check_spec(speculate, spec_ngram, kv_quantize), penalize=pen,
-                                       logprobs=logprobs), use_graph)
+    mode = _batch_plan(model, prompts, max_new_tokens, quantize, kv_quantize, shared_prompt, shared_prefix, batch_size,
+                       speculate, spec_ngram, pen, logprobs)[-1]
+    return _build(model, mode, use_graph)
 
 
 @torch.no_grad()
@@ -1444,34 +1438,33 @@ def generate_batch(model, prompts, max_new_tokens, temperature: float = 1.0, top
     ``generate_cached`` (``quantize`` / ``kv_quantize`` / ``shared_prompt``: ValueError).
     ``shared_prefix=True``, ``batch_size < 1`` and a budget list of the wrong length or with an
     entry < 1 raise ValueError.  With ``batch_size=None`` and an int budget nothing changes."""
-    pen = _pen_kw(sampling_penalties(repetition_penalty, presence_penalty, frequency_penalty))
-    logprobs = _check_logprobs(logprobs, speculate)
-    plan = _batch_plan(model, prompts, max_new_tokens, quantize, kv_quantize, shared_prompt, shared_prefix, batch_size,
-                       speculate, spec_ngram, bool(pen), logprobs)
-    stop_token = _stop(stop_token)
-    sampling = (temperature, top_k, stop_token, *sampling_filters(top_p, min_p))
-    if plan is None:
-        outs = [p.view(-1) for p in prompts]
-        return outs if logprobs is None else (outs, [_row(_no_records(1, logprobs, p.device), 0, 0) for p in outs])
-    prompts, budgets, queue, fit, P, mode = plan
+    smp = sampling(temperature, top_k, stop_token, top_p, min_p, repetition_penalty, presence_penalty,
+                   frequency_penalty)
+    given = prompts
+    prompts, budgets, queue, fit, P, mode = _batch_plan(model, prompts, max_new_tokens, quantize, kv_quantize,
+                                                        shared_prompt, shared_prefix, batch_size, speculate,
+                                                        spec_ngram, smp.penalties is not None, logprobs)
+    logprobs = mode["logprobs"]
+    if budgets is None:
+        outs = [p.view(-1) for p in given]
+        return _with_records(outs, logprobs, lambda: [_row(_no_records(1, logprobs, p.device), 0, 0) for p in outs])
     outs: list = [None] * len(prompts)
     lps: list = [None] * len(prompts)
     for i, p in enumerate(prompts):
         if i not in fit:  # alone through ``generate_cached``: the recompute loop, or a decoder of its own
-            y = generate_cached(model, p[None], budgets[i], temperature=temperature, top_k=top_k, use_graph=use_graph,
-                                top_p=top_p, min_p=min_p, quantize=quantize, kv_quantize=kv_quantize,
-                                speculate=speculate, spec_ngram=spec_ngram,
-                                spec_table=None if spec_table is None else [spec_table[i]], logprobs=logprobs, **pen)
+            y = generate_cached(model, p[None], budgets[i], smp._replace(stop_token=None), use_graph=use_graph,
+                                quantize=quantize, kv_quantize=kv_quantize, speculate=speculate, spec_ngram=spec_ngram,
+                                spec_table=None if spec_table is None else [spec_table[i]], logprobs=logprobs)
             if logprobs is not None:
                 y, rec = y
-            outs[i] = _result(p, y[0][p.numel():], stop_token)
+            outs[i] = _result(p, y[0][p.numel():], smp.stop_token)
             if logprobs is not None:
                 lps[i] = _row(rec, 0, outs[i].numel() - p.numel())
     if not fit:
-        return outs if logprobs is None else (outs, lps)
+        return _with_records(outs, logprobs, lps)
     with _borrow(model, mode, decoder, use_graph) as dec:
         if queue:
-            news = dec.serve([prompts[i] for i in fit], [budgets[i] for i in fit], *sampling, **pen)
+            news = dec.serve([prompts[i] for i in fit], [budgets[i] for i in fit], smp)
             if logprobs is not None:
                 news, recs = news
         else:
@@ -1484,15 +1477,15 @@ def generate_batch(model, prompts, max_new_tokens, temperature: float = 1.0, top
                 if dec.K:
                     dec.set_draft_table(None if spec_table is None else [spec_table[i] for i in fit])
                 logits = dec.prefill(*_right_pad([prompts[i] for i in fit], dec.device))
-            dec.sample_into(logits, *sampling, **pen)  # gen[b, its prompt's length]
-            dec.run(max_new_tokens - 1, *sampling, **pen)
+            dec.sample_into(logits, smp, None)  # gen[b, its prompt's length]
+            dec.run(max_new_tokens - 1, smp)
         for b, i in enumerate(fit):
             L = prompts[i].numel()
             outs[i] = (_result(prompts[i], news[b]) if queue else
-                       _result(prompts[i], dec.gen[b, L:L + max_new_tokens], stop_token))
+                       _result(prompts[i], dec.gen[b, L:L + max_new_tokens], smp.stop_token))
             if logprobs is not None:  # exactly the new tokens, through the stop token
                 lps[i] = recs[b] if queue else dec.records(b, L, outs[i].numel())
-    return outs if logprobs is None else (outs, lps)
+    return _with_records(outs, logprobs, lps)
 
 
 def _row(rec, b, n) -> "ops.LogProbs":

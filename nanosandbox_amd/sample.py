@@ -295,9 +295,9 @@ def main(argv=None):
             raise ValueError("--serve_batch cannot admit suffixes against a shared prefix yet: it cannot be combined "
                              "with --shared_prefix")
     if c["speculate"]:
-        from .runtime.decode import _check_spec
-        _check_spec(c["speculate"], c["spec_ngram"], c["kv_quantize"], c["shared_prompt"], c["shared_prefix"],
-                    bool(c["serve_batch"]))
+        from .runtime.decode import _check
+        _check(None, c["kv_quantize"] or None, c["shared_prompt"], c["shared_prefix"], bool(c["serve_batch"]),
+               c["speculate"], c["spec_ngram"])
         if not c["kv_cache"]:
             raise ValueError("--speculate needs the KV-cache path: the recompute loop (--kv_cache=False) decodes one "
                              "token per pass")
