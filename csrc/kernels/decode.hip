@@ -302,17 +302,15 @@ int gemv_row_nc() {  // default 4: measured per-token decode (graph) 124M 0.372 
 
 // NSA_GEMV1_NC: columns per workgroup of the plain one-row GEMV (default 2: the narrow
 // MLP down-projection, N = C, gets C / 2 workgroups; 4 / 8 measured 1-3% slower per token)
-int gemv1_nc(int N) {
+int gemv1_nc() {
   static const int n = env_nc("NSA_GEMV1_NC");
-  (void)N;
   return n ? n : 2;
 }
 
 template <int PRO>
 hipError_t launch_gemv_row(const RowPro& a, const void* W, const void* bias, void* y, int N, int K, int act,
                            int out_f32, hipStream_t s) {
-  // the row, plus the chunk weights of the attention combine
-  const size_t lds = (size_t)(K + (PRO == PRO_ATTN ? (K / DA_D) * a.n_split : 0)) * sizeof(float);
+  const size_t lds = row_lds_bytes<PRO>(a, K);
   const bf16_t* w = (const bf16_t*)W;
   const bf16_t* b = (const bf16_t*)bias;
   // at most gemv_row_grid() workgroups, each looping over column blocks (the vocabulary
@@ -320,24 +318,20 @@ hipError_t launch_gemv_row(const RowPro& a, const void* W, const void* bias, voi
   const int nc = gemv_row_nc();
   const int nblk = (N + nc - 1) / nc;
   const unsigned grid = (unsigned)std::min(nblk, gemv_row_grid());
-#define NSA_ROW(NC_)                                                                      \
-  do {                                                                                    \
-    if (act)                                                                              \
-      gemv_row_kernel<PRO, 1, false, NC_><<<grid, 256, lds, s>>>(a, w, b, y, N, K);      \
-    else if (out_f32)                                                                     \
-      gemv_row_kernel<PRO, 0, true, NC_><<<grid, 256, lds, s>>>(a, w, b, y, N, K);       \
-    else                                                                                  \
-      gemv_row_kernel<PRO, 0, false, NC_><<<grid, 256, lds, s>>>(a, w, b, y, N, K);      \
-  } while (0)
+  auto launch = [&](auto NC) {
+    epilogue_dispatch(act, out_f32, [&](auto ACT, auto OUTF) {
+      gemv_row_kernel<PRO, decltype(ACT)::value, decltype(OUTF)::value, decltype(NC)::value>
+          <<<grid, 256, lds, s>>>(a, w, b, y, N, K);
+    });
+  };
   if (nc == 16)
-    NSA_ROW(16);
+    launch(int_c<16>{});
   else if (nc == 4)
-    NSA_ROW(4);
+    launch(int_c<4>{});
   else if (nc == 2)
-    NSA_ROW(2);
+    launch(int_c<2>{});
   else
-    NSA_ROW(8);
-#undef NSA_ROW
+    launch(int_c<8>{});
   return hipGetLastError();
 }
 
@@ -531,26 +525,24 @@ __global__ __launch_bounds__(NW * 64) void skinny_gemm_kernel(const bf16_t* __re
 // y[rows, N] = act(x[rows, K] W[N, K]^T + b) for 2 <= rows <= 64 (N % 16 == 0, K % 32 == 0)
 NSA_API hipError_t nsa_skinny_gemm(const void* x, const void* W, const void* bias, void* y, int rows, int N, int K,
                                    int act, int out_f32, hipStream_t s) {
-  if (rows < 1 || rows > 64 || N % 16 || K % 32 || N < 16 || K < 32 || (act && out_f32)) return hipErrorInvalidValue;
+  if (rows < 1 || rows > SKINNY_MAX_ROWS || N % 16 || K % SKINNY_K_BF16 || N < 16 || K < SKINNY_K_BF16 ||
+      (act && out_f32))
+    return hipErrorInvalidValue;
   const unsigned grid = (unsigned)(N / 16);
-#define NSA_SKINNY(MT)                                                                                            \
-  do {                                                                                                            \
-    if (act)                                                                                                      \
-      skinny_gemm_kernel<MT, 1, false><<<grid, 256, 0, s>>>((const bf16_t*)x, (const bf16_t*)W, (const bf16_t*)bias, \
-                                                            y, rows, N, K);                                       \
-    else if (out_f32)                                                                                             \
-      skinny_gemm_kernel<MT, 0, true><<<grid, 256, 0, s>>>((const bf16_t*)x, (const bf16_t*)W, (const bf16_t*)bias,  \
-                                                           y, rows, N, K);                                        \
-    else                                                                                                          \
-      skinny_gemm_kernel<MT, 0, false><<<grid, 256, 0, s>>>((const bf16_t*)x, (const bf16_t*)W, (const bf16_t*)bias, \
-                                                            y, rows, N, K);                                       \
-  } while (0)
+  auto launch = [&](auto MT) {
+    epilogue_dispatch(act, out_f32, [&](auto ACT, auto OUTF) {
+      skinny_gemm_kernel<decltype(MT)::value, decltype(ACT)::value, decltype(OUTF)::value>
+          <<<grid, 256, 0, s>>>((const bf16_t*)x, (const bf16_t*)W, (const bf16_t*)bias, y, rows, N, K);
+    });
+  };
   // NW = 16 waves per workgroup (1024 threads) measured slower in the decode graph: GPT-2
   // 124M / 1.5B batch 8 0.733 / 3.84 ms/token vs 0.532 / 3.34 with NW = 4
-  if (rows <= 16) NSA_SKINNY(1);
-  else if (rows <= 32) NSA_SKINNY(2);
-  else NSA_SKINNY(4);
-#undef NSA_SKINNY
+  if (rows <= 16)
+    launch(int_c<1>{});
+  else if (rows <= 32)
+    launch(int_c<2>{});
+  else
+    launch(int_c<4>{});
   return hipGetLastError();
 }
 
@@ -635,20 +627,17 @@ __global__ __launch_bounds__(256) void skinny_ln_gemm_kernel(const float* __rest
 NSA_API hipError_t nsa_skinny_ln_gemm(const void* res, const void* branch, void* s_out, const void* lw,
                                       const void* lb, float eps, const void* W, const void* bias, void* y, int rows,
                                       int N, int K, int act, int out_f32, hipStream_t s) {
-  if (rows < 1 || rows > 16 || N % 16 || K % 32 || N < 16 || K < 32 || K > 1920 || (act && out_f32) ||
-      (branch && !s_out))
+  if (rows < 1 || rows > SKINNY_GROUP_ROWS || N % 16 || K % SKINNY_K_BF16 || N < 16 || K < SKINNY_K_BF16 ||
+      K > SKINNY_LN_MAX_K || (act && out_f32) || (branch && !s_out))
     return hipErrorInvalidValue;
   const unsigned grid = (unsigned)(N / 16);
   const size_t lds = (size_t)16 * (K + 8) * sizeof(bf16_t);
   if (!branch) s_out = nullptr;  // s is res itself: nothing to write (as the single-row kernel)
-#define NSA_SKLN(A, F)                                                                                    \
-  skinny_ln_gemm_kernel<A, F><<<grid, 256, lds, s>>>((const float*)res, (const bf16_t*)branch, (float*)s_out, \
-                                                     (const bf16_t*)lw, (const bf16_t*)lb, eps, (const bf16_t*)W, \
-                                                     (const bf16_t*)bias, y, rows, N, K)
-  if (act) NSA_SKLN(1, false);
-  else if (out_f32) NSA_SKLN(0, true);
-  else NSA_SKLN(0, false);
-#undef NSA_SKLN
+  epilogue_dispatch(act, out_f32, [&](auto ACT, auto OUTF) {
+    skinny_ln_gemm_kernel<decltype(ACT)::value, decltype(OUTF)::value><<<grid, 256, lds, s>>>(
+        (const float*)res, (const bf16_t*)branch, (float*)s_out, (const bf16_t*)lw, (const bf16_t*)lb, eps,
+        (const bf16_t*)W, (const bf16_t*)bias, y, rows, N, K);
+  });
   return hipGetLastError();
 }
 
@@ -657,45 +646,30 @@ NSA_API hipError_t nsa_skinny_ln_gemm(const void* res, const void* branch, void*
 // bias may be NULL.
 NSA_API hipError_t nsa_gemv(const void* x, const void* W, const void* bias, void* y, int rows, int N, int K, int act,
                             int out_f32, hipStream_t s) {
-  if (rows < 1 || rows > 8 || K % 8 || N < 1 || (act && out_f32)) return hipErrorInvalidValue;
-  const unsigned grid = (unsigned)((N + 7) / 8);
-#define NSA_GEMV(MR)                                                                                        \
-  do {                                                                                                      \
-    if (act)                                                                                                \
-      gemv_kernel<MR, 1, false><<<grid, 256, 0, s>>>((const bf16_t*)x, (const bf16_t*)W, (const bf16_t*)bias, \
-                                                     y, rows, N, K);                                        \
-    else if (out_f32)                                                                                       \
-      gemv_kernel<MR, 0, true><<<grid, 256, 0, s>>>((const bf16_t*)x, (const bf16_t*)W, (const bf16_t*)bias,  \
-                                                    y, rows, N, K);                                         \
-    else                                                                                                    \
-      gemv_kernel<MR, 0, false><<<grid, 256, 0, s>>>((const bf16_t*)x, (const bf16_t*)W, (const bf16_t*)bias, \
-                                                     y, rows, N, K);                                        \
-  } while (0)
+  if (rows < 1 || rows > GEMV_MAX_ROWS || K % ROW_K_BF16 || N < 1 || (act && out_f32)) return hipErrorInvalidValue;
+  auto launch = [&](auto M, auto NC) {  // M: rows the kernel is built for; NC: columns per workgroup
+    const unsigned grid = (unsigned)((N + decltype(NC)::value - 1) / decltype(NC)::value);
+    epilogue_dispatch(act, out_f32, [&](auto ACT, auto OUTF) {
+      gemv_kernel<decltype(M)::value, decltype(ACT)::value, decltype(OUTF)::value, decltype(NC)::value>
+          <<<grid, 256, 0, s>>>((const bf16_t*)x, (const bf16_t*)W, (const bf16_t*)bias, y, rows, N, K);
+    });
+  };
   if (rows == 1) {
     // one row: NC columns per workgroup (narrow outputs need more, smaller workgroups to
     // keep enough weight bytes in flight)
-    const int nc = gemv1_nc(N);
-    const unsigned g1 = (unsigned)((N + nc - 1) / nc);
-#define NSA_GEMV1(NC_)                                                                                       \
-  do {                                                                                                       \
-    if (act)                                                                                                 \
-      gemv_kernel<1, 1, false, NC_><<<g1, 256, 0, s>>>((const bf16_t*)x, (const bf16_t*)W, (const bf16_t*)bias, \
-                                                       y, 1, N, K);                                          \
-    else if (out_f32)                                                                                        \
-      gemv_kernel<1, 0, true, NC_><<<g1, 256, 0, s>>>((const bf16_t*)x, (const bf16_t*)W, (const bf16_t*)bias,  \
-                                                      y, 1, N, K);                                           \
-    else                                                                                                     \
-      gemv_kernel<1, 0, false, NC_><<<g1, 256, 0, s>>>((const bf16_t*)x, (const bf16_t*)W, (const bf16_t*)bias, \
-                                                       y, 1, N, K);                                          \
-  } while (0)
-    if (nc == 2) NSA_GEMV1(2);
-    else if (nc == 4) NSA_GEMV1(4);
-    else NSA_GEMV1(8);
-#undef NSA_GEMV1
-  } else if (rows == 2) NSA_GEMV(2);
-  else if (rows <= 4) NSA_GEMV(4);
-  else NSA_GEMV(8);
-#undef NSA_GEMV
+    const int nc = gemv1_nc();
+    if (nc == 2)
+      launch(int_c<1>{}, int_c<2>{});
+    else if (nc == 4)
+      launch(int_c<1>{}, int_c<4>{});
+    else
+      launch(int_c<1>{}, int_c<8>{});
+  } else if (rows == 2)
+    launch(int_c<2>{}, int_c<8>{});
+  else if (rows <= 4)
+    launch(int_c<4>{}, int_c<8>{});
+  else
+    launch(int_c<8>{}, int_c<8>{});
   return hipGetLastError();
 }
 
@@ -706,17 +680,9 @@ NSA_API hipError_t nsa_gemv(const void* x, const void* W, const void* bias, void
 NSA_API hipError_t nsa_gemv_ln(const void* res, const void* branch, void* res_out, const void* lw, const void* lb,
                                const void* W, const void* bias, void* y, int N, int K, float eps, int act,
                                int out_f32, void* pos_inc, hipStream_t s) {
-  if (K % 8 || K > 8192 || N < 1 || (act && out_f32) || (branch && (!res_out || res_out == res)))
-    return hipErrorInvalidValue;
-  RowPro a{};
-  a.res = (const float*)res;
-  a.branch = (const bf16_t*)branch;
-  a.res_out = (float*)res_out;
-  a.lw = (const bf16_t*)lw;
-  a.lb = (const bf16_t*)lb;
-  a.eps = eps;
-  a.pos_inc = (int64_t*)pos_inc;
-  return launch_gemv_row<PRO_LN>(a, W, bias, y, N, K, act, out_f32, s);
+  if (!row_ln_ok(res, branch, res_out, N, K, ROW_K_BF16, act, out_f32)) return hipErrorInvalidValue;
+  return launch_gemv_row<PRO_LN>(row_ln(res, branch, res_out, lw, lb, eps, pos_inc), W, bias, y, N, K, act, out_f32,
+                                 s);
 }
 
 // First decode linear of a single-row step: res_out = wte[*tok] + wpe[*pos] (fp32, the
@@ -724,27 +690,15 @@ NSA_API hipError_t nsa_gemv_ln(const void* res, const void* branch, void* res_ou
 NSA_API hipError_t nsa_gemv_emb_ln(const void* tok, const void* pos, const void* wte, const void* wpe, void* res_out,
                                    const void* lw, const void* lb, const void* W, const void* bias, void* y, int N,
                                    int K, float eps, int act, int out_f32, hipStream_t s) {
-  if (K % 8 || K > 8192 || N < 1 || (act && out_f32) || !res_out) return hipErrorInvalidValue;
-  RowPro a{};
-  a.res_out = (float*)res_out;
-  a.lw = (const bf16_t*)lw;
-  a.lb = (const bf16_t*)lb;
-  a.eps = eps;
-  a.tok = (const int64_t*)tok;
-  a.pos = (const int64_t*)pos;
-  a.wte = (const bf16_t*)wte;
-  a.wpe = (const bf16_t*)wpe;
-  return launch_gemv_row<PRO_EMB_LN>(a, W, bias, y, N, K, act, out_f32, s);
+  if (!row_emb_ln_ok(res_out, N, K, ROW_K_BF16, act, out_f32)) return hipErrorInvalidValue;
+  return launch_gemv_row<PRO_EMB_LN>(row_emb_ln(tok, pos, wte, wpe, res_out, lw, lb, eps), W, bias, y, N, K, act,
+                                     out_f32, s);
 }
 
 // Single-row linear over the attention output: x = combine of the decode-attention
 // partials ws (nsa_decode_attn with out == NULL, batch 1), K = H * 64.
 NSA_API hipError_t nsa_gemv_attn(const void* ws, int n_split, const void* W, const void* bias, void* y, int N, int K,
                                  int act, int out_f32, hipStream_t s) {
-  if (K % DA_D || K > 8192 || N < 1 || n_split < 1 || (K / DA_D) * n_split > 16384 || (act && out_f32))
-    return hipErrorInvalidValue;
-  RowPro a{};
-  a.ws = (const float*)ws;
-  a.n_split = n_split;
-  return launch_gemv_row<PRO_ATTN>(a, W, bias, y, N, K, act, out_f32, s);
+  if (!row_attn_ok(n_split, N, K, act, out_f32)) return hipErrorInvalidValue;
+  return launch_gemv_row<PRO_ATTN>(row_attn(ws, n_split), W, bias, y, N, K, act, out_f32, s);
 }

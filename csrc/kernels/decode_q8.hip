@@ -150,16 +150,19 @@ __global__ __launch_bounds__(256) void gemv_q8_kernel(const bf16_t* __restrict__
 // together, with no K loop: chunks past the end re-read the last chunk against a zeroed x
 // (branch-free), rows past N re-read row N - 1 and are not stored.
 // ---------------------------------------------------------------------------
-struct Q8Cfg {
-  int kw, p;
-};
-// the fewest waves along K that cover the row in one pass; two passes beyond 4096
-Q8Cfg q8_cfg(int K) {
+// the fewest waves along K that cover the row in one pass; two passes beyond 4096:
+// f(int_c<KW>, int_c<P>)
+template <typename F>
+void q8_cfg(int K, F&& f) {
   const int nck = K / 16;
-  if (nck <= 64) return {1, 1};
-  if (nck <= 128) return {2, 1};
-  if (nck <= 256) return {4, 1};
-  return {4, 2};  // nck <= 512 (callers check)
+  if (nck <= 64)
+    f(int_c<1>{}, int_c<1>{});
+  else if (nck <= 128)
+    f(int_c<2>{}, int_c<1>{});
+  else if (nck <= 256)
+    f(int_c<4>{}, int_c<1>{});
+  else
+    f(int_c<4>{}, int_c<2>{});  // nck <= 512 (callers check)
 }
 // the weights of block row set n0 into wp (all P * NC loads in flight together)
 template <int NC, int P>
@@ -324,37 +327,23 @@ __global__ __launch_bounds__(256) void gemv1_q8_kernel(const bf16_t* __restrict_
 template <int PRO>
 hipError_t launch_gemv_row_q8(const RowPro& a, const void* Wq, const void* scale, const void* bias, void* y, int N,
                               int K, int act, int out_f32, hipStream_t s) {
-  // the row, plus the chunk weights of the attention combine
-  const size_t lds = (size_t)(K + (PRO == PRO_ATTN ? (K / DA_D) * a.n_split : 0)) * sizeof(float);
+  const size_t lds = row_lds_bytes<PRO>(a, K);
   const int8_t* w = (const int8_t*)Wq;
   const float* sc = (const float*)scale;
   const bf16_t* b = (const bf16_t*)bias;
-  const Q8Cfg cfg = q8_cfg(K);
-  // columns per wave set: 4 as the bf16 kernel, 2 where one wave covers K (K <= 1024: 8 columns per
-  // block; measured per token at batch 1, GPT-2 124M: 0.309 ms with 2, 0.319 with 4; bf16 0.336)
-  const int nc = cfg.kw == 1 ? 2 : 4;
-  // at most gemv_row_grid() workgroups, each looping over column blocks
-  const int bn = (4 / cfg.kw) * nc;
-  const int nblk = (N + bn - 1) / bn;
-  const unsigned grid = (unsigned)std::min(nblk, gemv_row_grid());
-#define NSA_ROWQ(NC_, KW_, P_)                                                                       \
-  do {                                                                                               \
-    if (act)                                                                                         \
-      gemv_row_q8_kernel<PRO, 1, false, NC_, KW_, P_><<<grid, 256, lds, s>>>(a, w, sc, b, y, N, K); \
-    else if (out_f32)                                                                                \
-      gemv_row_q8_kernel<PRO, 0, true, NC_, KW_, P_><<<grid, 256, lds, s>>>(a, w, sc, b, y, N, K);  \
-    else                                                                                             \
-      gemv_row_q8_kernel<PRO, 0, false, NC_, KW_, P_><<<grid, 256, lds, s>>>(a, w, sc, b, y, N, K); \
-  } while (0)
-  if (cfg.kw == 1)
-    NSA_ROWQ(2, 1, 1);
-  else if (cfg.kw == 2)
-    NSA_ROWQ(4, 2, 1);
-  else if (cfg.p == 1)
-    NSA_ROWQ(4, 4, 1);
-  else
-    NSA_ROWQ(4, 4, 2);
-#undef NSA_ROWQ
+  q8_cfg(K, [&](auto KW, auto P) {
+    // columns per wave set: 4 as the bf16 kernel, 2 where one wave covers K (K <= 1024: 8 columns per
+    // block; measured per token at batch 1, GPT-2 124M: 0.309 ms with 2, 0.319 with 4; bf16 0.336)
+    constexpr int kw = decltype(KW)::value, nc = kw == 1 ? 2 : 4;
+    // at most gemv_row_grid() workgroups, each looping over column blocks
+    constexpr int bn = (4 / kw) * nc;
+    const int nblk = (N + bn - 1) / bn;
+    const unsigned grid = (unsigned)std::min(nblk, gemv_row_grid());
+    epilogue_dispatch(act, out_f32, [&](auto ACT, auto OUTF) {
+      gemv_row_q8_kernel<PRO, decltype(ACT)::value, decltype(OUTF)::value, nc, kw, decltype(P)::value>
+          <<<grid, 256, lds, s>>>(a, w, sc, b, y, N, K);
+    });
+  });
   return hipGetLastError();
 }
 
@@ -498,53 +487,38 @@ __global__ __launch_bounds__(256) void skinny_ln_gemm_q8_kernel(const float* __r
 // Wq int8, scale fp32, x / b bf16; act: 0 none, 1 exact-erf GELU; out_f32: y is fp32.
 NSA_API hipError_t nsa_gemv_q8(const void* x, const void* Wq, const void* scale, const void* bias, void* y, int rows,
                                int N, int K, int act, int out_f32, hipStream_t s) {
-  if (rows < 1 || rows > 8 || K % 16 || K < 16 || N < 1 || (act && out_f32)) return hipErrorInvalidValue;
-#define NSA_GEMVQ(MR)                                                                                         \
-  do {                                                                                                        \
-    const unsigned grid = (unsigned)((N + 7) / 8);                                                            \
-    if (act)                                                                                                  \
-      gemv_q8_kernel<MR, 1, false, 8, 4><<<grid, 256, 0, s>>>((const bf16_t*)x, (const int8_t*)Wq,             \
-                                                              (const float*)scale, (const bf16_t*)bias, y,    \
-                                                              rows, N, K);                                    \
-    else if (out_f32)                                                                                         \
-      gemv_q8_kernel<MR, 0, true, 8, 4><<<grid, 256, 0, s>>>((const bf16_t*)x, (const int8_t*)Wq,              \
-                                                             (const float*)scale, (const bf16_t*)bias, y,     \
-                                                             rows, N, K);                                     \
-    else                                                                                                      \
-      gemv_q8_kernel<MR, 0, false, 8, 4><<<grid, 256, 0, s>>>((const bf16_t*)x, (const int8_t*)Wq,             \
-                                                              (const float*)scale, (const bf16_t*)bias, y,    \
-                                                              rows, N, K);                                    \
-  } while (0)
-  if (rows == 1 && K <= 8192) {
+  if (rows < 1 || rows > GEMV_MAX_ROWS || K % ROW_K_Q8 || K < ROW_K_Q8 || N < 1 || (act && out_f32))
+    return hipErrorInvalidValue;
+  const bf16_t* xb = (const bf16_t*)x;
+  const int8_t* w = (const int8_t*)Wq;
+  const float* sc = (const float*)scale;
+  const bf16_t* b = (const bf16_t*)bias;
+  auto launch = [&](auto M) {  // the K loop of the multi-row kernel
+    const unsigned grid = (unsigned)((N + 7) / 8);
+    epilogue_dispatch(act, out_f32, [&](auto ACT, auto OUTF) {
+      gemv_q8_kernel<decltype(M)::value, decltype(ACT)::value, decltype(OUTF)::value, 8, 4>
+          <<<grid, 256, 0, s>>>(xb, w, sc, b, y, rows, N, K);
+    });
+  };
+  if (rows == 1 && K <= ROW_MAX_K) {
     // one row: 2 columns per wave set (narrow outputs need many small workgroups to keep
     // enough weight bytes in flight), as the bf16 kernel's NSA_GEMV1_NC default
-    const Q8Cfg cfg = q8_cfg(K);
-    const unsigned g1 = (unsigned)((N + (4 / cfg.kw) * 2 - 1) / ((4 / cfg.kw) * 2));
-#define NSA_GEMV1Q(KW_, P_)                                                                                   \
-  do {                                                                                                        \
-    if (act)                                                                                                  \
-      gemv1_q8_kernel<1, false, 2, KW_, P_><<<g1, 256, 0, s>>>((const bf16_t*)x, (const int8_t*)Wq,            \
-                                                               (const float*)scale, (const bf16_t*)bias, y, N, \
-                                                               K);                                            \
-    else if (out_f32)                                                                                         \
-      gemv1_q8_kernel<0, true, 2, KW_, P_><<<g1, 256, 0, s>>>((const bf16_t*)x, (const int8_t*)Wq,             \
-                                                              (const float*)scale, (const bf16_t*)bias, y, N, \
-                                                              K);                                             \
-    else                                                                                                      \
-      gemv1_q8_kernel<0, false, 2, KW_, P_><<<g1, 256, 0, s>>>((const bf16_t*)x, (const int8_t*)Wq,            \
-                                                               (const float*)scale, (const bf16_t*)bias, y, N, \
-                                                               K);                                            \
-  } while (0)
-    if (cfg.kw == 1) NSA_GEMV1Q(1, 1);
-    else if (cfg.kw == 2) NSA_GEMV1Q(2, 1);
-    else if (cfg.p == 1) NSA_GEMV1Q(4, 1);
-    else NSA_GEMV1Q(4, 2);
-#undef NSA_GEMV1Q
-  } else if (rows == 1) NSA_GEMVQ(1);  // K > 8192: the K loop of the multi-row kernel
-  else if (rows == 2) NSA_GEMVQ(2);
-  else if (rows <= 4) NSA_GEMVQ(4);
-  else NSA_GEMVQ(8);
-#undef NSA_GEMVQ
+    q8_cfg(K, [&](auto KW, auto P) {
+      constexpr int bn = (4 / decltype(KW)::value) * 2;
+      const unsigned g1 = (unsigned)((N + bn - 1) / bn);
+      epilogue_dispatch(act, out_f32, [&](auto ACT, auto OUTF) {
+        gemv1_q8_kernel<decltype(ACT)::value, decltype(OUTF)::value, 2, decltype(KW)::value, decltype(P)::value>
+            <<<g1, 256, 0, s>>>(xb, w, sc, b, y, N, K);
+      });
+    });
+  } else if (rows == 1)  // wider than ROW_MAX_K
+    launch(int_c<1>{});
+  else if (rows == 2)
+    launch(int_c<2>{});
+  else if (rows <= 4)
+    launch(int_c<4>{});
+  else
+    launch(int_c<8>{});
   return hipGetLastError();
 }
 
@@ -552,17 +526,9 @@ NSA_API hipError_t nsa_gemv_q8(const void* x, const void* Wq, const void* scale,
 NSA_API hipError_t nsa_gemv_ln_q8(const void* res, const void* branch, void* res_out, const void* lw, const void* lb,
                                   const void* Wq, const void* scale, const void* bias, void* y, int N, int K,
                                   float eps, int act, int out_f32, void* pos_inc, hipStream_t s) {
-  if (K % 16 || K < 16 || K > 8192 || N < 1 || (act && out_f32) || (branch && (!res_out || res_out == res)))
-    return hipErrorInvalidValue;
-  RowPro a{};
-  a.res = (const float*)res;
-  a.branch = (const bf16_t*)branch;
-  a.res_out = (float*)res_out;
-  a.lw = (const bf16_t*)lw;
-  a.lb = (const bf16_t*)lb;
-  a.eps = eps;
-  a.pos_inc = (int64_t*)pos_inc;
-  return launch_gemv_row_q8<PRO_LN>(a, Wq, scale, bias, y, N, K, act, out_f32, s);
+  if (K < ROW_K_Q8 || !row_ln_ok(res, branch, res_out, N, K, ROW_K_Q8, act, out_f32)) return hipErrorInvalidValue;
+  return launch_gemv_row_q8<PRO_LN>(row_ln(res, branch, res_out, lw, lb, eps, pos_inc), Wq, scale, bias, y, N, K, act,
+                                    out_f32, s);
 }
 
 // nsa_gemv_emb_ln with an int8 linear (the wte / wpe rows stay bf16)
@@ -570,49 +536,35 @@ NSA_API hipError_t nsa_gemv_emb_ln_q8(const void* tok, const void* pos, const vo
                                       void* res_out, const void* lw, const void* lb, const void* Wq, const void* scale,
                                       const void* bias, void* y, int N, int K, float eps, int act, int out_f32,
                                       hipStream_t s) {
-  if (K % 16 || K < 16 || K > 8192 || N < 1 || (act && out_f32) || !res_out) return hipErrorInvalidValue;
-  RowPro a{};
-  a.res_out = (float*)res_out;
-  a.lw = (const bf16_t*)lw;
-  a.lb = (const bf16_t*)lb;
-  a.eps = eps;
-  a.tok = (const int64_t*)tok;
-  a.pos = (const int64_t*)pos;
-  a.wte = (const bf16_t*)wte;
-  a.wpe = (const bf16_t*)wpe;
-  return launch_gemv_row_q8<PRO_EMB_LN>(a, Wq, scale, bias, y, N, K, act, out_f32, s);
+  if (K < ROW_K_Q8 || !row_emb_ln_ok(res_out, N, K, ROW_K_Q8, act, out_f32)) return hipErrorInvalidValue;
+  return launch_gemv_row_q8<PRO_EMB_LN>(row_emb_ln(tok, pos, wte, wpe, res_out, lw, lb, eps), Wq, scale, bias, y, N,
+                                        K, act, out_f32, s);
 }
 
 // nsa_gemv_attn with int8 weights (K = H * 64: a multiple of 16)
 NSA_API hipError_t nsa_gemv_attn_q8(const void* ws, int n_split, const void* Wq, const void* scale, const void* bias,
                                     void* y, int N, int K, int act, int out_f32, hipStream_t s) {
-  if (K % DA_D || K < DA_D || K > 8192 || N < 1 || n_split < 1 || (K / DA_D) * n_split > 16384 || (act && out_f32))
-    return hipErrorInvalidValue;
-  RowPro a{};
-  a.ws = (const float*)ws;
-  a.n_split = n_split;
-  return launch_gemv_row_q8<PRO_ATTN>(a, Wq, scale, bias, y, N, K, act, out_f32, s);
+  if (K < DA_D || !row_attn_ok(n_split, N, K, act, out_f32)) return hipErrorInvalidValue;
+  return launch_gemv_row_q8<PRO_ATTN>(row_attn(ws, n_split), Wq, scale, bias, y, N, K, act, out_f32, s);
 }
 
 // y[rows, N] = act((x[rows, K] Wq[N, K]^T) * scale[N] + b) for 2 <= rows <= 16, any N, K % 64 == 0
 NSA_API hipError_t nsa_skinny_gemm_q8(const void* x, const void* Wq, const void* scale, const void* bias, void* y,
                                       int rows, int N, int K, int act, int out_f32, hipStream_t s) {
-  if (rows < 1 || rows > 16 || K % 64 || K < 64 || N < 1 || (act && out_f32)) return hipErrorInvalidValue;
+  if (rows < 1 || rows > SKINNY_GROUP_ROWS || K % SKINNY_K_Q8 || K < SKINNY_K_Q8 || N < 1 || (act && out_f32))
+    return hipErrorInvalidValue;
   const unsigned grid = (unsigned)((N + 15) / 16);
-#define NSA_SKQ(A, F, UN_)                                                                                   \
-  skinny_gemm_q8_kernel<A, F, UN_><<<grid, 256, 0, s>>>((const bf16_t*)x, (const int8_t*)Wq, (const float*)scale, \
-                                                        (const bf16_t*)bias, y, rows, N, K)
+  auto launch = [&](auto UN) {
+    epilogue_dispatch(act, out_f32, [&](auto ACT, auto OUTF) {
+      skinny_gemm_q8_kernel<decltype(ACT)::value, decltype(OUTF)::value, decltype(UN)::value><<<grid, 256, 0, s>>>(
+          (const bf16_t*)x, (const int8_t*)Wq, (const float*)scale, (const bf16_t*)bias, y, rows, N, K);
+    });
+  };
   // 4 units (1024 k over the workgroup) in flight per round up to K = 1024, 8 beyond
-  if (K <= 1024) {
-    if (act) NSA_SKQ(1, false, 4);
-    else if (out_f32) NSA_SKQ(0, true, 4);
-    else NSA_SKQ(0, false, 4);
-  } else {
-    if (act) NSA_SKQ(1, false, 8);
-    else if (out_f32) NSA_SKQ(0, true, 8);
-    else NSA_SKQ(0, false, 8);
-  }
-#undef NSA_SKQ
+  if (K <= 1024)
+    launch(int_c<4>{});
+  else
+    launch(int_c<8>{});
   return hipGetLastError();
 }
 
@@ -621,19 +573,16 @@ NSA_API hipError_t nsa_skinny_ln_gemm_q8(const void* res, const void* branch, vo
                                          const void* lb, float eps, const void* Wq, const void* scale,
                                          const void* bias, void* y, int rows, int N, int K, int act, int out_f32,
                                          hipStream_t s) {
-  if (rows < 1 || rows > 16 || K % 64 || K < 64 || K > 1920 || N < 1 || (act && out_f32) || (branch && !s_out))
+  if (rows < 1 || rows > SKINNY_GROUP_ROWS || K % SKINNY_K_Q8 || K < SKINNY_K_Q8 || K > SKINNY_LN_MAX_K || N < 1 ||
+      (act && out_f32) || (branch && !s_out))
     return hipErrorInvalidValue;
   if (!branch) s_out = nullptr;  // s is res itself: nothing to write (as the single-row kernel)
   const unsigned grid = (unsigned)((N + 15) / 16);
   const size_t lds = (size_t)16 * (K + 8) * sizeof(bf16_t);
-#define NSA_SKLNQ(A, F)                                                                                         \
-  skinny_ln_gemm_q8_kernel<A, F><<<grid, 256, lds, s>>>((const float*)res, (const bf16_t*)branch, (float*)s_out,   \
-                                                        (const bf16_t*)lw, (const bf16_t*)lb, eps,                 \
-                                                        (const int8_t*)Wq, (const float*)scale,                    \
-                                                        (const bf16_t*)bias, y, rows, N, K)
-  if (act) NSA_SKLNQ(1, false);
-  else if (out_f32) NSA_SKLNQ(0, true);
-  else NSA_SKLNQ(0, false);
-#undef NSA_SKLNQ
+  epilogue_dispatch(act, out_f32, [&](auto ACT, auto OUTF) {
+    skinny_ln_gemm_q8_kernel<decltype(ACT)::value, decltype(OUTF)::value><<<grid, 256, lds, s>>>(
+        (const float*)res, (const bf16_t*)branch, (float*)s_out, (const bf16_t*)lw, (const bf16_t*)lb, eps,
+        (const int8_t*)Wq, (const float*)scale, (const bf16_t*)bias, y, rows, N, K);
+  });
   return hipGetLastError();
 }

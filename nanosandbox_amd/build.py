@@ -61,6 +61,13 @@ def _run(cmd):
 FILE_FLAGS = {"flash_attn.hip": ["-fno-slp-vectorize"], "flash_attn_f16.hip": ["-fno-slp-vectorize"]}
 
 
+def kernel_flags(src, defines=(), file_flags=None, include_dir=os.path.join(CSRC, "kernels")):
+    """The hipcc flags one ``csrc/kernels`` source is compiled with (before ``-c src -o obj``)."""
+    ff = FILE_FLAGS if file_flags is None else file_flags
+    return [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-munsafe-fp-atomics",
+            "-I", include_dir, *[f"-D{d}" for d in defines], *ff.get(os.path.basename(src), [])]
+
+
 def build_kernels(force=False, jobs=8, verbose=True, defines=(), lib_path=KERNEL_LIB, obj_dir=BUILD_DIR,
                   file_flags=None):
     srcs = sorted(glob.glob(os.path.join(CSRC, "kernels", "*.hip")))
@@ -70,8 +77,6 @@ def build_kernels(force=False, jobs=8, verbose=True, defines=(), lib_path=KERNEL
     os.makedirs(obj_dir, exist_ok=True)
     os.makedirs(os.path.dirname(lib_path), exist_ok=True)
     hipcc = _hipcc()
-    flags = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden",
-             "-munsafe-fp-atomics", "-I", os.path.join(CSRC, "kernels"), *[f"-D{d}" for d in defines]]
 
     def deps(src):
         # sources a kernel file #includes from this directory (flash_attn_f16.hip is
@@ -82,12 +87,10 @@ def build_kernels(force=False, jobs=8, verbose=True, defines=(), lib_path=KERNEL
                 out.append(os.path.join(os.path.dirname(src), line.split('"')[1]))
         return out
 
-    ff = FILE_FLAGS if file_flags is None else file_flags
-
     def compile_one(src):
         obj = os.path.join(obj_dir, os.path.basename(src) + ".o")
         if force or _newer(obj, [src] + headers + deps(src) + [os.path.abspath(__file__)]):
-            _run([hipcc, *flags, *ff.get(os.path.basename(src), []), "-c", src, "-o", obj])
+            _run([hipcc, *kernel_flags(src, defines, file_flags), "-c", src, "-o", obj])
             if verbose:
                 print(f"  [hipcc {ARCH}] {os.path.relpath(src, ROOT)}")
         return obj

@@ -1399,6 +1399,36 @@ def _stream_weight(w):
     return "", (compute_weight(w, BF16),)
 
 
+def _stream_call(kind, lead, w, b, y_shape, device, dims, gelu=False, out_f32=False, *extra):
+    """One weight-streaming decode kernel, ``nsa_<kind>`` or its ``_q8`` form by the type of ``w``:
+    (*lead, W | (Wq, scale), bias, y, *dims, act, out_f32, *extra, stream); returns y.  ``lead``
+    and ``extra`` are passed as they are: pointers of tensors the caller holds, and numbers."""
+    sfx, wt = _stream_weight(w)
+    bc = compute_weight(b, BF16) if b is not None else None
+    # sizes unpacked: passed as one tuple they take torch's slow argument path, ~1.5 us of host time a call
+    y = torch.empty(*y_shape, device=device, dtype=F32 if out_f32 else BF16)
+    _lib.call("nsa_" + kind + sfx, *lead, *map(_lib.ptr, wt), _lib.ptr(bc), _lib.ptr(y), *dims,
+              1 if gelu else 0, 1 if out_f32 else 0, *extra, _lib.stream())
+    return y
+
+
+def _ln_operands(res, branch, ln_w, ln_b, shape):
+    """The operands (res, branch, s_out, ln_w, ln_b) the LayerNorm-prologue kernels take, rows as
+    ``shape``, and s = res + branch as the caller returns it (res itself without a branch)."""
+    r2 = res.reshape(*shape).contiguous()
+    br = branch.reshape(*shape).contiguous() if branch is not None else None
+    s_out = torch.empty_like(r2) if branch is not None else None
+    lw, lb = compute_weight(ln_w, BF16), compute_weight(ln_b, BF16) if ln_b is not None else None
+    return (r2, br, s_out, lw, lb), (s_out.view(res.shape) if branch is not None else res)
+
+
+# What the kernels' entry points accept (csrc/kernels/decode_rows.h; they refuse anything else)
+_ROW_K = {False: 8, True: 16}      # ROW_K_BF16, ROW_K_Q8: K granule of the GEMV kernels, by int8 weights
+_SKINNY_K = {False: 32, True: 64}  # SKINNY_K_BF16, SKINNY_K_Q8: K granule of the skinny kernels
+_ROW_MAX_K = 8192                  # ROW_MAX_K: widest row of the single-row prologue kernels
+_SKINNY_LN_MAX_K = 1920            # SKINNY_LN_MAX_K: widest row of the skinny LayerNorm kernels
+
+
 GEMV_MAX_ROWS = int(os.environ.get("NSA_GEMV_MAX_ROWS", "1"))
 # decode batches of 2..SKINNY_MAX_ROWS rows: the MFMA weight-streaming kernel (nsa_skinny_gemm).
 # HIP-graph decode, ms/token (GPT-2 124M / 1.5B): batch 8 0.685 / 4.24 with the library GEMM,
@@ -1431,30 +1461,19 @@ def decode_linear(x, w, b=None, gelu: bool = False, out_f32: bool = False):
     q8 = isinstance(w, QuantWeight)
     N = w.shape[0]
     if isinstance(x, AttnPartials):  # one row; the attention combine runs in the GEMV prologue
-        y = torch.empty(N, device=x.ws.device, dtype=F32 if out_f32 else BF16)
-        sfx, wt = _stream_weight(w)
-        _lib.call("nsa_gemv_attn" + sfx, _lib.ptr(x.ws), x.n_split, *map(_lib.ptr, wt),
-                  _lib.ptr(compute_weight(b, BF16) if b is not None else None), _lib.ptr(y), N, x.C,
-                  1 if gelu else 0, 1 if out_f32 else 0, _lib.stream())
+        y = _stream_call("gemv_attn", (_lib.ptr(x.ws), x.n_split), w, b, (N,), x.ws.device, (N, x.C), gelu, out_f32)
         return y.view(1, 1, N)
     K = x.shape[-1]
     rows = x.numel() // K
-    if x.is_cuda and x.dtype == BF16 and rows <= GEMV_MAX_ROWS and K % (16 if q8 else 8) == 0:
-        x2 = x.reshape(rows, K).contiguous()
-        sfx, wt = _stream_weight(w)
-        bc = compute_weight(b, BF16) if b is not None else None
-        y = torch.empty(rows, N, device=x.device, dtype=F32 if out_f32 else BF16)
-        _lib.call("nsa_gemv" + sfx, _lib.ptr(x2), *map(_lib.ptr, wt), _lib.ptr(bc), _lib.ptr(y), rows, N, K,
-                  1 if gelu else 0, 1 if out_f32 else 0, _lib.stream())
-        return y.view(*x.shape[:-1], N)
-    if (x.is_cuda and x.dtype == BF16 and 2 <= rows <= SKINNY_MAX_ROWS and K % (64 if q8 else 32) == 0
+    kind = None
+    if x.is_cuda and x.dtype == BF16 and rows <= GEMV_MAX_ROWS and K % _ROW_K[q8] == 0:
+        kind = "gemv"
+    elif (x.is_cuda and x.dtype == BF16 and 2 <= rows <= SKINNY_MAX_ROWS and K % _SKINNY_K[q8] == 0
             and (q8 or N % 16 == 0) and not (gelu and out_f32)):
+        kind = "skinny_gemm"
+    if kind:
         x2 = x.reshape(rows, K).contiguous()
-        sfx, wt = _stream_weight(w)
-        bc = compute_weight(b, BF16) if b is not None else None
-        y = torch.empty(rows, N, device=x.device, dtype=F32 if out_f32 else BF16)
-        _lib.call("nsa_skinny_gemm" + sfx, _lib.ptr(x2), *map(_lib.ptr, wt), _lib.ptr(bc), _lib.ptr(y), rows, N, K,
-                  1 if gelu else 0, 1 if out_f32 else 0, _lib.stream())
+        y = _stream_call(kind, (_lib.ptr(x2),), w, b, (rows, N), x.device, (rows, N, K), gelu, out_f32)
         return y.view(*x.shape[:-1], N)
     if q8:
         w = dequantize(w).to(x.dtype)
@@ -1476,40 +1495,22 @@ def decode_linear_ln(res, branch, ln_w, ln_b, w, b=None, gelu: bool = False, out
     q8 = isinstance(w, QuantWeight)  # the _q8 form of the same kernel; else decode_linear's fallback
     C = res.shape[-1]
     rows = res.numel() // C
-    if (res.is_cuda and res.dtype == F32 and rows == 1 and GEMV_MAX_ROWS >= 1 and C % (16 if q8 else 8) == 0
-            and C <= 8192 and (branch is None or branch.dtype == BF16)):
-        N = w.shape[0]
-        r2 = res.reshape(C).contiguous()
-        br = branch.reshape(C).contiguous() if branch is not None else None
-        s_out = torch.empty_like(r2) if branch is not None else None
-        lw, lb = compute_weight(ln_w, BF16), compute_weight(ln_b, BF16) if ln_b is not None else None
-        sfx, wt = _stream_weight(w)
-        bc = compute_weight(b, BF16) if b is not None else None
-        y = torch.empty(N, device=res.device, dtype=F32 if out_f32 else BF16)
-        _lib.call("nsa_gemv_ln" + sfx, _lib.ptr(r2), _lib.ptr(br), _lib.ptr(s_out), _lib.ptr(lw), _lib.ptr(lb),
-                  *map(_lib.ptr, wt), _lib.ptr(bc), _lib.ptr(y), N, C, LN_EPS, 1 if gelu else 0,
-                  1 if out_f32 else 0, _lib.ptr(pos_inc), _lib.stream())
-        s_new = s_out.view(res.shape) if branch is not None else res
-        return s_new, y.view(*res.shape[:-1], N)
     N = w.shape[0]
-    if (res.is_cuda and res.dtype == F32 and 2 <= rows <= min(SKINNY_MAX_ROWS, SKINNY_LN_MAX_ROWS)
-            and C % (64 if q8 else 32) == 0 and C <= 1920
-            and (q8 or N % 16 == 0) and not (gelu and out_f32) and (branch is None or branch.dtype == BF16)
+    fused = res.is_cuda and res.dtype == F32 and (branch is None or branch.dtype == BF16)
+    if fused and rows == 1 and GEMV_MAX_ROWS >= 1 and C % _ROW_K[q8] == 0 and C <= _ROW_MAX_K:
+        ops, s_new = _ln_operands(res, branch, ln_w, ln_b, (C,))
+        y = _stream_call("gemv_ln", map(_lib.ptr, ops), w, b, (N,), res.device, (N, C, LN_EPS), gelu, out_f32,
+                         _lib.ptr(pos_inc))
+        return s_new, y.view(*res.shape[:-1], N)
+    if (fused and 2 <= rows <= min(SKINNY_MAX_ROWS, SKINNY_LN_MAX_ROWS) and C % _SKINNY_K[q8] == 0
+            and C <= _SKINNY_LN_MAX_K and (q8 or N % 16 == 0) and not (gelu and out_f32)
             and out_dtype in (None, BF16)):
         # 2..16 rows: residual add + LayerNorm recomputed per workgroup in the skinny GEMM's prologue
-        r2 = res.reshape(rows, C).contiguous()
-        br = branch.reshape(rows, C).contiguous() if branch is not None else None
-        s_out = torch.empty_like(r2) if branch is not None else None
-        lw, lb = compute_weight(ln_w, BF16), compute_weight(ln_b, BF16) if ln_b is not None else None
-        sfx, wt = _stream_weight(w)
-        bc = compute_weight(b, BF16) if b is not None else None
-        y = torch.empty(rows, N, device=res.device, dtype=F32 if out_f32 else BF16)
-        _lib.call("nsa_skinny_ln_gemm" + sfx, _lib.ptr(r2), _lib.ptr(br), _lib.ptr(s_out), _lib.ptr(lw), _lib.ptr(lb),
-                  LN_EPS, *map(_lib.ptr, wt), _lib.ptr(bc), _lib.ptr(y), rows, N, C, 1 if gelu else 0,
-                  1 if out_f32 else 0, _lib.stream())
+        ops, s_new = _ln_operands(res, branch, ln_w, ln_b, (rows, C))
+        y = _stream_call("skinny_ln_gemm", (*map(_lib.ptr, ops), LN_EPS), w, b, (rows, N), res.device, (rows, N, C),
+                         gelu, out_f32)
         if pos_inc is not None:
             pos_inc.add_(1)
-        s_new = s_out.view(res.shape) if branch is not None else res
         return s_new, y.view(*res.shape[:-1], N)
     if branch is None:
         s_new, h = layer_norm_pass(res, ln_w, ln_b, out_dtype=out_dtype)
@@ -1531,16 +1532,12 @@ def decode_embed_linear_ln(tok, pos, wte, wpe, ln_w, ln_b, w, b=None, dtype=BF16
     wte_c, wpe_c = compute_weight(wte, dtype), compute_weight(wpe, dtype)
     q8 = isinstance(w, QuantWeight)
     if (tok.is_cuda and B == 1 and dtype == BF16 and res_dtype == F32 and GEMV_MAX_ROWS >= 1
-            and C % (16 if q8 else 8) == 0 and C <= 8192):
+            and C % _ROW_K[q8] == 0 and C <= _ROW_MAX_K):
         N = w.shape[0]
         x = torch.empty(1, 1, C, device=tok.device, dtype=F32)
-        y = torch.empty(N, device=tok.device, dtype=BF16)
         lw, lb = compute_weight(ln_w, BF16), compute_weight(ln_b, BF16) if ln_b is not None else None
-        sfx, wt = _stream_weight(w)
-        bc = compute_weight(b, BF16) if b is not None else None
-        _lib.call("nsa_gemv_emb_ln" + sfx, _lib.ptr(tok), _lib.ptr(pos), _lib.ptr(wte_c), _lib.ptr(wpe_c), _lib.ptr(x),
-                  _lib.ptr(lw), _lib.ptr(lb), *map(_lib.ptr, wt), _lib.ptr(bc), _lib.ptr(y), N, C, LN_EPS, 0, 0,
-                  _lib.stream())
+        ops = (tok, pos, wte_c, wpe_c, x, lw, lb)
+        y = _stream_call("gemv_emb_ln", map(_lib.ptr, ops), w, b, (N,), tok.device, (N, C, LN_EPS))
         return x, y.view(1, 1, N)
     x = wte_c.index_select(0, tok.view(-1)).float() + wpe_c.index_select(0, pos.view(-1)).float()
     x = x.to(res_dtype).view(B, 1, C)
