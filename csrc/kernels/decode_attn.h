@@ -55,12 +55,24 @@ struct CacheScales<int8_t> {
 // the threads that meet position pos take the row from there in the same arithmetic as from
 // the cache, never from the global row this launch writes.  So the output is a function of
 // the cache contents only: append gives what kv_append followed by a plain call gives.
-template <typename CT>
+//
+// ANC (bf16 caches; beam search, decode_beam.hip): the key at position t is not the query's own
+// row's but that of the batch row anc[t] (int32, clamped to 0 .. anc_rows - 1), batch rows
+// anc_stride cache rows apart: it lies at cache row row0 + anc[t] * anc_stride + t, row0 now being
+// the head's offset inside batch row 0, and own is the query's batch row, where an append goes.
+// A thread fetches its key's row index first, then the K row through it, and leaves the index in
+// LDS for the threads that gather the V rows.  The arithmetic and its order are untouched, so
+// the partial is bit for bit the plain one on caches gathered through anc.
+template <typename CT, bool ANC = false>
 __device__ __forceinline__ void decode_attn_chunk(const bf16_t* __restrict__ qrow, const CT* __restrict__ kc,
                                                   const CT* __restrict__ vc, CT* kc_w, CT* vc_w,
                                                   const CacheScales<CT>& cs, int64_t row0, int pos, int Tmax, int k0,
-                                                  float* __restrict__ part, int C, float scale_log2, int append) {
+                                                  float* __restrict__ part, int C, float scale_log2, int append,
+                                                  const int* __restrict__ anc = nullptr, int64_t anc_stride = 0,
+                                                  int anc_rows = 1, int own = 0) {
   constexpr bool KV8 = sizeof(CT) == 1;
+  static_assert(!(ANC && KV8), "ancestry gathers bf16 caches only");
+  __shared__ int rs[ANC ? DA_CHUNK : 1];  // ANC: the batch row of every key of the chunk
   __shared__ float qs[DA_D];
   __shared__ float ps[DA_CHUNK];
   __shared__ float red[2][4];
@@ -75,6 +87,15 @@ __device__ __forceinline__ void decode_attn_chunk(const bf16_t* __restrict__ qro
   if (tid < DA_D) qs[tid] = bf2f(qrow[tid]);
   const int key = k0 + tid;
   const bool live = key <= pos;
+  [[maybe_unused]] int64_t arow = 0;  // ANC: this thread's key's cache row
+  if constexpr (ANC) {
+    if (live) {
+      const int r = min(max(anc[key], 0), anc_rows - 1);
+      rs[tid] = r;
+      arow = row0 + r * anc_stride + key;
+    }
+    row0 += own * anc_stride;  // from here on: the query's own rows, for the append
+  }
   // int8 caches: this thread's key row (raw bytes) and its K / V scales; the row this launch
   // appends comes from LDS instead (fresh), and its loads go to the (valid, unused) q row, not
   // to the cache row being written
@@ -142,7 +163,7 @@ __device__ __forceinline__ void decode_attn_chunk(const bf16_t* __restrict__ qro
     } else {
       // the new token's row comes from qkv when appending (this launch is what writes it to
       // the cache), as its V row does below; otherwise every row, pos included, is the cache's
-      const bf16_t* krow = (append && key == pos) ? qrow + C : kc + (row0 + key) * DA_D;
+      const bf16_t* krow = (append && key == pos) ? qrow + C : kc + (ANC ? arow : row0 + key) * DA_D;
 #pragma unroll
       for (int c = 0; c < DA_D / 8; ++c) {
         float kf[8];
@@ -185,7 +206,9 @@ __device__ __forceinline__ void decode_attn_chunk(const bf16_t* __restrict__ qro
 #pragma unroll
         for (int e = 0; e < 8; ++e) vf[e] = nq[1][8 * dg + e];
     } else {
-      const bf16_t* vr = (append && kk == pos) ? qrow + 2 * C : vc + (row0 + kk) * DA_D;
+      int64_t vrow = row0 + kk;
+      if constexpr (ANC) vrow += (rs[kk - k0] - own) * anc_stride;
+      const bf16_t* vr = (append && kk == pos) ? qrow + 2 * C : vc + vrow * DA_D;
       load8(vr + 8 * dg, vf);
     }
     const float pj = ps[8 * kg + j];

@@ -58,7 +58,9 @@ def _run(cmd):
 # softmax's adjacent f32 multiplies / adds into v_pk_*_f32, an anti-lever beside MFMAs
 # (MI355X_MICROARCH.md 'price of one filler'; A/B: scripts/attn_ab.py against a variant
 # library built with file_flags={}).
-FILE_FLAGS = {"flash_attn.hip": ["-fno-slp-vectorize"], "flash_attn_f16.hip": ["-fno-slp-vectorize"]}
+FILE_FLAGS = {"flash_attn.hip": ["-fno-slp-vectorize"], "flash_attn_f16.hip": ["-fno-slp-vectorize"],
+              # no packed fp32 arithmetic at all in the beam kernels
+              "decode_beam.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def kernel_flags(src, defines=(), file_flags=None, include_dir=os.path.join(CSRC, "kernels")):

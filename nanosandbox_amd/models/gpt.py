@@ -495,3 +495,21 @@ class GPT(nn.Module):
                               shared_prefix=shared_prefix, batch_size=batch_size, speculate=speculate,
                               spec_ngram=spec_ngram, spec_table=spec_table, repetition_penalty=repetition_penalty,
                               presence_penalty=presence_penalty, frequency_penalty=frequency_penalty, **lpk)
+
+    @torch.no_grad()
+    def generate_beam(self, idx, max_new_tokens, num_beams, stop_token=None, length_penalty=0.0, quantize=None,
+                      use_graph=None, decoder=None, kv_quantize=None, speculate=None, **sampling_keywords):
+        """Beam search from one prompt (``idx``: [T0] or [1, T0]) -> (``num_beams`` 1-D tensors, prompt + new
+        tokens, through ``stop_token`` where a hypothesis drew it; their scores fp32 [num_beams]): the most
+        likely continuations a search of that width finds, a score being the summed log-probability of
+        the new tokens under the raw logits (what ``score`` gives for the returned text), ordered by
+        ``score / length ** length_penalty`` (0.0: the raw score).  The hypotheses are the rows of a
+        shared-prompt decoder whose captured step selects the survivors on the device and lets them
+        attend over their ancestors' cached keys in place (``runtime/decode.py`` ``generate_beam``).
+        ``num_beams`` 1 .. 8 (1: greedy decoding the ordinary way); ``quantize="int8"`` composes; ``kv_quantize``,
+        ``speculate``, sampling keywords, more than one prompt and prompt + new tokens past block_size raise
+        ValueError."""
+        from ..runtime.decode import generate_beam
+        return generate_beam(self, idx, max_new_tokens, num_beams, stop_token=stop_token,
+                             length_penalty=length_penalty, quantize=quantize, use_graph=use_graph, decoder=decoder,
+                             kv_quantize=kv_quantize, speculate=speculate, **sampling_keywords)

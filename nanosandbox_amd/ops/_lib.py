@@ -137,6 +137,13 @@ _SIGNATURES = {
                                c_void_p, c_int, c_int, c_int, c_int, c_float, c_int, c_void_p],
     "nsa_decode_attn_shared_rows": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                     c_void_p, c_int, c_int, c_int, c_int, c_float, c_int, c_void_p],
+    # beam search (csrc/kernels/decode_beam.hip).  The attention: nsa_decode_attn_shared's arguments with the
+    # ancestry table src after vc.  The step: top_ids, top_lp, scores, done, length, parent, tok, src, bp_parent,
+    # bp_token, n, all_done, W, R, stop
+    "nsa_decode_attn_beam": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                             c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_int, c_void_p],
+    "nsa_beam_step": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                      c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_void_p],
     # suffix queries over a shared prefix cache + the row's own keys (csrc/kernels/prefix_attn.hip): qkv, pk, pv,
     # out, B, S, H, Tp, P, scale
     "nsa_prefix_attn": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p],

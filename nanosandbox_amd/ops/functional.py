@@ -1151,6 +1151,144 @@ def decode_attention_shared(qkv, pkc, pvc, kc, vc, plen, pos, n_head: int, appen
     return y.reshape(B, 1, C).to(qkv.dtype)
 
 
+BEAM_MAX = 8  # beams of a search (csrc/kernels/decode_beam.hip BEAM_MAX; the alternatives token_logprobs gives)
+
+
+def decode_attention_beam(qkv, pkc, pvc, kc, vc, src, plen, pos, n_head: int, append: bool = False):
+    """``decode_attention_shared`` for the hypotheses of a beam search: qkv [W, 1, 3C] -> [W, 1, C].
+
+    The caches are a shared-prompt decoder's and ``pos`` is one position for the batch.  ``src``
+    (int32 [W, R]) is the ancestry table: beam w's key at row-cache slot t is the one row
+    ``src[w, t]`` stored there, so the result is ``decode_attention_shared``'s on row caches gathered
+    as ``kc_m[w, :, t] = kc[src[w, t], :, t]``, bit for bit on the GPU, and no K / V is ever copied
+    between rows.  ``append``: the token's K / V go to (w, pos - plen), its own row, and the token
+    attends over them there whatever ``src`` says of that slot.
+
+    GPU, bf16, D = 64: one launch of ``nsa_decode_attn_beam`` (the prompt workgroups of
+    ``nsa_decode_attn_shared``; every row workgroup's threads fetch their slot's row index, then the
+    K and V rows through it) and the same combine.  Anything else: fp32 torch over the gathered keys."""
+    B, S, C3 = qkv.shape
+    C = C3 // 3
+    _, H, Tp, D = pkc.shape
+    R = kc.shape[2]
+    assert S == 1 and H == n_head and pkc.shape[0] == 1 and kc.shape[0] == B and kc.shape[1] == H and kc.shape[3] == D
+    assert not isinstance(kc, QuantCache) and not isinstance(pkc, QuantCache), "no int8 caches in the shared form"
+    assert plen.numel() == 1 and pos.numel() == 1, "one prompt length and one position for the batch"
+    assert src.shape == (B, R) and src.dtype == torch.int32 and src.is_contiguous()
+    scale = 1.0 / math.sqrt(D)
+    if qkv.is_cuda and qkv.dtype == BF16 and pkc.dtype == BF16 and kc.dtype == BF16 and D == 64:
+        assert kc.is_contiguous() and vc.is_contiguous() and pkc.is_contiguous() and pvc.is_contiguous()
+        qkv = qkv.contiguous()
+        n_split = -(-Tp // SHARED_PROMPT_CHUNK) + -(-R // 256)
+        ws = torch.empty(B * H * n_split * (4 + D), device=qkv.device, dtype=F32)
+        out = torch.empty(B, 1, C, device=qkv.device, dtype=qkv.dtype)
+        _lib.call("nsa_decode_attn_beam", _lib.ptr(qkv), _lib.ptr(pkc), _lib.ptr(pvc), _lib.ptr(kc), _lib.ptr(vc),
+                  _lib.ptr(src), _lib.ptr(plen), _lib.ptr(pos), _lib.ptr(ws), _lib.ptr(out), B, H, Tp, R, scale,
+                  1 if append else 0, _lib.stream())
+        return out
+    P = int(plen.item())
+    slot = int(pos.item()) - P
+    q, kn, vn = qkv.view(B, 3, H, D).unbind(1)                  # [B, H, D] each
+    if append and 0 <= slot < R:
+        kc[:, :, slot] = kn.to(kc.dtype)
+        vc[:, :, slot] = vn.to(vc.dtype)
+    n = min(max(slot + 1, 0), R) if slot < R else 0
+    rows = src[:, :n].long().clamp(0, B - 1)
+    if append and n:
+        rows[:, slot] = torch.arange(B, device=src.device)
+    t = torch.arange(n, device=src.device)
+    y = torch.empty(B, H, D, dtype=F32, device=qkv.device)
+    for b in range(B):
+        k = torch.cat([pkc[0, :, :P].float(), kc[rows[b], :, t].transpose(0, 1).float()], dim=1)  # [H, P + n, D]
+        v = torch.cat([pvc[0, :, :P].float(), vc[rows[b], :, t].transpose(0, 1).float()], dim=1)
+        att = torch.softmax(torch.einsum("hd,hkd->hk", q[b].float(), k) * scale, dim=-1)
+        y[b] = torch.einsum("hk,hkd->hd", att, v)
+    return y.reshape(B, 1, C).to(qkv.dtype)
+
+
+def beam_select(scores, done, top_ids, top_lp, stop_token=None):
+    """The rule of one beam-search step -> (parent int32 [W], token int64 [W], scores fp32 [W], done
+    bool [W]): the W survivors among the continuations of W hypotheses.
+
+    ``scores`` (fp32 [W]) are the hypotheses' summed log-probabilities, ``done`` (bool [W]) says which
+    are finished, and ``top_ids`` (int32) / ``top_lp`` (fp32) [W, W] are every row's W most likely ids and
+    their log-probabilities, what ``token_logprobs(logits, ., top=W)`` returns.  A live beam w offers the
+    W candidates (w, j), worth ``scores[w] + top_lp[w, j]`` (one fp32 addition) with the token ``top_ids[w,
+    j]``; a finished beam offers (w, 0) alone, worth ``scores[w]``, with ``stop_token`` (None: id 0).  The
+    candidates are ordered by (value descending, parent ascending, j ascending), values comparing as
+    floats and -inf being a value like any other, and the first W survive: survivor i continues
+    ``parent[i]`` with ``token[i]``, its score is the candidate's value, and it is finished if its parent
+    was or its token is the stop token.
+
+    A row's W best are enough: the W best of all W x V continuations lie among them.  A search
+    starts from ``scores = [0, -inf, ...]`` over W copies of the prompt's distribution, so its first
+    step is this rule too."""
+    W = scores.shape[0]
+    assert top_ids.shape == (W, W) and top_lp.shape == (W, W) and done.shape == (W,)
+    done = done.bool()
+    value = torch.where(done[:, None], scores.float()[:, None].expand(W, W), scores.float()[:, None] + top_lp.float())
+    offered = (~done[:, None] | (torch.arange(W, device=scores.device) == 0)[None, :]).reshape(-1)
+    cand = offered.nonzero().view(-1)  # (parent ascending, j ascending): a stable sort keeps it among equals
+    order = torch.sort(value.reshape(-1)[cand], descending=True, stable=True).indices[:W]
+    pick = cand[order]
+    parent = torch.div(pick, W, rounding_mode="floor")
+    was = done[parent]
+    token = top_ids.reshape(-1)[pick].to(torch.int64)
+    token = torch.where(was, torch.full_like(token, 0 if stop_token is None else stop_token), token)
+    now = was if stop_token is None else was | (token == stop_token)
+    return parent.to(torch.int32), token, value.reshape(-1)[pick], now
+
+
+def beam_step_(top_ids, top_lp, scores, done, length, parent, tok, src, bp_parent, bp_token, n, all_done,
+               stop_token=None):
+    """One beam-search step's bookkeeping, in place (2 <= W <= 8; the decoder's form of ``beam_select``):
+
+    * ``parent`` (int32 [W]), ``tok`` (int64 [W] or [W, 1]: what the next step feeds), ``scores`` (fp32 [W])
+      and ``done`` (int32 [W]) become what ``beam_select`` gives, and ``length[i]`` (int32 [W]: a
+      hypothesis's new tokens) its parent's, plus one unless the parent was finished;
+    * with ``n`` (int32 scalar tensor) the index of the token this step generates: the back-pointers
+      ``bp_parent[n, :]`` (int32 [R, W]) and ``bp_token[n, :]`` (int64 [R, W]) are the survivors' parents and
+      tokens, the ancestry table ``src`` (int32 [W, R], ``decode_attention_beam``) becomes ``src'[i, :n] =
+      src[parent[i], :n]`` and ``src'[i, n] = i``, its entries past n untouched, and ``n`` advances;
+    * ``all_done`` (int32 scalar tensor): whether every survivor is finished.
+
+    ``n`` outside 0 .. R - 1 changes nothing.  On the GPU one workgroup (``nsa_beam_step``:
+    graph-capturable, no host involvement), torch elsewhere."""
+    W, R = src.shape
+    if not 2 <= W <= BEAM_MAX:
+        raise ValueError(f"beam_step_ takes 2 .. {BEAM_MAX} beams, got {W}")
+    assert top_ids.shape == (W, W) and top_ids.dtype == torch.int32 and top_ids.is_contiguous()
+    assert top_lp.shape == (W, W) and top_lp.dtype == F32 and top_lp.is_contiguous()
+    assert scores.shape == (W,) and scores.dtype == F32 and tok.numel() == W and tok.dtype == torch.int64
+    for t in (done, length, parent):
+        assert t.shape == (W,) and t.dtype == torch.int32
+    assert src.dtype == torch.int32 and src.is_contiguous() and tok.is_contiguous()
+    assert bp_parent.shape == (R, W) and bp_parent.dtype == torch.int32 and bp_parent.is_contiguous()
+    assert bp_token.shape == (R, W) and bp_token.dtype == torch.int64 and bp_token.is_contiguous()
+    assert n.numel() == 1 and all_done.numel() == 1 and n.dtype == all_done.dtype == torch.int32
+    if scores.is_cuda:
+        _lib.call("nsa_beam_step", _lib.ptr(top_ids), _lib.ptr(top_lp), _lib.ptr(scores), _lib.ptr(done),
+                  _lib.ptr(length), _lib.ptr(parent), _lib.ptr(tok), _lib.ptr(src), _lib.ptr(bp_parent),
+                  _lib.ptr(bp_token), _lib.ptr(n), _lib.ptr(all_done), W, R,
+                  -1 if stop_token is None else int(stop_token), _lib.stream())
+        return
+    i = int(n.item())
+    if not 0 <= i < R:
+        return
+    par, token, value, now = beam_select(scores, done != 0, top_ids, top_lp, stop_token)
+    pl = par.long()
+    length.copy_(length[pl] + (done[pl] == 0).to(torch.int32))
+    src[:, :i] = src[pl, :i]
+    src[:, i] = torch.arange(W, dtype=torch.int32, device=src.device)
+    parent.copy_(par)
+    tok.view(W).copy_(token)
+    scores.copy_(value)
+    done.copy_(now.to(torch.int32))
+    bp_parent[i], bp_token[i] = par, token
+    all_done.fill_(int(now.all()))
+    n.add_(1)
+
+
 SPEC_MAX_QUERIES = 8  # queries per row of decode_attention_spec: 1 fed token + at most 7 drafts
 
 

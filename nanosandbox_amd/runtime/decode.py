@@ -134,6 +134,17 @@ per_row, ``stop_token``, ``top_p`` / ``min_p``, the penalties, both quantization
 ``shared_prefix``, the queue and eager mode; ``speculate`` raises ValueError (a verified position can
 be written by more than one step).  Without ``logprobs`` there are no buffers (``lp`` is None) and
 every launch, graph key and result is what it was.
+``Decoder(..., shared_prompt=True, num_beams=W)`` (2 <= W <= 8 = the rows) searches instead of sampling
+(``generate_beam``; ``ops.beam_select`` states a step's rule).  The W hypotheses are the rows, with one position
+for all, and the state is on the device: ``scores``, ``bdone``, ``length``, ``parent``, the back-pointers ``bp_parent``
+/ ``bp_token`` (one row per generated token), the token index ``n``, the flag ``all_done`` and the ancestry table
+``src`` (int32 [W, R]).  A survivor continues another row's text without any copy: ``src[w, t]`` names the row
+that stored hypothesis w's key at slot t, ``ops.decode_attention_beam`` reads K and V through it, and
+``ops.beam_step_`` permutes it with the survivors.  A step is the plain one with that attention, then one
+``ops.token_logprobs`` launch (every row's W most likely ids) and ``beam_step_``, captured as one graph whose key
+gains ``("beam", W, stop token)``; a finished hypothesis stays a frozen row that is fed the stop token.  With
+``quantize="int8"`` and eager mode; ``kv_quantize`` and ``speculate`` raise ValueError.  Without ``num_beams`` nothing
+of this exists: every launch, graph key and result is what it was.
 The caches hold at most ``block_size`` positions; ``GPT.generate_cached`` falls
 back to the recompute loop when prompt + new tokens exceed that (nanoGPT crops the
 context there, which a cache cannot do without re-encoding).
@@ -192,12 +203,13 @@ def sampling_penalties(repetition_penalty=None, presence_penalty=None, frequency
 
 
 def graph_key(smp: Sampling, per_row=False, queue=False, spec=None, table=False, penalize=False,
-              logprobs=None) -> tuple:
+              logprobs=None, beams=None) -> tuple:
     """The key of a captured sampling step in ``Decoder.sgraphs``: (temperature, top_k), then the stop
     token (a ``per_row`` decoder: None included), (top_p, min_p) if either is on (without them: the
     keys of the top-k sampler), ``"queue"``, ``("spec", K, N)`` (``spec`` = (K, N)) and ``"table"`` (a
     draft table is set), ``("pen", rp, pp, fp)`` on a penalising decoder (the identity (1, 0, 0) when
-    the call passes none) and ``("lp", N)`` on one that records log-probabilities."""
+    the call passes none), ``("lp", N)`` on one that records log-probabilities and ``("beam", W, stop token)``
+    on a beam decoder, whose step has the stop token built in."""
     key = (float(smp.temperature), smp.top_k) + ((smp.stop_token,) if per_row else ())
     if smp.top_p is not None or smp.min_p is not None:
         key += (smp.top_p, smp.min_p)
@@ -209,20 +221,32 @@ def graph_key(smp: Sampling, per_row=False, queue=False, spec=None, table=False,
         key += ("pen", *(smp.penalties or (1.0, 0.0, 0.0)))
     if logprobs is not None:
         key += ("lp", logprobs)
+    if beams:
+        key += ("beam", beams, smp.stop_token)
     return key
 
 
 def _check(quantize=None, kv_quantize=None, shared_prompt=False, shared_prefix=False, queue=False, speculate=None,
-           spec_ngram=3, penalize=False, logprobs=None, rows=None, max_new=None):
+           spec_ngram=3, penalize=False, logprobs=None, rows=None, max_new=None, beams=None):
     """Every rule on a mode that depends on neither the model nor the device, for ``Decoder`` and the
     front ends alike: ValueError for what does not compose, never a silent plain step -> (K, N,
     logprobs), the drafted tokens and n-gram length of a speculative call (K = 0: none) and
     ``logprobs`` validated (None: off; 0 .. 8 alternatives).  ``penalize``: a count table, or a call
-    with a penalty on; ``rows`` / ``max_new``: a decoder's own (a front end plans them afterwards)."""
+    with a penalty on; ``rows`` / ``max_new``: a decoder's own (a front end plans them afterwards);
+    ``beams``: the hypotheses of a beam search (None: no search)."""
     if quantize not in (None, "int8"):
         raise ValueError(f"quantize must be None or 'int8', got {quantize!r}")
     if kv_quantize not in (None, "int8"):
         raise ValueError(f"kv_quantize must be None or 'int8', got {kv_quantize!r}")
+    if beams is not None:
+        if isinstance(beams, bool) or int(beams) != beams or not 1 <= beams <= ops.functional.BEAM_MAX:
+            raise ValueError(f"num_beams must be an int in 1 .. {ops.functional.BEAM_MAX}, got {beams!r}")
+        if kv_quantize:
+            raise ValueError("beam search reads its hypotheses' keys through the bf16 row caches of a shared-prompt "
+                             "decoder: it cannot be combined with kv_quantize")
+        if speculate:
+            raise ValueError("beam search cannot be combined with speculate: a hypothesis continues with the step's "
+                             "survivors, not with drafts")
     if shared_prompt and kv_quantize:
         raise ValueError("shared_prompt keeps bf16 caches: it cannot be combined with kv_quantize")
     if shared_prefix and shared_prompt:
@@ -262,10 +286,16 @@ class Decoder:
     def __init__(self, model, batch_size: int, max_len: int | None = None, use_graph: bool | None = None,
                  per_row: bool = False, quantize: str | None = None, kv_quantize: str | None = None,
                  shared_prompt: bool = False, max_new: int | None = None, speculate: int | None = None,
-                 spec_ngram: int = 3, penalize: bool = False, logprobs: int | None = None):
+                 spec_ngram: int = 3, penalize: bool = False, logprobs: int | None = None,
+                 num_beams: int | None = None):
         self.K, self.N, logprobs = _check(quantize, kv_quantize, shared_prompt, speculate=speculate,
                                           spec_ngram=spec_ngram, penalize=penalize, logprobs=logprobs,
-                                          rows=batch_size, max_new=max_new)
+                                          rows=batch_size, max_new=max_new, beams=num_beams)
+        # a beam decoder: the W hypotheses are the rows of a shared-prompt decoder, one position for all
+        self.W = int(num_beams or 0)
+        if self.W:
+            assert self.W == batch_size >= 2 and shared_prompt, "beams are the rows of a shared_prompt decoder"
+            assert not per_row and not penalize and logprobs is None, "a beam search neither samples nor records"
         per_row = per_row or bool(self.K)  # a speculating row advances by its own number of positions
         self.model = model
         self.per_row = per_row
@@ -381,6 +411,23 @@ class Decoder:
             self.top_lp = torch.full((batch_size, self.T + 1, logprobs), float("nan"), device=self.device,
                                      dtype=torch.float32)
             self.lp_last = torch.full((batch_size,), -1, device=self.device, dtype=torch.int64)
+        if self.W:
+            # a search's device state.  Per hypothesis: the summed log-probability, the finished flag, the
+            # number of new tokens and the row it continued; the ancestry table src (hypothesis w's key at
+            # slot t is the one row src[w, t] stored: ``ops.decode_attention_beam``); per generated token the
+            # survivors' parents and tokens, which the result is read from; the index n of the next token,
+            # the flag the loop polls, and every row's W most likely ids with their log-probabilities
+            W, R = self.W, self.R
+
+            def ints(*shape):
+                return torch.zeros(*shape, device=self.device, dtype=torch.int32)
+            self.scores = torch.zeros(W, device=self.device, dtype=torch.float32)
+            self.bdone, self.length, self.parent = ints(W), ints(W), ints(W)
+            self.src, self.bp_parent = ints(W, R), ints(R, W)
+            self.bp_token = torch.zeros(R, W, device=self.device, dtype=torch.int64)
+            self.n, self.all_done = ints(1), ints(1)
+            self.btop = ops.LogProbs(torch.zeros(W, device=self.device, dtype=torch.float32), ints(W, W),
+                                     torch.zeros(W, W, device=self.device, dtype=torch.float32))
         self.use_graph = (self.device.type == "cuda") if use_graph is None else use_graph
         if self.use_graph and not self.graph_capable(model):
             # the fused decode kernels cover head_dim 64, bf16 and V <= 53248; the fallback
@@ -414,7 +461,7 @@ class Decoder:
                 and cfg.vocab_size <= 53248)
 
     def fits(self, batch_size, per_row=False, quantize=None, kv_quantize=None, shared_prompt=False,
-             max_new=None, speculate=None, spec_ngram=3, penalize=False, logprobs=None) -> bool:
+             max_new=None, speculate=None, spec_ngram=3, penalize=False, logprobs=None, num_beams=None) -> bool:
         """Whether a call that needs ``Decoder(model, batch_size, per_row=..., ...)`` can run on this
         one: the same rows and form, (shared) row caches of at least ``max_new`` slots, and the same
         number of drafted tokens and n-gram length (speculative), and a count table if and only if
@@ -424,7 +471,8 @@ class Decoder:
                 and self.kv_quantize == kv_quantize and self.shared == bool(shared_prompt)
                 and (not self.shared or self.R >= (max_new or self.T))
                 and self.K == K and (not K or self.N == int(spec_ngram))
-                and (self.cnt is not None) == bool(penalize) and self.logprobs == logprobs)
+                and (self.cnt is not None) == bool(penalize) and self.logprobs == logprobs
+                and self.W == int(num_beams or 0))
 
     def _quantize_weights(self):
         """int8 mode: quantize every linear weight and the tied lm_head / wte table, and point
@@ -541,7 +589,11 @@ class Decoder:
         """The token ``tok`` at position ``pos`` through the model (``_layers``) -> fp32 logits [B, V];
         ``pos`` has advanced: by the head kernel itself, or (per_row) the unfinished rows move on and
         the finished rows stay."""
-        if self.shared:
+        if self.W:
+            def attend(i, qkv):
+                return ops.decode_attention_beam(qkv, self.pkc[i], self.pvc[i], self.kc[i], self.vc[i], self.src,
+                                                 self.plen, self.pos, self.H, append=True)
+        elif self.shared:
             def attend(i, qkv):
                 return ops.decode_attention_shared(qkv, self.pkc[i], self.pvc[i], self.kc[i], self.vc[i], self.plen,
                                                    self.pos, self.H, append=True)
@@ -945,8 +997,10 @@ class Decoder:
         decoder's mode: the fed token and the position; the finished flags (a warm-up draw may hit the
         stop token); a speculative step also accepts and drafts (its fed tokens, their positions and
         the counters); a penalising decoder counts the draw (the table) and one with ``logprobs``
-        records it (the records and the marker)."""
+        records it (the records and the marker); a beam decoder's whole search state."""
         return ([self.tok, self.pos] + ([self.done] if self.per_row else [])
+                + ([self.scores, self.bdone, self.length, self.parent, self.src, self.bp_parent, self.bp_token, self.n,
+                    self.all_done, *self.btop] if self.W else [])
                 + ([self.stok, self.spos, self.cpos, self.spec_counts] if self.K else [])
                 + ([self.cnt] if self.cnt is not None else [])
                 + ([self.lp, self.top_ids, self.top_lp, self.lp_last] if self.lp is not None else []))
@@ -994,7 +1048,7 @@ class Decoder:
         if not self.use_graph:
             return step
         key = graph_key(smp, self.per_row, queue, (self.K, self.N) if self.K else None,
-                        bool(self.K) and self.table is not None, self.cnt is not None, self.logprobs)
+                        bool(self.K) and self.table is not None, self.cnt is not None, self.logprobs, self.W or None)
         if key not in self.sgraphs:
             self.sgraphs[key], _ = self._capture(step)
         return self.sgraphs[key].replay
@@ -1060,6 +1114,67 @@ class Decoder:
         if self.use_graph:
             self.replays += ran
 
+    def _beam_select(self, logits, stop_token):
+        """Close a step of the search on ``logits`` [W, >= V]: every row's W most likely ids (one
+        ``ops.token_logprobs`` launch, ``top=W``), then ``ops.beam_step_``: the survivors, the tokens the next
+        step feeds, the back-pointers and the ancestry."""
+        ops.token_logprobs(logits, self.tok.view(-1), top=self.W, V=self.model.config.vocab_size, out=self.btop)
+        ops.beam_step_(self.btop.top_ids, self.btop.top, self.scores, self.bdone, self.length, self.parent, self.tok,
+                       self.src, self.bp_parent, self.bp_token, self.n, self.all_done, stop_token)
+
+    @torch.no_grad()
+    def beam_start(self, idx, stop_token=None):
+        """Begin a search from the prompt ``idx`` (``prefill_shared``: encoded once, or not at all when it
+        is the cached one): the state is ``scores = [0, -inf, ...]`` over W copies of the prompt's one
+        distribution, and the first step of the rule picks its W most likely tokens."""
+        assert self.W, "beam_start needs Decoder(..., num_beams=W)"
+        logits = self.prefill_shared(idx).contiguous()
+        self.scores.fill_(float("-inf"))
+        self.scores[0] = 0.0
+        for t in (self.bdone, self.length, self.n, self.all_done):
+            t.zero_()
+        self._beam_select(logits, stop_token)
+
+    @torch.no_grad()
+    def run_beam(self, n: int, stop_token=None):
+        """n more steps of the search: feed the survivors' tokens (``_step_impl`` with
+        ``ops.decode_attention_beam``), then ``_beam_select``; on the GPU one captured graph per stop token,
+        replayed.  A finished hypothesis stays a row and is fed the stop token, so the step keeps
+        its shape.  With a stop token ``all_done`` is read every ``DONE_POLL`` steps and the loop ends
+        once every hypothesis has finished."""
+        assert self.W, "run_beam needs Decoder(..., num_beams=W)"
+        step = self._replay(lambda: self._beam_select(self._step_impl(), stop_token), Sampling(stop_token=stop_token))
+        ran = 0
+        while ran < n:
+            if stop_token is not None and ran and ran % self.DONE_POLL == 0 and bool(self.all_done.item()):
+                break
+            step()
+            ran += 1
+        if self.use_graph:
+            self.replays += ran
+
+    def beam_result(self, length_penalty: float = 0.0):
+        """The search's hypotheses -> (W 1-D tensors of new tokens, through the stop token if they
+        finished; their scores fp32 [W]), ordered by ``score / length ** length_penalty`` descending
+        (stably: the survivors are held by score), the length counting the new tokens.  The state is
+        read back once, and every hypothesis follows the back-pointers from its last token to its
+        first."""
+        W = self.W
+        n = int(self.n.item())
+        ints = torch.cat([self.bp_parent[:n].reshape(-1).long(), self.bp_token[:n].reshape(-1),
+                          self.length.long()]).tolist()
+        par, tokens, length = ints[:n * W], ints[n * W:2 * n * W], ints[2 * n * W:]
+        scores = self.scores.tolist()
+        order = sorted(range(W), key=lambda w: -(scores[w] / max(length[w], 1) ** float(length_penalty)))
+        outs = []
+        for w in order:
+            text, cur = [], w
+            for i in reversed(range(n)):
+                text.append(tokens[i * W + cur])
+                cur = par[i * W + cur]
+            outs.append(torch.tensor(text[::-1][:length[w]], dtype=torch.int64, device=self.device))
+        return outs, self.scores[torch.tensor(order, device=self.device)]
+
     def records(self, rows, first: int, stop: int) -> "ops.LogProbs":
         """A copy of what was recorded for positions first .. stop - 1 of ``rows`` (an index or a slice)."""
         assert self.lp is not None, "records needs Decoder(..., logprobs=N)"
@@ -1103,17 +1218,17 @@ def sample_next(logits: torch.Tensor, temperature: float = 1.0, top_k: int | Non
 
 
 def _mode(B, per_row=False, quantize=None, kv_quantize=None, slots=None, spec=(0, 3), penalize=False,
-          logprobs=None) -> dict:
+          logprobs=None, beams=None) -> dict:
     """The decoder a call needs, as ``Decoder``'s arguments (and ``Decoder.fits``'s): B rows, per_row
     or not, the two quantizations, ``slots``, the row-cache slots of a shared_prompt decoder
     (None: an unshared one), ``spec``, the (K, N) of ``_check`` (K > 0: a speculative one, which
     is per_row), ``penalize``: one with a count table, for a call with a penalty on, and ``logprobs``:
-    one with the log-probability buffers of that many alternatives (None: without).  ``_check`` has
-    refused what does not compose."""
+    one with the log-probability buffers of that many alternatives (None: without), ``beams``: a beam
+    decoder of that many hypotheses (its B; ``slots`` given).  ``_check`` has refused what does not compose."""
     K, N = spec
     return dict(batch_size=B, per_row=per_row or bool(K), quantize=quantize, kv_quantize=kv_quantize,
                 shared_prompt=slots is not None, max_new=slots, speculate=K or None, spec_ngram=N,
-                penalize=bool(penalize), logprobs=logprobs)
+                penalize=bool(penalize), logprobs=logprobs, num_beams=beams)
 
 
 def _build(model, mode, use_graph=None):
@@ -1256,6 +1371,78 @@ def generate_cached(model, idx: torch.Tensor, max_new_tokens: int, temperature: 
         dec.run(max_new_tokens - 1, smp)
         out = torch.cat([idx, dec.gen[:, T0:T0 + max_new_tokens]], dim=1)
         return _with_records(out, logprobs, lambda: dec.records(slice(None), T0, T0 + max_new_tokens))
+
+
+def _beam_plan(model, idx, max_new_tokens, num_beams, quantize=None, kv_quantize=None, speculate=None):
+    """``generate_beam``'s plan -> (prompt [T0], W, mode): the one prompt on the model's device, the
+    number of hypotheses and the mode of the decoder the call runs on, validated.  W = 1: the per_row
+    decoder of a greedy ``generate_batch`` call that records log-probabilities."""
+    _check(quantize, kv_quantize, speculate=speculate, beams=num_beams)
+    W, N = int(num_beams), int(max_new_tokens)
+    cfg = model.config
+    if idx.dim() > 1 and idx.shape[0] != 1:
+        raise ValueError(f"beam search takes one prompt per call, got {idx.shape[0]} rows")
+    prompt = idx.reshape(-1).to(model.lm_head.weight.device)
+    assert prompt.numel() >= 1, "the prompt needs at least one token"
+    if W > cfg.vocab_size:
+        raise ValueError(f"num_beams ({W}) exceeds the vocabulary ({cfg.vocab_size}): a step has no W distinct "
+                         "continuations of one hypothesis")
+    if prompt.numel() + max(N, 0) > cfg.block_size:
+        raise ValueError(f"beam search needs the KV-cache path: prompt ({prompt.numel()}) + new tokens ({N}) exceed "
+                         f"block_size {cfg.block_size}")
+    if W == 1:
+        return prompt, W, _mode(1, True, quantize, logprobs=0)
+    return prompt, W, _mode(W, False, quantize, slots=max(N, 1), beams=W)
+
+
+def beam_decoder(model, idx, max_new_tokens, num_beams, use_graph=None, quantize=None):
+    """The Decoder this ``generate_beam`` call would build, for a caller that keeps it across calls
+    (``decoder=``: weight shadows, the captured step and the cached prompt survive) and releases it."""
+    return _build(model, _beam_plan(model, idx, max_new_tokens, num_beams, quantize)[2], use_graph)
+
+
+@torch.no_grad()
+def generate_beam(model, idx, max_new_tokens: int, num_beams: int, stop_token: int | None = None,
+                  length_penalty: float = 0.0, quantize: str | None = None, use_graph: bool | None = None,
+                  decoder: "Decoder | None" = None, kv_quantize: str | None = None, speculate: int | None = None,
+                  **sampling_keywords):
+    """Beam search: the ``num_beams`` = W most likely continuations of one prompt that a search of width W
+    finds -> (W 1-D tensors, prompt + new tokens, through ``stop_token`` where a hypothesis drew it; their
+    scores fp32 [W]).  A score is the summed log-probability of the new tokens under the model's raw
+    logits, the quantity ``ops.token_logprobs`` and ``GPT.score`` define; no temperature, filter or penalty
+    applies.  The hypotheses are ordered by ``score / length ** length_penalty`` (the length counting the
+    new tokens; 0.0, the default: by the raw score), stably.
+
+    The W hypotheses are the rows of a shared-prompt decoder (``Decoder(..., shared_prompt=True,
+    num_beams=W, max_new=max_new_tokens)``): the prompt is encoded and cached once, and a step runs the
+    W fed tokens through the ordinary embedding, linears and lm_head, attends with
+    ``ops.decode_attention_beam`` (a hypothesis reads the keys of the rows it descends from where they
+    lie: nothing is copied when it changes parents), takes every row's W most likely ids
+    (``ops.token_logprobs``) and closes with ``ops.beam_step_`` (``ops.beam_select`` states the rule): one
+    captured graph, replayed per token, the whole state on the device.  A finished hypothesis stays
+    a frozen row that is fed the stop token; once all have finished the loop ends (looked for every
+    ``DONE_POLL`` steps), and the result is read back once and unwound through the back-pointers.
+
+    ``num_beams=1`` is greedy decoding the ordinary way (``generate_batch`` with ``top_k=1``), scored by
+    its recorded log-probabilities.  ``quantize="int8"`` composes.  ValueError: W outside 1 .. 8 or
+    above the vocabulary size, more than one prompt, ``kv_quantize``, ``speculate``, any sampling keyword
+    (``temperature``, ``top_k``, ...: a search draws nothing) and prompt + new tokens past block_size.  On the GPU the device kernels need bf16 and head_dim 64 (as ``shared_prompt``
+    does); elsewhere the same decoder runs on the torch forms of the ops."""
+    if sampling_keywords:
+        raise ValueError(f"beam search does not sample: it takes no {', '.join(sorted(sampling_keywords))}")
+    stop_token = None if stop_token is None or stop_token < 0 else int(stop_token)
+    prompt, W, mode = _beam_plan(model, idx, max_new_tokens, num_beams, quantize, kv_quantize, speculate)
+    if max_new_tokens <= 0:
+        return [prompt], torch.zeros(1, device=prompt.device)
+    if W == 1:
+        outs, recs = generate_batch(model, [prompt], max_new_tokens, 1.0, 1, stop_token, use_graph=use_graph,
+                                    decoder=decoder, quantize=quantize, logprobs=0)
+        return outs, recs[0].token.sum().view(1)
+    with _borrow(model, mode, decoder, use_graph) as dec:
+        dec.beam_start(prompt, stop_token)
+        dec.run_beam(max_new_tokens - 1, stop_token)
+        news, scores = dec.beam_result(length_penalty)
+        return [torch.cat([prompt, new]) for new in news], scores
 
 
 def _with_records(out, logprobs, records):

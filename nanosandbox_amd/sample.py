@@ -45,6 +45,12 @@ perplexity, and with N > 0 every new token with its N most likely alternatives
 (``Decoder(logprobs=N)``: recorded by one more launch inside the decode step); every mode but
 ``--speculate``.  ``--score=True`` with ``--prompts_file`` generates nothing: every line is scored
 (``GPT.score``) and printed with its summed log-probability, token count and perplexity.
+``--num_beams=W`` (1 .. 8) searches instead of sampling: the W most likely continuations a beam search of
+that width finds (``GPT.generate_beam``: the hypotheses are the rows of a shared-prompt decoder whose
+captured step picks the survivors on the device), printed best first with their summed log-probabilities
+and ordered by ``score / length ** length_penalty`` (``--length_penalty=0.0``: the raw score).  With
+``--prompts_file`` one prompt after the other on one reused decoder.  It composes with ``--quantize`` and
+``--stop_token`` and refuses ``--kv_cache=False``, ``--kv_quantize`` and ``--speculate``; the sampling keys do not apply.
 """
 
 from __future__ import annotations
@@ -91,6 +97,8 @@ SAMPLE_DEFAULTS = dict(
     spec_ngram=3,  # speculate: the longest n-gram looked up in the row's own text for a draft
     logprobs=-1,  # N >= 0: print each sample's log-probability and perplexity, N > 0 (<= 8): and N alternatives per token; -1: off
     score=False,  # with prompts_file: score every line (GPT.score) instead of generating
+    num_beams=0,  # W > 0: beam search of width W (1 .. 8) instead of sampling (GPT.generate_beam); 0: off
+    length_penalty=0.0,  # num_beams: hypotheses are ordered by score / length ** length_penalty; 0.0: the raw score
 )
 
 
@@ -138,6 +146,35 @@ def _score_file(model, c, encode, device):
         print(t)
         print(f"logprob {outs[-1][0]:.4f} over {outs[-1][1]} tokens, perplexity {outs[-1][2]:.4f}")
         print("---------------")
+    return outs
+
+
+def _beam_search(model, c, encode, decode, start, device):
+    """num_beams: every prompt (the lines of prompts_file, or start) through ``GPT.generate_beam`` on one decoder."""
+    from .runtime.decode import beam_decoder
+    stop = c["stop_token"] if c["stop_token"] >= 0 else None
+    texts = [start]
+    if c["prompts_file"]:
+        with open(c["prompts_file"], "r", encoding="utf-8") as f:
+            texts = [ln.rstrip("\n") for ln in f if ln.strip()]
+    prompts = [torch.tensor(encode(t), dtype=torch.long, device=device) for t in texts]
+    mode = dict(num_beams=c["num_beams"], quantize=c["quantize"] or None)
+    dec, outs = beam_decoder(model, max(prompts, key=len), c["max_new_tokens"], **mode), []
+    try:
+        for p in prompts:
+            ys, scores = model.generate_beam(p, c["max_new_tokens"], stop_token=stop, length_penalty=c["length_penalty"],
+                                             decoder=dec, kv_quantize=c["kv_quantize"] or None,
+                                             speculate=c["speculate"] or None, **mode)
+            for y, s in zip(ys, scores.tolist()):
+                new = y[p.numel():].tolist()
+                if stop is not None and stop in new:
+                    new = new[:new.index(stop)]
+                outs.append(decode(p.tolist() + new))
+                print(outs[-1])
+                print(f"logprob {s:.4f} over {y.numel() - p.numel()} tokens")
+                print("---------------")
+    finally:
+        dec.release()
     return outs
 
 
@@ -304,6 +341,11 @@ def main(argv=None):
         if _penalties(c) != dict(repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0):
             raise ValueError("--speculate cannot be combined with --repetition_penalty / --presence_penalty / "
                              "--frequency_penalty: a verified position's counts would have to include its drafts")
+    if c["num_beams"]:
+        from .runtime.decode import _check
+        _check(c["quantize"] or None, c["kv_quantize"] or None, speculate=c["speculate"] or None, beams=c["num_beams"])
+        if not c["kv_cache"]:
+            raise ValueError("--num_beams searches on the KV-cache path: it cannot be combined with --kv_cache=False")
     spec = dict(speculate=c["speculate"], spec_ngram=c["spec_ngram"]) if c["speculate"] else {}
     quantize = c["quantize"] or None
     kv_quantize = c["kv_quantize"] or None
@@ -331,6 +373,9 @@ def main(argv=None):
     if c["score"]:
         with torch.no_grad():
             return _score_file(model, c, encode, device)
+    if c["num_beams"]:
+        with torch.no_grad():
+            return _beam_search(model, c, encode, decode, start, device)
     if c["serve_batch"]:
         with torch.no_grad():
             return _serve_queue(model, c, encode, decode, start, device)

@@ -132,6 +132,21 @@ def run_rows(model, idx, new, lengths=None, quantize=None, kv_quantize=None, sha
     return dt, ttft
 
 
+def run_beam(model, prompt, new, W):
+    """A beam search of width W from ``prompt`` [T0] on captured graphs -> seconds of ``new`` timed steps (the
+    first step, the search's start and the capture lie outside)."""
+    dec = Decoder(model, W, use_graph=True, shared_prompt=True, max_new=new + 2, num_beams=W)
+    dec.beam_start(prompt)
+    dec.run_beam(1)  # capture outside the timed loop
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    dec.run_beam(new)
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    dec.release()
+    return dt
+
+
 def run_spec(model, idx, new, K, ngram, table=None, quantize=None):
     """The graph mode on a speculative decoder.  table: None (n-gram drafts), "right" or "wrong".
     Returns (seconds of the timed steps, the decoder's spec_stats for them)."""
@@ -321,6 +336,9 @@ def main():
                                                     "(graph_pen, rows_pen) on a Decoder(penalize=True)")
     ap.add_argument("--logprobs", default="", help="N[,N ...]: add twins of the graph and rows modes that record "
                                                    "log-probabilities and N alternatives (graph_lpN, rows_lpN)")
+    ap.add_argument("--beams", default="", help="W[,W ...]: only beam search of these widths, interleaved with "
+                    "shared-prompt sampling at batch W (the same linears; the select and the gather differ): "
+                    "medians of --repeat runs")
     ap.add_argument("--top_k", type=int, default=200, help="0: no top-k")
     ap.add_argument("--top_p", type=float, default=1.0, help="nucleus mass; 1.0: off")
     ap.add_argument("--min_p", type=float, default=0.0, help="floor relative to the most likely token; 0.0: off")
@@ -375,7 +393,19 @@ def main():
         torch.manual_seed(0)
         model = GPT(GPTConfig(n_layer=L, n_head=H, n_embd=C, dropout=0.0, bias=True)).eval().cuda()
         model.set_compute_dtype(torch.bfloat16)
-        for B in [int(b) for b in a.batches.split(",")]:
+        for W in [int(w) for w in a.beams.split(",") if w]:
+            idx = torch.randint(0, 50257, (W, a.prompt), device="cuda")
+            times = {"rows_shared": [], "beam": []}
+            with torch.no_grad():
+                run_rows(model, idx, 4, shared=True), run_beam(model, idx[0], 4, W)  # warm-up (tuner, allocator)
+                for _ in range(max(a.repeat, 1)):
+                    times["rows_shared"].append(run_rows(model, idx, a.new, shared=True)[0])
+                    times["beam"].append(run_beam(model, idx[0], a.new, W))
+            for mode, ts in times.items():
+                print(json.dumps({"model": name, "batch": W, "mode": mode, "prompt": a.prompt, "new_tokens": a.new,
+                                  "ms_per_step": round(sorted(ts)[len(ts) // 2] / a.new * 1e3, 4), "repeats": len(ts),
+                                  "calibration_tflops": cal.get("tflops") if cal else None}), flush=True)
+        for B in [] if a.beams else [int(b) for b in a.batches.split(",")]:
             idx = torch.randint(0, 50257, (B, a.prompt), device="cuda")
             with torch.no_grad():
                 for mode in modes if a.queue else []:
