@@ -25,7 +25,12 @@ constexpr int ATTN_MAX_WEIGHTS = 16384;   // PRO_ATTN: heads * n_split chunk wei
 constexpr int GEMV_MAX_ROWS = 8;          // vector GEMV: 8 x rows partial sums per lane
 constexpr int SKINNY_GROUP_ROWS = 16;     // one 16-row MFMA group: the skinny LayerNorm and int8 kernels
 constexpr int SKINNY_MAX_ROWS = 64;       // bf16 skinny GEMM: 4 groups
-constexpr int ROW_K_BF16 = 8, ROW_K_Q8 = 16;         // K granule of the vector kernels: k per 16-byte weight piece
+constexpr int WIDE_MAX_ROWS = 64;         // wide split-K GEMM (decode_wide.hip): 2 or 4 groups
+constexpr int WIDE_TILE_N = 64;           // its workgroup's output columns: one wave per 16
+constexpr int WIDE_CHUNK = 256;           // k per LDS chunk of X (8 units of 32), double-buffered
+constexpr int WIDE_TARGET_WGS = 128;      // its split-K rule: tiles x KS up to this many workgroups ...
+constexpr int WIDE_MIN_UNITS = 32;        // ... with at least this many 32-wide K units (4 chunks) per workgroup
+constexpr int ROW_K_BF16 = 8, ROW_K_Q8 = 16;        // K granule of the vector kernels: k per 16-byte weight piece
 constexpr int SKINNY_K_BF16 = 32, SKINNY_K_Q8 = 64;  // K granule of the skinny kernels: k per lane group's unit
 
 // int8 -> fp32 (two's-complement bytes, exact): the int8 weights of decode_q8.hip and the

@@ -59,8 +59,9 @@ def _run(cmd):
 # (MI355X_MICROARCH.md 'price of one filler'; A/B: scripts/attn_ab.py against a variant
 # library built with file_flags={}).
 FILE_FLAGS = {"flash_attn.hip": ["-fno-slp-vectorize"], "flash_attn_f16.hip": ["-fno-slp-vectorize"],
-              # no packed fp32 arithmetic at all in the beam kernels
-              "decode_beam.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+              # no packed fp32 arithmetic at all in the beam kernels and the wide decode GEMM
+              "decode_beam.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+              "decode_wide.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def kernel_flags(src, defines=(), file_flags=None, include_dir=os.path.join(CSRC, "kernels")):

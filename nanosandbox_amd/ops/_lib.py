@@ -105,6 +105,11 @@ _SIGNATURES = {
     "nsa_pos_advance": [c_void_p, c_void_p, c_int, c_void_p],
     "nsa_gemv":[c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p],
     "nsa_skinny_gemm": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p],
+    # 17 .. 64 rows (csrc/kernels/decode_wide.hip): nsa_skinny_gemm's arguments, then ksplit, ws, ws_bytes
+    "nsa_wide_gemm": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                      c_int64, c_void_p],
+    "nsa_wide_gemm_ws_bytes": [c_int, c_int, c_int, c_int],
+    "nsa_wide_gemm_ksplit": [c_int, c_int, c_int],
     "nsa_skinny_ln_gemm": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p,
                            c_int, c_int, c_int, c_int, c_int, c_void_p],
     "nsa_gemv_emb_ln": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
@@ -201,7 +206,7 @@ _SIGNATURES = {
     "nsa_probe_mark": [c_void_p, c_void_p],
 }
 # entry points whose return value is not a hipError_t
-_RESTYPES = {"nsa_keysort_ws_bytes": c_int64, "nsa_ln_nt_min_bytes": c_int64}
+_RESTYPES = {"nsa_keysort_ws_bytes": c_int64, "nsa_ln_nt_min_bytes": c_int64, "nsa_wide_gemm_ws_bytes": c_int64}
 
 
 class KernelLibraryMissing(RuntimeError):

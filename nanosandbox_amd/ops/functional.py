@@ -1579,6 +1579,36 @@ SKINNY_MAX_ROWS = int(os.environ.get("NSA_SKINNY_MAX_ROWS", "16"))
 # 0.532 / 3.18 fused; batch 16 0.597 / 3.78 unfused vs 0.667 / 4.10 fused (every workgroup
 # normalises all rows: the per-workgroup prologue outgrows the saved launch)
 SKINNY_LN_MAX_ROWS = int(os.environ.get("NSA_SKINNY_LN_MAX_ROWS", "8"))
+# decode batches of SKINNY_MAX_ROWS + 1 .. WIDE_MAX_ROWS rows: the wide-tile split-K MFMA weight
+# stream (nsa_wide_gemm, csrc/kernels/decode_wide.hip: 64-column workgroups share one LDS image of X);
+# above it ``linear``.  HIP-graph decode, ms/token (GPT-2 124M / 1.5B), ``linear`` vs this kernel, medians
+# of three: batch 24 1.722 / 12.17 vs 0.857 / 5.24; 32 1.719 / 12.21 vs 0.872 / 5.39; 48 1.737 / 12.31 vs
+# 1.027 / 6.35; 64 1.749 / 12.40 vs 1.100 / 6.78 (repeats within 0.4 %).  It won every point, so the cap
+# is 64; per call it loses the 64-row lm_head to ``linear`` (53 vs 45 us at 1.5B).  16 turns it off.
+WIDE_MAX_ROWS = int(os.environ.get("NSA_WIDE_MAX_ROWS", "64"))
+WIDE_CHUNK = 256                   # WIDE_CHUNK (decode_rows.h): k per LDS chunk of the wide kernel
+_WIDE_WS_MIN = 3 << 20             # first size of its workspace: above every split the rule picks (128 x 16 KB)
+_WIDE_WS = {}                      # device index -> the workspace (uint8, counters zero)
+_WIDE_WS_RETIRED = []              # outgrown workspaces: a captured graph may still hold their address
+
+
+def _wide_workspace(device, rows, N, K):
+    """(pointer, bytes) of the device's ``nsa_wide_gemm`` workspace, large enough for this shape under
+    the rule's split; (None, 0) where the launch needs none.  One buffer per device, zero when
+    allocated (the kernel leaves its counters zero), shared by successive launches; it is never
+    grown inside a graph capture (a step's warm-up outside the capture sizes it)."""
+    need = _lib.call_ret("nsa_wide_gemm_ws_bytes", rows, N, K, 0)
+    if need == 0:
+        return None, 0
+    ws = _WIDE_WS.get(device.index)
+    if ws is None or ws.numel() < need:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("nsa_wide_gemm's workspace must be sized outside a graph capture: run the step "
+                               "eagerly once before capturing it")
+        if ws is not None:
+            _WIDE_WS_RETIRED.append(ws)
+        ws = _WIDE_WS[device.index] = torch.zeros(max(need, _WIDE_WS_MIN), device=device, dtype=torch.uint8)
+    return ws.data_ptr(), ws.numel()
 
 
 def decode_linear(x, w, b=None, gelu: bool = False, out_f32: bool = False):
@@ -1589,8 +1619,10 @@ def decode_linear(x, w, b=None, gelu: bool = False, out_f32: bool = False):
     library GEMM + bias copy.  The vector GEMV's VALU grows with the rows (batch 4: 1.52 ms
     per token at 124M in round 2), so the default cap is 1 row (``NSA_GEMV_MAX_ROWS``) and
     batches of 2 .. ``NSA_SKINNY_MAX_ROWS`` (16) rows run on ``nsa_skinny_gemm`` (MFMA
-    weight stream, bias / GELU epilogue) when N % 16 == 0 and K % 32 == 0; larger batches go
-    to ``linear`` (our small-tile / NT kernels: no library GEMM on this path).
+    weight stream, bias / GELU epilogue) when N % 16 == 0 and K % 32 == 0; batches above that up
+    to ``NSA_WIDE_MAX_ROWS`` (64) rows run on ``nsa_wide_gemm`` (64-column workgroups, split-K; bf16
+    weights only) under the same conditions; larger batches go to ``linear`` (our small-tile / NT
+    kernels: no library GEMM on this path).
 
     ``w`` may be a ``QuantWeight``: the same rules pick the ``_q8`` form of the same kernel
     (K % 16 == 0 at one row, K % 64 == 0 and any N on the skinny kernel); whatever those do
@@ -1603,15 +1635,19 @@ def decode_linear(x, w, b=None, gelu: bool = False, out_f32: bool = False):
         return y.view(1, 1, N)
     K = x.shape[-1]
     rows = x.numel() // K
-    kind = None
+    kind, extra = None, ()
     if x.is_cuda and x.dtype == BF16 and rows <= GEMV_MAX_ROWS and K % _ROW_K[q8] == 0:
         kind = "gemv"
     elif (x.is_cuda and x.dtype == BF16 and 2 <= rows <= SKINNY_MAX_ROWS and K % _SKINNY_K[q8] == 0
             and (q8 or N % 16 == 0) and not (gelu and out_f32)):
         kind = "skinny_gemm"
+    elif (x.is_cuda and x.dtype == BF16 and not q8 and SKINNY_MAX_ROWS < rows <= WIDE_MAX_ROWS and N % 16 == 0
+            and K % _SKINNY_K[False] == 0 and not (gelu and out_f32)):
+        kind = "wide_gemm"
+        extra = (0, *_wide_workspace(x.device, rows, N, K))  # ksplit 0: the kernel's own rule
     if kind:
         x2 = x.reshape(rows, K).contiguous()
-        y = _stream_call(kind, (_lib.ptr(x2),), w, b, (rows, N), x.device, (rows, N, K), gelu, out_f32)
+        y = _stream_call(kind, (_lib.ptr(x2),), w, b, (rows, N), x.device, (rows, N, K), gelu, out_f32, *extra)
         return y.view(*x.shape[:-1], N)
     if q8:
         w = dequantize(w).to(x.dtype)

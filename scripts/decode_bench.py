@@ -57,6 +57,9 @@ penalty (the penalised sampler and its count table beside the plain step of the 
 ``--logprobs N[,N ...]`` adds ``graph_lpN`` / ``rows_lpN`` right after ``graph`` / ``rows``: the same settings on
 a ``Decoder(logprobs=N)``, whose step records every drawn token's log-probability and N alternatives
 (one more launch per step beside the plain step of the same run).
+``--wide_ab`` adds ``graph_narrow`` / ``rows_narrow`` right after ``graph`` / ``rows``: the same run with
+``ops.functional.WIDE_MAX_ROWS`` lowered to ``SKINNY_MAX_ROWS``, so batches of 17 .. 64 rows take ``linear``
+instead of ``nsa_wide_gemm``: the path before the wide kernel, launch for launch.
 """
 
 import argparse
@@ -69,6 +72,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from nanosandbox_amd.models import GPT, GPTConfig  # noqa: E402
+from nanosandbox_amd.ops import functional  # noqa: E402
 from nanosandbox_amd.runtime.decode import Decoder  # noqa: E402
 
 SMP = dict(top_k=200, top_p=None, min_p=None)  # the sampling settings of every mode (--top_k / --top_p / --min_p)
@@ -336,6 +340,9 @@ def main():
                                                     "(graph_pen, rows_pen) on a Decoder(penalize=True)")
     ap.add_argument("--logprobs", default="", help="N[,N ...]: add twins of the graph and rows modes that record "
                                                    "log-probabilities and N alternatives (graph_lpN, rows_lpN)")
+    ap.add_argument("--wide_ab", action="store_true",
+                    help="add twins of the graph and rows modes with the wide decode GEMM off (graph_narrow, "
+                         "rows_narrow)")
     ap.add_argument("--beams", default="", help="W[,W ...]: only beam search of these widths, interleaved with "
                     "shared-prompt sampling at batch W (the same linears; the select and the gather differ): "
                     "medians of --repeat runs")
@@ -371,6 +378,8 @@ def main():
     if a.logprobs:  # the recording twins right after their mode
         twins = [f"lp{int(n)}" for n in a.logprobs.split(",")]
         modes = [t for m in modes for t in ([m] + [f"{m}_{x}" for x in twins] if m in ("graph", "rows") else [m])]
+    if a.wide_ab:  # each narrow twin right after its mode
+        modes = [t for m in modes for t in ([m, f"{m}_narrow"] if m in ("graph", "rows") else [m])]
     if a.shared_prefix:
         modes = ["prefix_rows", "prefix_shared"]
     block_size = GPTConfig().block_size
@@ -425,6 +434,9 @@ def main():
                     ttft = {}
                     spec = next((int(x[4:]) for x in sfx if x.startswith("spec")), 0)
                     lp = next((int(x[2:]) for x in sfx if x.startswith("lp")), None)
+                    wide_cap = functional.WIDE_MAX_ROWS
+                    if "narrow" in sfx:
+                        functional.WIDE_MAX_ROWS = functional.SKINNY_MAX_ROWS
                     if a.memory:
                         torch.cuda.synchronize()
                         torch.cuda.reset_peak_memory_stats()
@@ -459,6 +471,7 @@ def main():
                         n = a.new
                         run_cached(model, idx, 4, base == "graph", qz, kvq, "pen" in sfx, lp)
                         dt = run_cached(model, idx, n, base == "graph", qz, kvq, "pen" in sfx, lp)
+                    functional.WIDE_MAX_ROWS = wide_cap
                     mem = ({"decoder_peak_mb": round((torch.cuda.max_memory_allocated() - mem0) / 2 ** 20, 1)}
                            if a.memory else {})
                     print(json.dumps({"model": name, "batch": B, "mode": mode, "prompt": a.prompt, "new_tokens": n,
