@@ -32,6 +32,7 @@ constexpr int WIDE_TARGET_WGS = 128;      // its split-K rule: tiles x KS up to 
 constexpr int WIDE_MIN_UNITS = 32;        // ... with at least this many 32-wide K units (4 chunks) per workgroup
 constexpr int ROW_K_BF16 = 8, ROW_K_Q8 = 16;        // K granule of the vector kernels: k per 16-byte weight piece
 constexpr int SKINNY_K_BF16 = 32, SKINNY_K_Q8 = 64;  // K granule of the skinny kernels: k per lane group's unit
+constexpr int MX4_K = 32;  // K granule of every MXFP4 kernel (decode_mx4.hip): one block of 32 under one scale byte
 
 // int8 -> fp32 (two's-complement bytes, exact): the int8 weights of decode_q8.hip and the
 // int8 KV-cache rows of decode.hip

@@ -451,7 +451,7 @@ class GPT(nn.Module):
         """``generate`` with per-layer KV caches: the prompt is encoded once and every
         new token runs one position through the model (a replayed HIP graph on the GPU;
         ``runtime/decode.py``).  Same sampling; falls back to ``generate`` when prompt +
-        new tokens exceed block_size.  ``quantize="int8"``: int8 weight-only decoding;
+        new tokens exceed block_size.  ``quantize="int8"`` / ``"mxfp4"``: weight-only decoding;
         ``kv_quantize="int8"``: int8 KV caches (either: no fallback, ValueError past
         block_size).  ``shared_prompt=True``: the rows of ``idx`` are one prompt, cached once
         for the whole batch (equal rows or ValueError; no fallback either).  ``speculate=K``:

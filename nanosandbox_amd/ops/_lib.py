@@ -129,6 +129,19 @@ _SIGNATURES = {
                          c_void_p],
     "nsa_gemv_ln_q8": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                        c_int, c_int, c_float, c_int, c_int, c_void_p, c_void_p],
+    # MXFP4-weight forms (csrc/kernels/decode_mx4.hip): the _q8 forms' arguments, Wq the nibble matrix
+    # [N, K / 2] and scale the E8M0 byte matrix [N, K / 32]
+    "nsa_gemv_mx4": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p],
+    "nsa_skinny_gemm_mx4": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                            c_void_p],
+    "nsa_skinny_ln_gemm_mx4": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p,
+                               c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p],
+    "nsa_gemv_emb_ln_mx4": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                            c_void_p, c_void_p, c_int, c_int, c_float, c_int, c_int, c_void_p],
+    "nsa_gemv_attn_mx4": [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                          c_void_p],
+    "nsa_gemv_ln_mx4": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                        c_int, c_int, c_float, c_int, c_int, c_void_p, c_void_p],
     # int8 KV caches (csrc/kernels/decode.hip): (q, scale) per cache where the bf16 entry point takes kc / vc
     "nsa_kv_append_kv8": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                           c_int, c_int, c_void_p],

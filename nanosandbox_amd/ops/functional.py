@@ -1525,8 +1525,79 @@ def quantize_rows_int8(w) -> QuantWeight:
     return QuantWeight(q, scale.contiguous())
 
 
-def dequantize(qw: QuantWeight) -> torch.Tensor:
-    """The fp32 weight a ``QuantWeight`` stands for: q * scale[:, None]."""
+class MxWeight(NamedTuple):
+    """An OCP MXFP4 weight-only form of a linear's weight [N, K], K % 32 == 0: ``q`` uint8 [N, K / 2], two
+    E2M1 codes per byte (element k of a row in byte k // 2, even k in the low nibble; code bits: sign = bit 3,
+    exponent = bits 2-1, mantissa = bit 0: the magnitudes 0, 0.5, 1, 1.5, 2, 3, 4, 6), and ``scale`` uint8
+    [N, K / 32], one E8M0 byte per block of 32 along K (byte e stands for 2^(e - 127)).  It stands for
+    ``dequantize(mw)`` and is taken wherever a ``QuantWeight`` is."""
+    q: torch.Tensor
+    scale: torch.Tensor
+
+    @property
+    def shape(self):
+        return torch.Size((self.q.shape[0], 2 * self.q.shape[1]))
+
+
+MX_BLOCK = 32
+_MX_MAGNITUDES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)   # of the codes 0 .. 7; codes 8 .. 15 are their negatives
+_MX_MIDPOINTS = (0.25, 0.75, 1.25, 1.75, 2.5, 3.5, 5.0)      # between neighbours: a tie goes to the even code
+MX_SCALE_RULE = "floor"
+
+
+def quantize_mxfp4(w, rule: str | None = None) -> MxWeight:
+    """Round-to-nearest MXFP4 of ``w`` [N, K] (K % 32 == 0), in fp32, plain torch (CPU or GPU); runs once per
+    decoder.  Per block of 32 along K the shared exponent comes from the block's absmax, by ``rule``:
+
+    * ``"floor"`` (the default, ``MX_SCALE_RULE``): the OCP rule s = floor(log2 amax) - 2; elements above
+      6 * 2^s (a block whose amax is in (6, 8) 2^s) saturate at 6.
+    * ``"ceil"``: s = ceil(log2(amax / 6)), the smallest power of two under which no element exceeds 6:
+      nothing clips, at a step twice as coarse for the blocks the OCP rule would clip.
+
+    Measured relative Frobenius error ||dq - w|| / ||w||, seeded CPU runs: a 256 x 768 N(0, 0.02^2) matrix,
+    floor 0.1143 / ceil 0.1184 (per-row int8: 0.0077); the logits of the CPU tests' tiny GPT (2 layers, C = 64,
+    V = 97; tests/test_mx4_refs.py) against the unquantized model, floor 0.1573 / ceil 0.1658 (int8: 0.0084).
+    The OCP rule wins both (clipping one element of a block costs less than halving the resolution of the
+    other 31), so it is the one kept.
+
+    The byte is clamped to 2 .. 252, so every dequantized value (0.5 * 2^-125 at the least, 6 * 2^125 at the
+    most) is a normal bf16 number whatever the input; an all-zero block gets byte 127 and zero codes.  Elements
+    are rounded to the nearest representable magnitude, ties to the even code, saturating at 6."""
+    rule = rule or MX_SCALE_RULE
+    if rule not in ("ceil", "floor"):
+        raise ValueError(f"rule must be 'ceil' or 'floor', got {rule!r}")
+    wf = w.detach().float()
+    N, K = wf.shape
+    if K % MX_BLOCK or K < MX_BLOCK:
+        raise ValueError(f"MXFP4 blocks are {MX_BLOCK} wide along K: K = {K} is not a multiple")
+    blk = wf.view(N, K // MX_BLOCK, MX_BLOCK)
+    amax = blk.abs().amax(dim=2)
+    # frexp: amax = m 2^e with m in [0.5, 1), so floor(log2 amax) = e - 1, exactly (no log2 rounding)
+    m, e = torch.frexp(amax)
+    if rule == "floor":
+        s = e - 1 - 2
+    else:  # ceil(log2(amax / 6)): amax / 6 = (m / 0.75) 2^(e - 3), m / 0.75 in [2/3, 4/3)
+        s = e - 3 + (m > 0.75).to(e.dtype)
+    byte = torch.where(amax > 0, (s + 127).clamp(2, 252), torch.full_like(s, 127))
+    a = (blk.abs() * torch.exp2((127 - byte).float())[..., None])  # |w| / 2^s: a power-of-two scaling, exact
+    mid = torch.tensor(_MX_MIDPOINTS, device=wf.device)
+    code = (a[..., None] > mid).sum(-1)                    # above a midpoint: the next code ...
+    # ... and onto it from below at a tie whose upper neighbour is the even code (0.75, 1.75, 3.5 -> 2, 4, 6)
+    code = code + ((a[..., None] == mid[1::2]).any(-1)).to(code.dtype)
+    code = (code + 8 * ((blk < 0) & (code > 0)).to(code.dtype)).view(N, K).to(torch.uint8)  # zero is code 0, never -0
+    q = (code[:, 0::2] | (code[:, 1::2] << 4)).contiguous()
+    return MxWeight(q, byte.to(torch.uint8).contiguous())
+
+
+def dequantize(qw) -> torch.Tensor:
+    """The fp32 weight a ``QuantWeight`` (q * scale[:, None]) or an ``MxWeight`` (value[code] * 2^(byte - 127) of
+    the element's block) stands for."""
+    if isinstance(qw, MxWeight):
+        N, K = qw.shape
+        code = torch.stack((qw.q & 15, qw.q >> 4), dim=2).view(N, K).long()
+        mag = torch.tensor(_MX_MAGNITUDES + tuple(-v for v in _MX_MAGNITUDES), device=qw.q.device)
+        scale = torch.exp2(qw.scale.float() - 127)
+        return (mag[code].view(N, K // MX_BLOCK, MX_BLOCK) * scale[..., None]).view(N, K)
     return qw.q.float() * qw.scale[:, None]
 
 
@@ -1534,7 +1605,14 @@ def _stream_weight(w):
     """(entry-point suffix, the tensors passed where the bf16 entry point takes W)."""
     if isinstance(w, QuantWeight):
         return "_q8", (w.q, w.scale)
+    if isinstance(w, MxWeight):
+        return "_mx4", (w.q, w.scale)
     return "", (compute_weight(w, BF16),)
+
+
+def _weight_form(w):
+    """The key of ``_ROW_K`` / ``_SKINNY_K``: which weight stream ``w`` is."""
+    return "q8" if isinstance(w, QuantWeight) else "mx4" if isinstance(w, MxWeight) else "bf16"
 
 
 def _stream_call(kind, lead, w, b, y_shape, device, dims, gelu=False, out_f32=False, *extra):
@@ -1561,8 +1639,8 @@ def _ln_operands(res, branch, ln_w, ln_b, shape):
 
 
 # What the kernels' entry points accept (csrc/kernels/decode_rows.h; they refuse anything else)
-_ROW_K = {False: 8, True: 16}      # ROW_K_BF16, ROW_K_Q8: K granule of the GEMV kernels, by int8 weights
-_SKINNY_K = {False: 32, True: 64}  # SKINNY_K_BF16, SKINNY_K_Q8: K granule of the skinny kernels
+_ROW_K = {"bf16": 8, "q8": 16, "mx4": 32}      # ROW_K_BF16, ROW_K_Q8, MX4_K: K granule of the GEMV kernels, by weights
+_SKINNY_K = {"bf16": 32, "q8": 64, "mx4": 32}  # SKINNY_K_BF16, SKINNY_K_Q8, MX4_K: K granule of the skinny kernels
 _ROW_MAX_K = 8192                  # ROW_MAX_K: widest row of the single-row prologue kernels
 _SKINNY_LN_MAX_K = 1920            # SKINNY_LN_MAX_K: widest row of the skinny LayerNorm kernels
 
@@ -1627,8 +1705,11 @@ def decode_linear(x, w, b=None, gelu: bool = False, out_f32: bool = False):
     ``w`` may be a ``QuantWeight``: the same rules pick the ``_q8`` form of the same kernel
     (K % 16 == 0 at one row, K % 64 == 0 and any N on the skinny kernel); whatever those do
     not cover (CPU, fp32, other K, more rows) runs the rest of this function on
-    ``dequantize(w)`` in x's dtype: the reference semantics, and a slow path on the GPU."""
-    q8 = isinstance(w, QuantWeight)
+    ``dequantize(w)`` in x's dtype: the reference semantics, and a slow path on the GPU.
+    An ``MxWeight`` likewise picks the ``_mx4`` forms (K % 32 == 0, any N; one row up to K = 8192 on
+    ``nsa_gemv_mx4``, 2 .. 16 rows on ``nsa_skinny_gemm_mx4``), with the same fallback."""
+    form = _weight_form(w)
+    q8 = form != "bf16"  # a quantized stream: any N on the skinny kernel, no wide kernel, the dequantize fallback
     N = w.shape[0]
     if isinstance(x, AttnPartials):  # one row; the attention combine runs in the GEMV prologue
         y = _stream_call("gemv_attn", (_lib.ptr(x.ws), x.n_split), w, b, (N,), x.ws.device, (N, x.C), gelu, out_f32)
@@ -1636,13 +1717,16 @@ def decode_linear(x, w, b=None, gelu: bool = False, out_f32: bool = False):
     K = x.shape[-1]
     rows = x.numel() // K
     kind, extra = None, ()
-    if x.is_cuda and x.dtype == BF16 and rows <= GEMV_MAX_ROWS and K % _ROW_K[q8] == 0:
+    # nsa_gemv_mx4 is the single-row kernel alone (K <= _ROW_MAX_K), whatever NSA_GEMV_MAX_ROWS
+    gemv_rows = min(GEMV_MAX_ROWS, 1) if form == "mx4" else GEMV_MAX_ROWS
+    if (x.is_cuda and x.dtype == BF16 and rows <= gemv_rows and K % _ROW_K[form] == 0
+            and (form != "mx4" or K <= _ROW_MAX_K)):
         kind = "gemv"
-    elif (x.is_cuda and x.dtype == BF16 and 2 <= rows <= SKINNY_MAX_ROWS and K % _SKINNY_K[q8] == 0
+    elif (x.is_cuda and x.dtype == BF16 and 2 <= rows <= SKINNY_MAX_ROWS and K % _SKINNY_K[form] == 0
             and (q8 or N % 16 == 0) and not (gelu and out_f32)):
         kind = "skinny_gemm"
     elif (x.is_cuda and x.dtype == BF16 and not q8 and SKINNY_MAX_ROWS < rows <= WIDE_MAX_ROWS and N % 16 == 0
-            and K % _SKINNY_K[False] == 0 and not (gelu and out_f32)):
+            and K % _SKINNY_K["bf16"] == 0 and not (gelu and out_f32)):
         kind = "wide_gemm"
         extra = (0, *_wide_workspace(x.device, rows, N, K))  # ksplit 0: the kernel's own rule
     if kind:
@@ -1666,17 +1750,18 @@ def decode_linear_ln(res, branch, ln_w, ln_b, w, b=None, gelu: bool = False, out
     + ``decode_linear`` (``out_dtype``: the LayerNorm output dtype there).  ``pos_inc``: an
     int64 device tensor incremented by one after the row (inside the kernel on the fused
     path: the decode step's position update without its own launch).  Inference only."""
-    q8 = isinstance(w, QuantWeight)  # the _q8 form of the same kernel; else decode_linear's fallback
+    form = _weight_form(w)  # the _q8 / _mx4 form of the same kernel; else decode_linear's fallback
+    q8 = form != "bf16"
     C = res.shape[-1]
     rows = res.numel() // C
     N = w.shape[0]
     fused = res.is_cuda and res.dtype == F32 and (branch is None or branch.dtype == BF16)
-    if fused and rows == 1 and GEMV_MAX_ROWS >= 1 and C % _ROW_K[q8] == 0 and C <= _ROW_MAX_K:
+    if fused and rows == 1 and GEMV_MAX_ROWS >= 1 and C % _ROW_K[form] == 0 and C <= _ROW_MAX_K:
         ops, s_new = _ln_operands(res, branch, ln_w, ln_b, (C,))
         y = _stream_call("gemv_ln", map(_lib.ptr, ops), w, b, (N,), res.device, (N, C, LN_EPS), gelu, out_f32,
                          _lib.ptr(pos_inc))
         return s_new, y.view(*res.shape[:-1], N)
-    if (fused and 2 <= rows <= min(SKINNY_MAX_ROWS, SKINNY_LN_MAX_ROWS) and C % _SKINNY_K[q8] == 0
+    if (fused and 2 <= rows <= min(SKINNY_MAX_ROWS, SKINNY_LN_MAX_ROWS) and C % _SKINNY_K[form] == 0
             and C <= _SKINNY_LN_MAX_K and (q8 or N % 16 == 0) and not (gelu and out_f32)
             and out_dtype in (None, BF16)):
         # 2..16 rows: residual add + LayerNorm recomputed per workgroup in the skinny GEMM's prologue
@@ -1704,9 +1789,8 @@ def decode_embed_linear_ln(tok, pos, wte, wpe, ln_w, ln_b, w, b=None, dtype=BF16
     B = tok.numel()
     C = wte.shape[1]
     wte_c, wpe_c = compute_weight(wte, dtype), compute_weight(wpe, dtype)
-    q8 = isinstance(w, QuantWeight)
     if (tok.is_cuda and B == 1 and dtype == BF16 and res_dtype == F32 and GEMV_MAX_ROWS >= 1
-            and C % _ROW_K[q8] == 0 and C <= _ROW_MAX_K):
+            and C % _ROW_K[_weight_form(w)] == 0 and C <= _ROW_MAX_K):
         N = w.shape[0]
         x = torch.empty(1, 1, C, device=tok.device, dtype=F32)
         lw, lb = compute_weight(ln_w, BF16), compute_weight(ln_b, BF16) if ln_b is not None else None

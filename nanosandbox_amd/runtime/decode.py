@@ -39,6 +39,9 @@ model's (``ops.quantize_rows_int8``): every step streams int8 weights through th
 ``_q8`` forms of the same kernels (half the bytes, the same launches, the same captured
 graph), and prefill and the embedding read the dequantized weights through the
 ``compute`` shadows, so prompt and steps see one model.
+``Decoder(..., quantize="mxfp4")`` is the same mode with OCP MXFP4 weights (``ops.quantize_mxfp4``,
+the ``_mx4`` kernels): the dequantized values are exact in bf16, so prompt and steps see the
+very same weights.
 ``Decoder(..., kv_quantize="int8")`` keeps the caches as int8 rows with one fp32 scale per
 row (``ops.QuantCache``: 68 bytes per K or V row instead of 128, so a step reads 0.53x the
 cache bytes and the caches take 0.53x the memory).  The prompt goes through flash attention
@@ -234,7 +237,8 @@ def _check(quantize=None, kv_quantize=None, shared_prompt=False, shared_prefix=F
     ``logprobs`` validated (None: off; 0 .. 8 alternatives).  ``penalize``: a count table, or a call
     with a penalty on; ``rows`` / ``max_new``: a decoder's own (a front end plans them afterwards);
     ``beams``: the hypotheses of a beam search (None: no search)."""
-    if quantize not in (None, "int8"):
+    if quantize not in (None, "int8", "mxfp4"):
+        # the wording is pinned (tests/golden/decode_refusals.json); 'mxfp4' is accepted beside 'int8'
         raise ValueError(f"quantize must be None or 'int8', got {quantize!r}")
     if kv_quantize not in (None, "int8"):
         raise ValueError(f"kv_quantize must be None or 'int8', got {kv_quantize!r}")
@@ -323,12 +327,12 @@ class Decoder:
                                  f"rows on the GPU ({ops.functional.SKINNY_MAX_ROWS} step rows), got batch size "
                                  f"{batch_size}")
         if quantize:
-            # the int8 kernels are the single-row and skinny ones; there is no int8 form of the
+            # the int8 / MXFP4 kernels are the single-row and skinny ones; there is no quantized form of the
             # larger-batch GEMMs, and no silent bf16 step instead
             if on_gpu and batch_size > ops.functional.SKINNY_MAX_ROWS:
-                raise ValueError(f"quantize='int8' decodes at most {ops.functional.SKINNY_MAX_ROWS} rows on the GPU "
-                                 f"(the skinny int8 kernels), got batch size {batch_size}")
-            needs_fused("quantize='int8'")
+                raise ValueError(f"quantize={quantize!r} decodes at most {ops.functional.SKINNY_MAX_ROWS} rows on the "
+                                 f"GPU (the skinny {quantize} kernels), got batch size {batch_size}")
+            needs_fused(f"quantize={quantize!r}")
         self.B = batch_size
         self.T = max_len or cfg.block_size
         assert self.T <= cfg.block_size, "caches cannot exceed the position-embedding table"
@@ -443,7 +447,7 @@ class Decoder:
         # fp32 weight on every use (124M: ~750 MB of conversion traffic per token, and
         # inside the captured graph too).  Created here, dropped by ``release()``.
         self._shadowed = []
-        self.qweights = {}   # int8 mode: id(parameter) -> ops.QuantWeight
+        self.qweights = {}   # int8 / mxfp4 mode: id(parameter) -> ops.QuantWeight / ops.MxWeight
         self._qsaved = []    # (parameter, attribute, had it, value) to put back in release()
         if quantize:
             self._quantize_weights()
@@ -475,11 +479,13 @@ class Decoder:
                 and self.W == int(num_beams or 0))
 
     def _quantize_weights(self):
-        """int8 mode: quantize every linear weight and the tied lm_head / wte table, and point
+        """int8 / mxfp4 mode: quantize every linear weight and the tied lm_head / wte table, and point
         their ``compute`` shadows (what prefill and the embedding gather read) at the
         dequantized weights in the compute dtype (fp32 on the CPU included), so the prompt
-        runs through the same model as the int8 steps.  Whatever ``compute`` a parameter had
-        (a trained model's optimizer shadow) is kept for ``release()``."""
+        runs through the same model as the quantized steps (MXFP4 values are exact in bf16: the
+        very same weights).  Whatever ``compute`` a parameter had (a trained model's optimizer
+        shadow) is kept for ``release()``."""
+        quantize = ops.quantize_mxfp4 if self.quantize == "mxfp4" else ops.quantize_rows_int8
         model = self.model
         params = []
         for block in model.transformer.h:
@@ -488,7 +494,7 @@ class Decoder:
         head = model.lm_head.weight  # tied to wte: the token embeddings are the dequantized rows too
         params.append(head)
         for prm in params:
-            qw = ops.quantize_rows_int8(prm)
+            qw = quantize(prm)
             self.qweights[id(prm)] = qw
             self._qsaved.append((prm, "compute", hasattr(prm, "compute"), getattr(prm, "compute", None)))
             prm.compute = ops.dequantize(qw).to(self.dtype)
@@ -500,7 +506,7 @@ class Decoder:
         ops.gemm_dispatch.weights_changed()
 
     def _w(self, prm):
-        """The weight a decode op streams: the parameter, or its QuantWeight in int8 mode."""
+        """The weight a decode op streams: the parameter, or its QuantWeight / MxWeight in int8 / mxfp4 mode."""
         return self.qweights.get(id(prm), prm)
 
     def release(self):
@@ -564,7 +570,7 @@ class Decoder:
         rides in the attention kernel and bias / GELU in the GEMV epilogues: 5 launches
         per layer."""
         tr = self.model.transformer
-        W = self._w  # int8 mode: the QuantWeight of a linear's weight
+        W = self._w  # int8 / mxfp4 mode: the QuantWeight / MxWeight of a linear's weight
         branch = None  # the previous sublayer's output, not yet added to the residual x
         for i, block in enumerate(tr.h):
             attn, mlp = block.attn, block.mlp

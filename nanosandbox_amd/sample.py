@@ -15,7 +15,8 @@ batch of unequal lengths, ``--stop_token=ID`` ends a sample at that token
 ``--top_p=0.9`` (nucleus) and ``--min_p=0.05`` narrow the sampled set on top of ``top_k``
 (``--top_k=0``: no top-k); on the GPU the selection runs inside the sampling kernel.
 ``--quantize=int8`` decodes with int8 weight-only linears (per-row scales; the KV-cache
-path only, so it refuses ``--kv_cache=False``).  ``--kv_quantize=int8`` keeps the KV caches
+path only, so it refuses ``--kv_cache=False``); ``--quantize=mxfp4`` with OCP MXFP4 ones
+(4-bit elements, one scale byte per 32; the same refusal).  ``--kv_quantize=int8`` keeps the KV caches
 as int8 rows with one scale each (the same refusal).  ``--shared_prompt=True`` with
 ``--sample_batch=N`` encodes and caches the prompt once for the N rows of a batch and once
 for all rounds (``Decoder(shared_prompt=True)``); it refuses ``--prompts_file``,
@@ -88,7 +89,7 @@ SAMPLE_DEFAULTS = dict(
     sample_batch=1,  # samples of the prompt generated per decoder run (num_samples is still the total)
     prompts_file="",  # one prompt per line, generated as one ragged batch per sample round (start is ignored)
     stop_token=-1,  # token id that ends a sample (printed text ends before it); -1: none
-    quantize="",  # "int8": int8 weight-only decoding on the KV-cache path (Decoder(quantize="int8")); "": off
+    quantize="",  # "int8" / "mxfp4": weight-only decoding on the KV-cache path (Decoder(quantize=...)); "": off
     kv_quantize="",  # "int8": int8 KV caches, one scale per cache row (Decoder(kv_quantize="int8")); "": off
     shared_prompt=False,  # sample_batch > 1: encode and cache the prompt once for the batch (Decoder(shared_prompt=True))
     shared_prefix=False,  # prompts_file / sample_batch > 1: encode and cache the prompts' common prefix once for the batch
@@ -288,8 +289,8 @@ def main(argv=None):
     c = parse_argv(SAMPLE_DEFAULTS, sys.argv[1:] if argv is None else argv)
     check_sampling_filters(c["top_p"], c["min_p"])
     check_sampling_penalties(c["repetition_penalty"], c["presence_penalty"], c["frequency_penalty"])
-    if c["quantize"] not in ("", "int8"):
-        raise ValueError(f"quantize must be '' or 'int8', got {c['quantize']!r}")
+    if c["quantize"] not in ("", "int8", "mxfp4"):
+        raise ValueError(f"quantize must be '', 'int8' or 'mxfp4', got {c['quantize']!r}")
     if c["quantize"] and not c["kv_cache"]:
         raise ValueError("--quantize needs the KV-cache path: the recompute loop (--kv_cache=False) runs the "
                          "unquantized model")

@@ -16,7 +16,8 @@ the whole mode list N times, interleaved, for the run-to-run spread.  ``--sample
 times sample.py's flow for N samples of one prompt: a reused batch-1 decoder N times over
 (``sample_loop``) against one ``generate_batch`` of N rows (``sample_batch``).
 ``--quantize int8`` adds ``graph_int8`` / ``rows_int8``, the ``graph`` / ``rows`` modes on a
-``Decoder(quantize="int8")``, next to their bf16 twins in the interleaved mode list.
+``Decoder(quantize="int8")``, next to their bf16 twins in the interleaved mode list;
+``--quantize mxfp4`` adds ``graph_mxfp4`` / ``rows_mxfp4`` likewise (``int8,mxfp4``: both).
 ``--kv_quantize int8`` adds ``graph_kv8`` / ``rows_kv8`` (int8 KV caches,
 ``Decoder(kv_quantize="int8")``) and, with ``--quantize int8``, ``graph_int8_kv8`` /
 ``rows_int8_kv8``, each next to its twin; ``--prompt`` sets the context length the steps start
@@ -315,8 +316,9 @@ def main():
     ap.add_argument("--repeat", type=int, default=1, help="run the mode list this many times (interleaved)")
     ap.add_argument("--samples", type=int, default=0, help="also time N samples of one prompt: loop vs one batch")
     ap.add_argument("--calibrate", action="store_true", help="first print the box calibration GEMM (utils/boxcal.py)")
-    ap.add_argument("--quantize", default="", choices=["", "int8"],
-                    help="int8: add int8 weight-only twins of the graph and rows modes (graph_int8, rows_int8)")
+    ap.add_argument("--quantize", default="", choices=["", "int8", "mxfp4", "int8,mxfp4"],
+                    help="int8 / mxfp4: add weight-only twins of the graph and rows modes (graph_int8, rows_int8; "
+                         "graph_mxfp4, rows_mxfp4); int8,mxfp4: both, interleaved in one run")
     ap.add_argument("--kv_quantize", default="", choices=["", "int8"],
                     help="int8: add int8-KV-cache twins of the graph and rows modes (graph_kv8, rows_kv8; with "
                          "--quantize int8 also graph_int8_kv8, rows_int8_kv8)")
@@ -360,16 +362,17 @@ def main():
         print(json.dumps({"calibration_gemm": cal}), flush=True)
     modes = a.modes.split(",") + (["ragged"] if a.ragged else [])
     modes = [m for m in modes if m]
-    if a.quantize:  # each int8 twin right after its bf16 mode
-        modes = [t for m in modes for t in ([m, f"{m}_{a.quantize}"] if m in ("graph", "rows") else [m])]
+    if a.quantize:  # each quantized twin right after its bf16 mode
+        qs = a.quantize.split(",")
+        modes = [t for m in modes for t in ([m] + [f"{m}_{q}" for q in qs] if m in ("graph", "rows") else [m])]
     if a.kv_quantize:  # each int8-cache twin right after its mode (the int8-weight twins included)
         modes = [t for m in modes for t in ([m, f"{m}_kv8"] if m.partition("_")[0] in ("graph", "rows") else [m])]
     if a.shared_prompt:  # each shared twin right after its rows mode (bf16 caches only)
-        modes = [t for m in modes for t in ([m, f"{m}_shared"] if m in ("rows", "rows_int8") else [m])]
+        modes = [t for m in modes for t in ([m, f"{m}_shared"] if m in ("rows", "rows_int8", "rows_mxfp4") else [m])]
     if a.speculate:  # the speculative twins right after their rows mode (bf16 caches only)
         twins = [f"spec{int(k)}" + t for k in a.speculate.split(",")
                  for t in [""] + ["_" + x for x in a.spec_table.split(",") if x]]
-        modes = [t for m in modes for t in ([m] + [f"{m}_{x}" for x in twins] if m in ("rows", "rows_int8") else [m])]
+        modes = [t for m in modes for t in ([m] + [f"{m}_{x}" for x in twins] if m in ("rows", "rows_int8", "rows_mxfp4") else [m])]
     if a.penalties:  # each penalised twin right after its mode
         rp, pp, fp = (float(x) for x in a.penalties.split(","))
         PEN.update(repetition_penalty=rp, presence_penalty=pp, frequency_penalty=fp)
@@ -429,7 +432,7 @@ def main():
                                       "calibration_tflops": cal.get("tflops"), **extra}), flush=True)
                 for mode in [] if a.queue else modes:
                     base, *sfx = mode.split("_")  # graph_int8_kv8 -> graph, int8 weights, int8 caches
-                    qz = "int8" if "int8" in sfx else None
+                    qz = next((q for q in ("int8", "mxfp4") if q in sfx), None)
                     kvq = "int8" if "kv8" in sfx else None
                     ttft = {}
                     spec = next((int(x[4:]) for x in sfx if x.startswith("spec")), 0)
