@@ -30,7 +30,15 @@ constexpr int WIDE_TILE_N = 64;           // its workgroup's output columns: one
 constexpr int WIDE_CHUNK = 256;           // k per LDS chunk of X (8 units of 32), double-buffered
 constexpr int WIDE_TARGET_WGS = 128;      // its split-K rule: tiles x KS up to this many workgroups ...
 constexpr int WIDE_MIN_UNITS = 32;        // ... with at least this many 32-wide K units (4 chunks) per workgroup
-constexpr int ROW_K_BF16 = 8, ROW_K_Q8 = 16;        // K granule of the vector kernels: k per 16-byte weight piece
+constexpr int TALL_MAX_ROWS = 256;        // all-rows 32x32 MFMA GEMM (decode_tall.hip): 3, 4, 6 or 8 blocks of 32 rows
+constexpr int TALL_TILE_N = 128;          // its workgroup's output columns: one wave per 32
+constexpr int TALL_CHUNK = 128;           // k per LDS chunk of X (4 units of 32), double-buffered
+constexpr int TALL_SLOTS = 256;           // its split-K rule: workgroups the machine runs at once (one per CU) ...
+constexpr int TALL_MIN_UNITS = 8;         // ... at least this many 32-wide K units (2 chunks) per workgroup ...
+constexpr int TALL_MAX_KS = 64;           // ... at most this many workgroups along K ...
+constexpr int TALL_MAX_SPLIT_TILES = 1024; // ... no split above this many column tiles: the workspace's fixed counter region
+constexpr int TALL_PART_WEIGHT = 2;       // ... and a byte of fp32 partials counted as this many streamed bytes
+constexpr int ROW_K_BF16 = 8, ROW_K_Q8 = 16;       // K granule of the vector kernels: k per 16-byte weight piece
 constexpr int SKINNY_K_BF16 = 32, SKINNY_K_Q8 = 64;  // K granule of the skinny kernels: k per lane group's unit
 constexpr int MX4_K = 32;  // K granule of every MXFP4 kernel (decode_mx4.hip): one block of 32 under one scale byte
 

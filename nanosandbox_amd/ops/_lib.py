@@ -110,6 +110,11 @@ _SIGNATURES = {
                       c_int64, c_void_p],
     "nsa_wide_gemm_ws_bytes": [c_int, c_int, c_int, c_int],
     "nsa_wide_gemm_ksplit": [c_int, c_int, c_int],
+    # 65 .. 256 rows (csrc/kernels/decode_tall.hip): nsa_wide_gemm's arguments
+    "nsa_tall_gemm": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                      c_int64, c_void_p],
+    "nsa_tall_gemm_ws_bytes": [c_int, c_int, c_int, c_int],
+    "nsa_tall_gemm_ksplit": [c_int, c_int, c_int],
     "nsa_skinny_ln_gemm": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p,
                            c_int, c_int, c_int, c_int, c_int, c_void_p],
     "nsa_gemv_emb_ln": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
@@ -219,7 +224,8 @@ _SIGNATURES = {
     "nsa_probe_mark": [c_void_p, c_void_p],
 }
 # entry points whose return value is not a hipError_t
-_RESTYPES = {"nsa_keysort_ws_bytes": c_int64, "nsa_ln_nt_min_bytes": c_int64, "nsa_wide_gemm_ws_bytes": c_int64}
+_RESTYPES = {"nsa_keysort_ws_bytes": c_int64, "nsa_ln_nt_min_bytes": c_int64, "nsa_wide_gemm_ws_bytes": c_int64,
+             "nsa_tall_gemm_ws_bytes": c_int64}
 
 
 class KernelLibraryMissing(RuntimeError):

@@ -1666,26 +1666,41 @@ SKINNY_LN_MAX_ROWS = int(os.environ.get("NSA_SKINNY_LN_MAX_ROWS", "8"))
 WIDE_MAX_ROWS = int(os.environ.get("NSA_WIDE_MAX_ROWS", "64"))
 WIDE_CHUNK = 256                   # WIDE_CHUNK (decode_rows.h): k per LDS chunk of the wide kernel
 _WIDE_WS_MIN = 3 << 20             # first size of its workspace: above every split the rule picks (128 x 16 KB)
-_WIDE_WS = {}                      # device index -> the workspace (uint8, counters zero)
+_WIDE_WS = {}                      # device index (wide) or (entry, device index) -> the workspace (uint8, counters zero)
 _WIDE_WS_RETIRED = []              # outgrown workspaces: a captured graph may still hold their address
+# decode batches above both caps up to TALL_MAX_ROWS rows: the all-rows 32x32 MFMA weight stream
+# (nsa_tall_gemm, csrc/kernels/decode_tall.hip: 128-column workgroups own every row, X through LDS in
+# chunks of 128 k, split-K weighed against the partials' bytes); above it ``linear``.  HIP-graph decode,
+# ms/token (GPT-2 124M / 1.5B), ``linear`` vs this kernel, medians of three (repeats within 0.5 %): batch 96
+# 1.805 / 12.84 vs 1.493 / 8.85; 128 1.849 / 13.23 vs 1.774 / 10.16; 192 1.981 / 14.34 vs 2.272 / 13.09;
+# 256 2.214 / 15.55 vs 2.811 / 16.42.  It loses 124M from 192 rows and both models at 256, so the cap is
+# 128 (the kernel itself takes up to 256).  At or below the wide cap it is off and every launch is the one
+# made without it.
+TALL_MAX_ROWS = int(os.environ.get("NSA_TALL_MAX_ROWS", "128"))
+_TALL_LIMIT = 256                  # TALL_MAX_ROWS (decode_rows.h): the rows the kernel itself accepts
+TALL_CHUNK = 128                   # TALL_CHUNK: k per LDS chunk of the tall kernel
+TALL_TILE_N = 128                  # TALL_TILE_N: output columns of its workgroup
 
 
-def _wide_workspace(device, rows, N, K):
-    """(pointer, bytes) of the device's ``nsa_wide_gemm`` workspace, large enough for this shape under
-    the rule's split; (None, 0) where the launch needs none.  One buffer per device, zero when
-    allocated (the kernel leaves its counters zero), shared by successive launches; it is never
-    grown inside a graph capture (a step's warm-up outside the capture sizes it)."""
-    need = _lib.call_ret("nsa_wide_gemm_ws_bytes", rows, N, K, 0)
+def _wide_workspace(entry, device, rows, N, K):
+    """(pointer, bytes) of the device's split-K workspace of ``entry`` (``nsa_wide_gemm`` or ``nsa_tall_gemm``),
+    large enough for this shape under the rule's split; (None, 0) where the launch needs none.  One buffer
+    per device and entry (the two kernels lay their counters out differently, so neither's partials may
+    land in the other's buffer), zero when allocated (every launch leaves its counters zero), shared by
+    successive launches; it is never grown inside a graph capture (a step's warm-up outside the capture
+    sizes it)."""
+    need = _lib.call_ret(entry + "_ws_bytes", rows, N, K, 0)
     if need == 0:
         return None, 0
-    ws = _WIDE_WS.get(device.index)
+    key = device.index if entry == "nsa_wide_gemm" else (entry, device.index)
+    ws = _WIDE_WS.get(key)
     if ws is None or ws.numel() < need:
         if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("nsa_wide_gemm's workspace must be sized outside a graph capture: run the step "
+            raise RuntimeError(f"{entry}'s workspace must be sized outside a graph capture: run the step "
                                "eagerly once before capturing it")
         if ws is not None:
             _WIDE_WS_RETIRED.append(ws)
-        ws = _WIDE_WS[device.index] = torch.zeros(max(need, _WIDE_WS_MIN), device=device, dtype=torch.uint8)
+        ws = _WIDE_WS[key] = torch.zeros(max(need, _WIDE_WS_MIN), device=device, dtype=torch.uint8)
     return ws.data_ptr(), ws.numel()
 
 
@@ -1699,7 +1714,9 @@ def decode_linear(x, w, b=None, gelu: bool = False, out_f32: bool = False):
     batches of 2 .. ``NSA_SKINNY_MAX_ROWS`` (16) rows run on ``nsa_skinny_gemm`` (MFMA
     weight stream, bias / GELU epilogue) when N % 16 == 0 and K % 32 == 0; batches above that up
     to ``NSA_WIDE_MAX_ROWS`` (64) rows run on ``nsa_wide_gemm`` (64-column workgroups, split-K; bf16
-    weights only) under the same conditions; larger batches go to ``linear`` (our small-tile / NT
+    weights only) under the same conditions; batches above that up to ``NSA_TALL_MAX_ROWS`` (128) rows run on
+    ``nsa_tall_gemm`` (128-column workgroups owning all rows on 32x32 MFMAs, split-K; bf16 weights
+    only), again under the same conditions; larger batches go to ``linear`` (our small-tile / NT
     kernels: no library GEMM on this path).
 
     ``w`` may be a ``QuantWeight``: the same rules pick the ``_q8`` form of the same kernel
@@ -1728,7 +1745,12 @@ def decode_linear(x, w, b=None, gelu: bool = False, out_f32: bool = False):
     elif (x.is_cuda and x.dtype == BF16 and not q8 and SKINNY_MAX_ROWS < rows <= WIDE_MAX_ROWS and N % 16 == 0
             and K % _SKINNY_K["bf16"] == 0 and not (gelu and out_f32)):
         kind = "wide_gemm"
-        extra = (0, *_wide_workspace(x.device, rows, N, K))  # ksplit 0: the kernel's own rule
+        extra = (0, *_wide_workspace("nsa_wide_gemm", x.device, rows, N, K))  # ksplit 0: the kernel's own rule
+    elif (x.is_cuda and x.dtype == BF16 and not q8
+            and max(SKINNY_MAX_ROWS, WIDE_MAX_ROWS) < rows <= min(TALL_MAX_ROWS, _TALL_LIMIT) and N % 16 == 0
+            and K % _SKINNY_K["bf16"] == 0 and not (gelu and out_f32)):
+        kind = "tall_gemm"
+        extra = (0, *_wide_workspace("nsa_tall_gemm", x.device, rows, N, K))
     if kind:
         x2 = x.reshape(rows, K).contiguous()
         y = _stream_call(kind, (_lib.ptr(x2),), w, b, (rows, N), x.device, (rows, N, K), gelu, out_f32, *extra)

@@ -61,6 +61,8 @@ a ``Decoder(logprobs=N)``, whose step records every drawn token's log-probabilit
 ``--wide_ab`` adds ``graph_narrow`` / ``rows_narrow`` right after ``graph`` / ``rows``: the same run with
 ``ops.functional.WIDE_MAX_ROWS`` lowered to ``SKINNY_MAX_ROWS``, so batches of 17 .. 64 rows take ``linear``
 instead of ``nsa_wide_gemm``: the path before the wide kernel, launch for launch.
+``--tall_ab`` adds ``graph_short`` / ``rows_short`` in the same way: ``ops.functional.TALL_MAX_ROWS`` lowered to
+``WIDE_MAX_ROWS``, so batches of 65 .. 256 rows take ``linear`` instead of ``nsa_tall_gemm``.
 """
 
 import argparse
@@ -345,6 +347,9 @@ def main():
     ap.add_argument("--wide_ab", action="store_true",
                     help="add twins of the graph and rows modes with the wide decode GEMM off (graph_narrow, "
                          "rows_narrow)")
+    ap.add_argument("--tall_ab", action="store_true",
+                    help="add twins of the graph and rows modes with the tall decode GEMM off (graph_short, "
+                         "rows_short)")
     ap.add_argument("--beams", default="", help="W[,W ...]: only beam search of these widths, interleaved with "
                     "shared-prompt sampling at batch W (the same linears; the select and the gather differ): "
                     "medians of --repeat runs")
@@ -383,6 +388,8 @@ def main():
         modes = [t for m in modes for t in ([m] + [f"{m}_{x}" for x in twins] if m in ("graph", "rows") else [m])]
     if a.wide_ab:  # each narrow twin right after its mode
         modes = [t for m in modes for t in ([m, f"{m}_narrow"] if m in ("graph", "rows") else [m])]
+    if a.tall_ab:  # each short twin right after its mode
+        modes = [t for m in modes for t in ([m, f"{m}_short"] if m in ("graph", "rows") else [m])]
     if a.shared_prefix:
         modes = ["prefix_rows", "prefix_shared"]
     block_size = GPTConfig().block_size
@@ -437,9 +444,11 @@ def main():
                     ttft = {}
                     spec = next((int(x[4:]) for x in sfx if x.startswith("spec")), 0)
                     lp = next((int(x[2:]) for x in sfx if x.startswith("lp")), None)
-                    wide_cap = functional.WIDE_MAX_ROWS
+                    wide_cap, tall_cap = functional.WIDE_MAX_ROWS, functional.TALL_MAX_ROWS
                     if "narrow" in sfx:
                         functional.WIDE_MAX_ROWS = functional.SKINNY_MAX_ROWS
+                    if "short" in sfx:
+                        functional.TALL_MAX_ROWS = functional.WIDE_MAX_ROWS
                     if a.memory:
                         torch.cuda.synchronize()
                         torch.cuda.reset_peak_memory_stats()
@@ -474,7 +483,7 @@ def main():
                         n = a.new
                         run_cached(model, idx, 4, base == "graph", qz, kvq, "pen" in sfx, lp)
                         dt = run_cached(model, idx, n, base == "graph", qz, kvq, "pen" in sfx, lp)
-                    functional.WIDE_MAX_ROWS = wide_cap
+                    functional.WIDE_MAX_ROWS, functional.TALL_MAX_ROWS = wide_cap, tall_cap
                     mem = ({"decoder_peak_mb": round((torch.cuda.max_memory_allocated() - mem0) / 2 ** 20, 1)}
                            if a.memory else {})
                     print(json.dumps({"model": name, "batch": B, "mode": mode, "prompt": a.prompt, "new_tokens": n,
