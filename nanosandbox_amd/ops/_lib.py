@@ -147,6 +147,16 @@ _SIGNATURES = {
                           c_void_p],
     "nsa_gemv_ln_mx4": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                         c_int, c_int, c_float, c_int, c_int, c_void_p, c_void_p],
+    # 17 .. 64 rows on quantized weights (csrc/kernels/decode_wide_q.hip): nsa_wide_gemm's arguments with
+    # (Wq, scale) where it takes W
+    "nsa_wide_gemm_q8": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                         c_void_p, c_int64, c_void_p],
+    "nsa_wide_gemm_q8_ws_bytes": [c_int, c_int, c_int, c_int],
+    "nsa_wide_gemm_q8_ksplit": [c_int, c_int, c_int],
+    "nsa_wide_gemm_mx4": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                          c_void_p, c_int64, c_void_p],
+    "nsa_wide_gemm_mx4_ws_bytes": [c_int, c_int, c_int, c_int],
+    "nsa_wide_gemm_mx4_ksplit": [c_int, c_int, c_int],
     # int8 KV caches (csrc/kernels/decode.hip): (q, scale) per cache where the bf16 entry point takes kc / vc
     "nsa_kv_append_kv8": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                           c_int, c_int, c_void_p],
@@ -225,7 +235,8 @@ _SIGNATURES = {
 }
 # entry points whose return value is not a hipError_t
 _RESTYPES = {"nsa_keysort_ws_bytes": c_int64, "nsa_ln_nt_min_bytes": c_int64, "nsa_wide_gemm_ws_bytes": c_int64,
-             "nsa_tall_gemm_ws_bytes": c_int64}
+             "nsa_tall_gemm_ws_bytes": c_int64, "nsa_wide_gemm_q8_ws_bytes": c_int64,
+             "nsa_wide_gemm_mx4_ws_bytes": c_int64}
 
 
 class KernelLibraryMissing(RuntimeError):

@@ -1680,10 +1680,18 @@ TALL_MAX_ROWS = int(os.environ.get("NSA_TALL_MAX_ROWS", "128"))
 _TALL_LIMIT = 256                  # TALL_MAX_ROWS (decode_rows.h): the rows the kernel itself accepts
 TALL_CHUNK = 128                   # TALL_CHUNK: k per LDS chunk of the tall kernel
 TALL_TILE_N = 128                  # TALL_TILE_N: output columns of its workgroup
+# a ``QuantWeight`` / ``MxWeight`` at SKINNY_MAX_ROWS + 1 .. min(WIDE_MAX_ROWS, QUANT_MAX_ROWS) rows: the wide kernel's
+# quantized forms (nsa_wide_gemm_q8 / _mx4, csrc/kernels/decode_wide_q.hip: the same workgroup streaming int8 or
+# MXFP4 weights, K % 64 / K % 32 == 0, any N).  Opt-in: at the default of 16 the branch is never taken, such a
+# weight above 16 rows takes the dequantize fallback and the Decoder refuses the batch, as before the kernels
+# existed; 64 turns them on for every row count the wide kernel serves.
+QUANT_MAX_ROWS = int(os.environ.get("NSA_QUANT_MAX_ROWS", "16"))
+WIDE_Q_CHUNK = {"q8": 256, "mx4": 512}  # the CHUNK of WqQ8 / WqMx4 (decode_wide_q.hip): k per LDS chunk of X
 
 
 def _wide_workspace(entry, device, rows, N, K):
-    """(pointer, bytes) of the device's split-K workspace of ``entry`` (``nsa_wide_gemm`` or ``nsa_tall_gemm``),
+    """(pointer, bytes) of the device's split-K workspace of ``entry`` (``nsa_wide_gemm``, its ``_q8`` / ``_mx4``
+    forms or ``nsa_tall_gemm``),
     large enough for this shape under the rule's split; (None, 0) where the launch needs none.  One buffer
     per device and entry (the two kernels lay their counters out differently, so neither's partials may
     land in the other's buffer), zero when allocated (every launch leaves its counters zero), shared by
@@ -1724,9 +1732,12 @@ def decode_linear(x, w, b=None, gelu: bool = False, out_f32: bool = False):
     not cover (CPU, fp32, other K, more rows) runs the rest of this function on
     ``dequantize(w)`` in x's dtype: the reference semantics, and a slow path on the GPU.
     An ``MxWeight`` likewise picks the ``_mx4`` forms (K % 32 == 0, any N; one row up to K = 8192 on
-    ``nsa_gemv_mx4``, 2 .. 16 rows on ``nsa_skinny_gemm_mx4``), with the same fallback."""
+    ``nsa_gemv_mx4``, 2 .. 16 rows on ``nsa_skinny_gemm_mx4``), with the same fallback.  With
+    ``NSA_QUANT_MAX_ROWS`` raised above 16 (opt-in; 64 for the whole range) either quantized weight at 17 ..
+    min(``NSA_WIDE_MAX_ROWS``, ``NSA_QUANT_MAX_ROWS``) rows runs on ``nsa_wide_gemm_q8`` / ``nsa_wide_gemm_mx4``
+    (the wide kernel's workgroup and split-K; K % 64 / K % 32 == 0, any N) instead of the fallback."""
     form = _weight_form(w)
-    q8 = form != "bf16"  # a quantized stream: any N on the skinny kernel, no wide kernel, the dequantize fallback
+    q8 = form != "bf16"  # a quantized stream: any N, the wide kernel by QUANT_MAX_ROWS only, the dequantize fallback
     N = w.shape[0]
     if isinstance(x, AttnPartials):  # one row; the attention combine runs in the GEMV prologue
         y = _stream_call("gemv_attn", (_lib.ptr(x.ws), x.n_split), w, b, (N,), x.ws.device, (N, x.C), gelu, out_f32)
@@ -1746,6 +1757,10 @@ def decode_linear(x, w, b=None, gelu: bool = False, out_f32: bool = False):
             and K % _SKINNY_K["bf16"] == 0 and not (gelu and out_f32)):
         kind = "wide_gemm"
         extra = (0, *_wide_workspace("nsa_wide_gemm", x.device, rows, N, K))  # ksplit 0: the kernel's own rule
+    elif (x.is_cuda and x.dtype == BF16 and q8 and SKINNY_MAX_ROWS < rows <= min(WIDE_MAX_ROWS, QUANT_MAX_ROWS)
+            and K % _SKINNY_K[form] == 0 and not (gelu and out_f32)):
+        kind = "wide_gemm"
+        extra = (0, *_wide_workspace("nsa_wide_gemm" + _stream_weight(w)[0], x.device, rows, N, K))
     elif (x.is_cuda and x.dtype == BF16 and not q8
             and max(SKINNY_MAX_ROWS, WIDE_MAX_ROWS) < rows <= min(TALL_MAX_ROWS, _TALL_LIMIT) and N % 16 == 0
             and K % _SKINNY_K["bf16"] == 0 and not (gelu and out_f32)):

@@ -327,11 +327,13 @@ class Decoder:
                                  f"rows on the GPU ({ops.functional.SKINNY_MAX_ROWS} step rows), got batch size "
                                  f"{batch_size}")
         if quantize:
-            # the int8 / MXFP4 kernels are the single-row and skinny ones; there is no quantized form of the
-            # larger-batch GEMMs, and no silent bf16 step instead
-            if on_gpu and batch_size > ops.functional.SKINNY_MAX_ROWS:
-                raise ValueError(f"quantize={quantize!r} decodes at most {ops.functional.SKINNY_MAX_ROWS} rows on the "
-                                 f"GPU (the skinny {quantize} kernels), got batch size {batch_size}")
+            # the int8 / MXFP4 kernels are the single-row and skinny ones, and the wide one's up to
+            # NSA_QUANT_MAX_ROWS (opt-in: 16 by default); no silent bf16 step above them
+            fn = ops.functional
+            cap = max(fn.SKINNY_MAX_ROWS, min(fn.WIDE_MAX_ROWS, fn.QUANT_MAX_ROWS))
+            if on_gpu and batch_size > cap:
+                raise ValueError(f"quantize={quantize!r} decodes at most {cap} rows on the GPU (the skinny {quantize} "
+                                 f"kernels, and the wide ones up to NSA_QUANT_MAX_ROWS), got batch size {batch_size}")
             needs_fused(f"quantize={quantize!r}")
         self.B = batch_size
         self.T = max_len or cfg.block_size
