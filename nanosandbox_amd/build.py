@@ -60,12 +60,13 @@ def _run(cmd):
 # library built with file_flags={}).
 FILE_FLAGS = {"flash_attn.hip": ["-fno-slp-vectorize"], "flash_attn_f16.hip": ["-fno-slp-vectorize"],
               # no packed fp32 arithmetic at all in the beam kernels, the wide (bf16 and quantized) and tall decode
-              # GEMMs and the MXFP4 kernels
+              # GEMMs, the MXFP4 kernels and the quantized-weight GEMM
               "decode_beam.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
               "decode_mx4.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
               "decode_tall.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
               "decode_wide.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
-              "decode_wide_q.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+              "decode_wide_q.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+              "quant_gemm.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def kernel_flags(src, defines=(), file_flags=None, include_dir=os.path.join(CSRC, "kernels")):

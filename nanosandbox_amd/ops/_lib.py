@@ -157,6 +157,11 @@ _SIGNATURES = {
                           c_void_p, c_int64, c_void_p],
     "nsa_wide_gemm_mx4_ws_bytes": [c_int, c_int, c_int, c_int],
     "nsa_wide_gemm_mx4_ksplit": [c_int, c_int, c_int],
+    # any number of rows on quantized weights (csrc/kernels/quant_gemm.hip): x, Wq, scale, bias, y, M, N, K, act
+    "nsa_quant_gemm_q8": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p],
+    "nsa_quant_gemm_mx4": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p],
+    "nsa_quant_gemm_q8_chunk": [],
+    "nsa_quant_gemm_mx4_chunk": [],
     # int8 KV caches (csrc/kernels/decode.hip): (q, scale) per cache where the bf16 entry point takes kc / vc
     "nsa_kv_append_kv8": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                           c_int, c_int, c_void_p],

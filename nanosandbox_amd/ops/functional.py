@@ -1778,6 +1778,37 @@ def decode_linear(x, w, b=None, gelu: bool = False, out_f32: bool = False):
     return y.float() if out_f32 else y
 
 
+# the CHUNK of QgQ8 / QgMx4 (csrc/kernels/quant_gemm.hip): k per LDS chunk of X; _QUANT_GEMM_K: its K granule
+QUANT_GEMM_CHUNK = {"q8": 128, "mx4": 256}
+_QUANT_GEMM_K = {"q8": 64, "mx4": 32}
+
+
+def quant_linear(x, w, b=None, gelu: bool = False):
+    """act(x @ dequantize(w)^T + b) for any number of rows, ``w`` a ``QuantWeight`` or an ``MxWeight``: the
+    prompt-side linear of a quantized decoder (``Decoder(..., quantize_prefill=True)``).  GPU, bf16 x and
+    K % 64 == 0 (int8) / K % 32 == 0 (MXFP4): one launch of ``nsa_quant_gemm_q8`` / ``nsa_quant_gemm_mx4``
+    (csrc/kernels/quant_gemm.hip: 128 x 128 tiles, the weights dequantized in registers, the int8 row scale,
+    the bias and the exact GELU in the epilogue; no workspace, deterministic), any N, bf16 out.  Anything else
+    (CPU, fp32, other K) runs ``linear`` (+ GELU) on ``dequantize(w)`` in x's dtype: the reference semantics,
+    as in ``decode_linear``.  Inference only: not an autograd node."""
+    form = _weight_form(w)
+    if form == "bf16":
+        raise TypeError(f"quant_linear takes a QuantWeight or an MxWeight, got {type(w).__name__}")
+    N, K = w.shape
+    assert x.shape[-1] == K, f"x has {x.shape[-1]} columns, the weight {K}"
+    if x.is_cuda and x.dtype == BF16 and K % _QUANT_GEMM_K[form] == 0 and x.numel() > 0:
+        rows = x.numel() // K
+        x2 = x.detach().reshape(rows, K).contiguous()
+        bc = compute_weight(b, BF16) if b is not None else None
+        y = torch.empty(rows, N, device=x.device, dtype=BF16)
+        _lib.call("nsa_quant_gemm_" + form, _lib.ptr(x2), _lib.ptr(w.q), _lib.ptr(w.scale), _lib.ptr(bc), _lib.ptr(y),
+                  rows, N, K, 1 if gelu else 0, _lib.stream())
+        return y.view(*x.shape[:-1], N)
+    with torch.no_grad():
+        y = linear(x, dequantize(w).to(x.dtype), b)
+        return GeluFn.apply(y) if gelu else y
+
+
 def decode_linear_ln(res, branch, ln_w, ln_b, w, b=None, gelu: bool = False, out_f32: bool = False,
                      out_dtype=None, pos_inc=None):
     """One decode row through residual add + LayerNorm + linear:

@@ -42,6 +42,15 @@ graph), and prefill and the embedding read the dequantized weights through the
 ``Decoder(..., quantize="mxfp4")`` is the same mode with OCP MXFP4 weights (``ops.quantize_mxfp4``,
 the ``_mx4`` kernels): the dequantized values are exact in bf16, so prompt and steps see the
 very same weights.
+``Decoder(..., quantize=..., quantize_prefill=True)`` (opt-in) runs the prompt passes on the quantized weights too:
+``_prefill_layers`` (``prefill``, ``prefill_shared``, ``prefill_suffixes`` and every ``admit``) sends c_attn, both
+c_proj and c_fc (+ GELU) through ``ops.quant_linear`` (``nsa_quant_gemm_q8`` / ``_mx4``: a GEMM for any number of
+rows that dequantizes the weights in registers), and the four linears of every block get no bf16 ``compute`` shadow, so
+the decoder holds 1 or 0.53 bytes per block weight instead of 3 or 2.53.  The tied wte / lm_head table keeps its
+dequantized shadow: the embedding gather and the prompt's last-position head read it.  The steps are the same
+launches and graphs.  Without ``quantize`` the keyword raises ValueError; on the CPU or in fp32 the decoder runs
+the dequantized model through ``quant_linear``'s fallback.  ``fits`` compares the flag and ``release()`` puts back
+whatever shadows the parameters had.  Without the keyword every launch, graph key, shadow and result is what it was.
 ``Decoder(..., kv_quantize="int8")`` keeps the caches as int8 rows with one fp32 scale per
 row (``ops.QuantCache``: 68 bytes per K or V row instead of 128, so a step reads 0.53x the
 cache bytes and the caches take 0.53x the memory).  The prompt goes through flash attention
@@ -291,7 +300,11 @@ class Decoder:
                  per_row: bool = False, quantize: str | None = None, kv_quantize: str | None = None,
                  shared_prompt: bool = False, max_new: int | None = None, speculate: int | None = None,
                  spec_ngram: int = 3, penalize: bool = False, logprobs: int | None = None,
-                 num_beams: int | None = None):
+                 num_beams: int | None = None, quantize_prefill: bool = False):
+        if quantize_prefill and not quantize:
+            raise ValueError("quantize_prefill runs the prompt on the quantized weights: it needs quantize='int8' or "
+                             "'mxfp4'")
+        self.quantize_prefill = bool(quantize_prefill)
         self.K, self.N, logprobs = _check(quantize, kv_quantize, shared_prompt, speculate=speculate,
                                           spec_ngram=spec_ngram, penalize=penalize, logprobs=logprobs,
                                           rows=batch_size, max_new=max_new, beams=num_beams)
@@ -451,10 +464,13 @@ class Decoder:
         self._shadowed = []
         self.qweights = {}   # int8 / mxfp4 mode: id(parameter) -> ops.QuantWeight / ops.MxWeight
         self._qsaved = []    # (parameter, attribute, had it, value) to put back in release()
+        self._unshadowed = set()  # quantize_prefill: id(parameter) of the block linears, which get no shadow
         if quantize:
             self._quantize_weights()
         if self.dtype != torch.float32:
             for prm in model.parameters():
+                if id(prm) in self._unshadowed:  # quantize_prefill: nothing reads a bf16 copy of these
+                    continue
                 c = getattr(prm, "compute", None)
                 if c is None or c.dtype != self.dtype:
                     prm.compute = prm.detach().to(self.dtype)
@@ -467,18 +483,20 @@ class Decoder:
                 and cfg.vocab_size <= 53248)
 
     def fits(self, batch_size, per_row=False, quantize=None, kv_quantize=None, shared_prompt=False,
-             max_new=None, speculate=None, spec_ngram=3, penalize=False, logprobs=None, num_beams=None) -> bool:
+             max_new=None, speculate=None, spec_ngram=3, penalize=False, logprobs=None, num_beams=None,
+             quantize_prefill=False) -> bool:
         """Whether a call that needs ``Decoder(model, batch_size, per_row=..., ...)`` can run on this
         one: the same rows and form, (shared) row caches of at least ``max_new`` slots, and the same
         number of drafted tokens and n-gram length (speculative), and a count table if and only if
-        the call penalises, and the log-probability buffers of the call's N alternatives, or none."""
+        the call penalises, and the log-probability buffers of the call's N alternatives, or none, and the
+        same kind of prompt pass (``quantize_prefill``)."""
         K = int(speculate or 0)
         return (self.B == batch_size and self.per_row == bool(per_row or K) and self.quantize == quantize
                 and self.kv_quantize == kv_quantize and self.shared == bool(shared_prompt)
                 and (not self.shared or self.R >= (max_new or self.T))
                 and self.K == K and (not K or self.N == int(spec_ngram))
                 and (self.cnt is not None) == bool(penalize) and self.logprobs == logprobs
-                and self.W == int(num_beams or 0))
+                and self.W == int(num_beams or 0) and self.quantize_prefill == bool(quantize_prefill))
 
     def _quantize_weights(self):
         """int8 / mxfp4 mode: quantize every linear weight and the tied lm_head / wte table, and point
@@ -486,7 +504,12 @@ class Decoder:
         dequantized weights in the compute dtype (fp32 on the CPU included), so the prompt
         runs through the same model as the quantized steps (MXFP4 values are exact in bf16: the
         very same weights).  Whatever ``compute`` a parameter had (a trained model's optimizer
-        shadow) is kept for ``release()``."""
+        shadow) is kept for ``release()``.
+
+        ``quantize_prefill``: the four linears of every block get no dequantized shadow (whatever ``compute``
+        they had is set aside until ``release()``): ``_prefill_layers`` runs them on the quantized weights
+        through ``ops.quant_linear``.  The tied wte / lm_head table keeps its dequantized shadow: the
+        embedding gather and the prompt's last-position head read it."""
         quantize = ops.quantize_mxfp4 if self.quantize == "mxfp4" else ops.quantize_rows_int8
         model = self.model
         params = []
@@ -499,6 +522,11 @@ class Decoder:
             qw = quantize(prm)
             self.qweights[id(prm)] = qw
             self._qsaved.append((prm, "compute", hasattr(prm, "compute"), getattr(prm, "compute", None)))
+            if self.quantize_prefill and prm is not head:
+                self._unshadowed.add(id(prm))
+                if hasattr(prm, "compute"):
+                    del prm.compute
+                continue
             prm.compute = ops.dequantize(qw).to(self.dtype)
         # the padded lm_head operand of a flat parameter store holds the unquantized weights
         if hasattr(head, "compute_padded"):
@@ -527,6 +555,7 @@ class Decoder:
         if self._qsaved:
             ops.gemm_dispatch.weights_changed()
         self._qsaved = []
+        self._unshadowed = set()
         self.qweights = {}
         self.graph = None
         self.sgraphs = {}
@@ -537,8 +566,18 @@ class Decoder:
         (default: the decoder's own; ``prefill_shared`` passes the prompt caches).  ``prefix``
         (``prefill_suffixes``: the prefix length P): x holds the suffixes that follow the cached
         prefix, and every query also attends over prompt-cache rows 0 .. P - 1.  ``rows``
-        (``admit``; int64 [n] on the device): row j of x is cache row ``rows[j]``."""
+        (``admit``; int64 [n] on the device): row j of x is cache row ``rows[j]``.  ``quantize_prefill``: the
+        four linears of a block run on the quantized weights (``ops.quant_linear``, bias and GELU in its
+        epilogue) instead of ``ops.linear`` / the MLP module on bf16 shadows."""
         kc, vc = kc or self.kc, vc or self.vc
+        if self.quantize_prefill:
+            W = self._w
+
+            def lin(layer, h, gelu=False):
+                return ops.quant_linear(h, W(layer.weight), layer.bias, gelu=gelu)
+        else:
+            def lin(layer, h, gelu=False):
+                return ops.linear(h, layer.weight, layer.bias)
         tr = self.model.transformer
         blocks = tr.h
         ln = blocks[0].ln_1
@@ -546,15 +585,15 @@ class Decoder:
         for i, block in enumerate(blocks):
             nxt = blocks[i + 1].ln_1 if i + 1 < len(blocks) else tr.ln_f
             attn, mlp = block.attn, block.mlp
-            qkv = ops.linear(h, attn.c_attn.weight, attn.c_attn.bias)
+            qkv = lin(attn.c_attn, h)
             ops.kv_append(qkv, kc[i], vc[i], None, 0, rows=rows)
             if prefix is None:
                 y = ops.attention(qkv, attn.n_head, 0.0, False)
             else:
                 y = ops.prefix_attention(qkv, self.pkc[i], self.pvc[i], prefix, attn.n_head)
-            y = ops.linear(y, attn.c_proj.weight, attn.c_proj.bias)
+            y = lin(attn.c_proj, y)
             x, h2 = ops.add_layer_norm(x, y, block.ln_2.weight, block.ln_2.bias)
-            y = mlp(h2)
+            y = lin(mlp.c_proj, lin(mlp.c_fc, h2, gelu=True)) if self.quantize_prefill else mlp(h2)
             x, h = ops.add_layer_norm(x, y, nxt.weight, nxt.bias)
         return h  # ln_f(x)
 
@@ -1239,6 +1278,17 @@ def _mode(B, per_row=False, quantize=None, kv_quantize=None, slots=None, spec=(0
                 penalize=bool(penalize), logprobs=logprobs, num_beams=beams)
 
 
+def _quantized_prefill(mode, quantize_prefill):
+    """``mode`` for a call with ``quantize_prefill``: the same decoder with the prompt passes on the quantized
+    weights; ValueError where the call does not quantize.  Without the keyword ``mode`` itself."""
+    if not quantize_prefill:
+        return mode
+    if not mode["quantize"]:
+        raise ValueError("quantize_prefill runs the prompt on the quantized weights: it needs quantize='int8' or "
+                         "'mxfp4'")
+    return dict(mode, quantize_prefill=True)
+
+
 def _build(model, mode, use_graph=None):
     return Decoder(model, max_len=model.config.block_size, use_graph=use_graph, **mode)
 
@@ -1299,15 +1349,16 @@ def _cached_mode(model, idx, max_new_tokens, quantize, kv_quantize, shared_promp
 
 def cached_decoder(model, idx, max_new_tokens, use_graph=None, quantize=None, kv_quantize=None, shared_prompt=False,
                    speculate=None, spec_ngram=3, repetition_penalty=None, presence_penalty=None,
-                   frequency_penalty=None, logprobs=None):
+                   frequency_penalty=None, logprobs=None, quantize_prefill=False):
     """The Decoder this ``generate_cached`` call would build, for a caller that keeps it across
     calls (``decoder=``) and releases it.  A call that runs on none (no new tokens, or the
     recompute loop) gets the ordinary one all the same, as ``sample.py`` always has: building it
     draws from torch's generator, and a seeded run keeps its tokens.  With a penalty on it is a
     penalising one, with ``logprobs`` one that records them."""
     pen = sampling_penalties(repetition_penalty, presence_penalty, frequency_penalty) is not None
-    return _build(model, _cached_mode(model, idx, max_new_tokens, quantize, kv_quantize, shared_prompt, speculate,
-                                      spec_ngram, pen, logprobs)[0], use_graph)
+    return _build(model, _quantized_prefill(_cached_mode(model, idx, max_new_tokens, quantize, kv_quantize,
+                                                         shared_prompt, speculate, spec_ngram, pen, logprobs)[0],
+                                            quantize_prefill), use_graph)
 
 
 @torch.no_grad()
@@ -1318,8 +1369,12 @@ def generate_cached(model, idx: torch.Tensor, max_new_tokens: int, temperature: 
                     kv_quantize: str | None = None, shared_prompt: bool = False,
                     speculate: int | None = None, spec_ngram: int = 3, spec_table=None,
                     repetition_penalty: float | None = None, presence_penalty: float | None = None,
-                    frequency_penalty: float | None = None, logprobs: int | None = None):
+                    frequency_penalty: float | None = None, logprobs: int | None = None,
+                    quantize_prefill: bool = False):
     """``model.generate`` with KV caches: same sampling, one token's forward per new token.
+
+    ``quantize_prefill=True`` (with ``quantize``; ValueError without): the prompt runs on the quantized weights too
+    and the decoder keeps no bf16 copy of the block linears (``Decoder(..., quantize_prefill=True)``).
 
     ``logprobs=N`` (0 .. 8; None: off): the call returns ``(tokens, ops.LogProbs)``, the second covering
     exactly the new tokens: ``token`` [B, n] is the log-probability of every drawn token under the
@@ -1362,6 +1417,7 @@ def generate_cached(model, idx: torch.Tensor, max_new_tokens: int, temperature: 
     smp = sampling(temperature, top_k, None, top_p, min_p, repetition_penalty, presence_penalty, frequency_penalty)
     mode, cached = _cached_mode(model, idx, max_new_tokens, quantize, kv_quantize, shared_prompt, speculate, spec_ngram,
                                 smp.penalties is not None, logprobs)
+    mode = _quantized_prefill(mode, quantize_prefill)
     logprobs = mode["logprobs"]
     if max_new_tokens <= 0:
         return _with_records(idx, logprobs, lambda: _no_records(idx.shape[0], logprobs, idx.device))
@@ -1549,7 +1605,8 @@ def _batch_plan(model, prompts, max_new_tokens, quantize, kv_quantize, shared_pr
 
 def batch_decoder(model, prompts, max_new_tokens, use_graph=None, quantize=None, kv_quantize=None,
                   shared_prompt=False, shared_prefix=False, batch_size=None, speculate=None, spec_ngram=3,
-                  repetition_penalty=None, presence_penalty=None, frequency_penalty=None, logprobs=None):
+                  repetition_penalty=None, presence_penalty=None, frequency_penalty=None, logprobs=None,
+                  quantize_prefill=False):
     """The Decoder this ``generate_batch`` call would build, for a caller that keeps it across
     calls (``decoder=``; a shared one then keeps the prompt or prefix too) and releases it.  A call
     that shares none (no new tokens, or no prompt that fits the cache) gets the ordinary one of a
@@ -1557,7 +1614,7 @@ def batch_decoder(model, prompts, max_new_tokens, use_graph=None, quantize=None,
     pen = sampling_penalties(repetition_penalty, presence_penalty, frequency_penalty) is not None
     mode = _batch_plan(model, prompts, max_new_tokens, quantize, kv_quantize, shared_prompt, shared_prefix, batch_size,
                        speculate, spec_ngram, pen, logprobs)[-1]
-    return _build(model, mode, use_graph)
+    return _build(model, _quantized_prefill(mode, quantize_prefill), use_graph)
 
 
 @torch.no_grad()
@@ -1569,8 +1626,11 @@ def generate_batch(model, prompts, max_new_tokens, temperature: float = 1.0, top
                    shared_prefix: bool = False, batch_size: int | None = None, speculate: int | None = None,
                    spec_ngram: int = 3, spec_table=None, repetition_penalty: float | None = None,
                    presence_penalty: float | None = None, frequency_penalty: float | None = None,
-                   logprobs: int | None = None):
+                   logprobs: int | None = None, quantize_prefill: bool = False):
     """Generate for a list of prompts of unequal lengths as one batch.
+
+    ``quantize_prefill=True``: as in ``generate_cached``; every prompt pass, a queue's admissions included, runs on
+    the quantized weights.
 
     ``logprobs=N`` (0 .. 8; None: off): as in ``generate_cached``; the call returns ``(results, records)``,
     ``records[i]`` the ``ops.LogProbs`` of prompt i's new tokens (``token`` [n_i], ``top_ids`` / ``top`` [n_i, N]),
@@ -1639,6 +1699,7 @@ def generate_batch(model, prompts, max_new_tokens, temperature: float = 1.0, top
     prompts, budgets, queue, fit, P, mode = _batch_plan(model, prompts, max_new_tokens, quantize, kv_quantize,
                                                         shared_prompt, shared_prefix, batch_size, speculate,
                                                         spec_ngram, smp.penalties is not None, logprobs)
+    mode = _quantized_prefill(mode, quantize_prefill)
     logprobs = mode["logprobs"]
     if budgets is None:
         outs = [p.view(-1) for p in given]
@@ -1649,7 +1710,8 @@ def generate_batch(model, prompts, max_new_tokens, temperature: float = 1.0, top
         if i not in fit:  # alone through ``generate_cached``: the recompute loop, or a decoder of its own
             y = generate_cached(model, p[None], budgets[i], smp._replace(stop_token=None), use_graph=use_graph,
                                 quantize=quantize, kv_quantize=kv_quantize, speculate=speculate, spec_ngram=spec_ngram,
-                                spec_table=None if spec_table is None else [spec_table[i]], logprobs=logprobs)
+                                spec_table=None if spec_table is None else [spec_table[i]], logprobs=logprobs,
+                                **({"quantize_prefill": True} if quantize_prefill else {}))
             if logprobs is not None:
                 y, rec = y
             outs[i] = _result(p, y[0][p.numel():], smp.stop_token)

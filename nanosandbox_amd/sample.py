@@ -16,7 +16,8 @@ batch of unequal lengths, ``--stop_token=ID`` ends a sample at that token
 (``--top_k=0``: no top-k); on the GPU the selection runs inside the sampling kernel.
 ``--quantize=int8`` decodes with int8 weight-only linears (per-row scales; the KV-cache
 path only, so it refuses ``--kv_cache=False``); ``--quantize=mxfp4`` with OCP MXFP4 ones
-(4-bit elements, one scale byte per 32; the same refusal).  ``--kv_quantize=int8`` keeps the KV caches
+(4-bit elements, one scale byte per 32; the same refusal); with either, ``--quantize_prefill=True`` runs the
+prompt on the quantized weights too and keeps no bf16 copy of the block linears.  ``--kv_quantize=int8`` keeps the KV caches
 as int8 rows with one scale each (the same refusal).  ``--shared_prompt=True`` with
 ``--sample_batch=N`` encodes and caches the prompt once for the N rows of a batch and once
 for all rounds (``Decoder(shared_prompt=True)``); it refuses ``--prompts_file``,
@@ -90,6 +91,7 @@ SAMPLE_DEFAULTS = dict(
     prompts_file="",  # one prompt per line, generated as one ragged batch per sample round (start is ignored)
     stop_token=-1,  # token id that ends a sample (printed text ends before it); -1: none
     quantize="",  # "int8" / "mxfp4": weight-only decoding on the KV-cache path (Decoder(quantize=...)); "": off
+    quantize_prefill=False,  # with quantize: the prompt on the quantized weights, no bf16 copy of the block linears
     kv_quantize="",  # "int8": int8 KV caches, one scale per cache row (Decoder(kv_quantize="int8")); "": off
     shared_prompt=False,  # sample_batch > 1: encode and cache the prompt once for the batch (Decoder(shared_prompt=True))
     shared_prefix=False,  # prompts_file / sample_batch > 1: encode and cache the prompts' common prefix once for the batch
@@ -150,6 +152,11 @@ def _score_file(model, c, encode, device):
     return outs
 
 
+def _quantize_prefill(c):
+    """The ``quantize_prefill`` keyword of a call, passed only when the key is on."""
+    return dict(quantize_prefill=True) if c["quantize_prefill"] else {}
+
+
 def _beam_search(model, c, encode, decode, start, device):
     """num_beams: every prompt (the lines of prompts_file, or start) through ``GPT.generate_beam`` on one decoder."""
     from .runtime.decode import beam_decoder
@@ -192,7 +199,7 @@ def _serve_queue(model, c, encode, decode, start, device):
     ys = model.generate_batch(prompts, c["max_new_tokens"], temperature=c["temperature"], top_k=c["top_k"],
                               stop_token=stop, top_p=c["top_p"], min_p=c["min_p"], quantize=c["quantize"] or None,
                               kv_quantize=c["kv_quantize"] or None, shared_prompt=bool(c["shared_prompt"]),
-                              batch_size=c["serve_batch"], **_penalties(c), **_logprobs(c))
+                              batch_size=c["serve_batch"], **_penalties(c), **_logprobs(c), **_quantize_prefill(c))
     ys, recs = ys if _logprobs(c) else (ys, None)
     outs = []
     for i, (p, y) in enumerate(zip(prompts, ys)):
@@ -234,6 +241,7 @@ def _generate_batches(model, c, encode, decode, start, device):
                     mode.update(speculate=c["speculate"], spec_ngram=c["spec_ngram"])
                 mode.update(_penalties(c))
                 mode.update(_logprobs(c))
+                mode.update(_quantize_prefill(c))
                 if B not in decs:  # a shared prompt / prefix stays cached in it: later rounds do not encode it again
                     decs[B] = batch_decoder(model, prompts, c["max_new_tokens"], **mode)
                 ys = model.generate_batch(prompts, c["max_new_tokens"], temperature=c["temperature"], top_k=c["top_k"],
@@ -294,6 +302,10 @@ def main(argv=None):
     if c["quantize"] and not c["kv_cache"]:
         raise ValueError("--quantize needs the KV-cache path: the recompute loop (--kv_cache=False) runs the "
                          "unquantized model")
+    if c["quantize_prefill"] and not c["quantize"]:
+        raise ValueError("--quantize_prefill runs the prompt on the quantized weights: it needs --quantize")
+    if c["quantize_prefill"] and c["num_beams"]:
+        raise ValueError("--quantize_prefill is not threaded through the beam search: drop --num_beams")
     if c["kv_quantize"] not in ("", "int8"):
         raise ValueError(f"kv_quantize must be '' or 'int8', got {c['kv_quantize']!r}")
     if c["kv_quantize"] and not c["kv_cache"]:
@@ -391,14 +403,15 @@ def main(argv=None):
         # built once, not per sample
         from .runtime.decode import cached_decoder
         dec = cached_decoder(model, x, c["max_new_tokens"], quantize=quantize, kv_quantize=kv_quantize, **spec,
-                             **_penalties(c), **_logprobs(c))
+                             **_penalties(c), **_logprobs(c), **_quantize_prefill(c))
     try:
         with torch.no_grad():
             for _ in range(c["num_samples"]):
                 if dec is not None:
                     y = model.generate_cached(x, c["max_new_tokens"], temperature=c["temperature"], top_k=c["top_k"],
                                               decoder=dec, top_p=c["top_p"], min_p=c["min_p"], quantize=quantize,
-                                              kv_quantize=kv_quantize, **spec, **_penalties(c), **_logprobs(c))
+                                              kv_quantize=kv_quantize, **spec, **_penalties(c), **_logprobs(c),
+                                              **_quantize_prefill(c))
                 else:
                     y = model.generate(x, c["max_new_tokens"], temperature=c["temperature"], top_k=c["top_k"],
                                        top_p=c["top_p"], min_p=c["min_p"], **_penalties(c), **_logprobs(c))

@@ -63,6 +63,12 @@ a ``Decoder(logprobs=N)``, whose step records every drawn token's log-probabilit
 instead of ``nsa_wide_gemm``: the path before the wide kernel, launch for launch.
 ``--tall_ab`` adds ``graph_short`` / ``rows_short`` in the same way: ``ops.functional.TALL_MAX_ROWS`` lowered to
 ``WIDE_MAX_ROWS``, so batches of 65 .. 256 rows take ``linear`` instead of ``nsa_tall_gemm``.
+``--quantize_prefill`` (with ``--quantize`` and the ``rows`` mode) adds ``rows_int8_qp`` / ``rows_mxfp4_qp`` right after
+``rows_int8`` / ``rows_mxfp4``: the same settings on a ``Decoder(quantize_prefill=True)``, whose prompt passes run on the
+quantized weights (``nsa_quant_gemm_*``) and which keeps no bf16 copy of the block linears.  The quantized rows lines
+then carry ``ttft_ms`` and ``decoder_mb`` (bytes allocated by the decoder's construction: caches, shadows and
+quantized weights), and the ``_qp`` lines ``expected_drop_mb``, the bf16 size of the block linears
+(2 * 12 * n_layer * n_embd^2 bytes) that ``decoder_mb`` must fall by.  Batches above 16 need ``NSA_QUANT_MAX_ROWS=64``.
 """
 
 import argparse
@@ -79,6 +85,7 @@ from nanosandbox_amd.ops import functional  # noqa: E402
 from nanosandbox_amd.runtime.decode import Decoder  # noqa: E402
 
 SMP = dict(top_k=200, top_p=None, min_p=None)  # the sampling settings of every mode (--top_k / --top_p / --min_p)
+LAST = {}  # run_rows: decoder_mb, what the last decoder's construction allocated
 PEN = {}  # --penalties: the three penalty keywords of the _pen modes
 DIMS = {"gpt2": (12, 12, 768), "gpt2-medium": (24, 16, 1024), "gpt2-large": (36, 20, 1280), "gpt2-xl": (48, 25, 1600)}
 
@@ -110,18 +117,23 @@ def ragged_lengths(B, prompt):
     return [prompt if B == 1 else lo + (prompt - lo) * b // (B - 1) for b in range(B)]
 
 
-def run_rows(model, idx, new, lengths=None, quantize=None, kv_quantize=None, shared=False, pen=False, lp=None):
+def run_rows(model, idx, new, lengths=None, quantize=None, kv_quantize=None, shared=False, pen=False, lp=None,
+             qp=False):
     """The graph mode on a per_row decoder: equal lengths, or (lengths) a ragged batch; shared:
     a shared_prompt decoder, every row continuing idx[0].  Returns (seconds of the timed steps,
     seconds from the start of the prefill to the first drawn token).  pen: a penalising decoder,
     sampling with --penalties.  lp: a decoder that records log-probabilities and lp alternatives."""
     B = idx.shape[0]
+    qpk = dict(quantize_prefill=True) if qp else {}  # qp: the prompt passes on the quantized weights
+    torch.cuda.synchronize()
+    alloc0 = torch.cuda.memory_allocated()
     if shared:  # slots for the capture step and the timed ones
         dec = Decoder(model, B, use_graph=True, per_row=True, quantize=quantize, shared_prompt=True, max_new=new + 1,
-                      penalize=pen, logprobs=lp)
+                      penalize=pen, logprobs=lp, **qpk)
     else:
         dec = Decoder(model, B, use_graph=True, per_row=True, quantize=quantize, kv_quantize=kv_quantize,
-                      penalize=pen, logprobs=lp)
+                      penalize=pen, logprobs=lp, **qpk)
+    LAST["decoder_mb"] = round((torch.cuda.memory_allocated() - alloc0) / 2 ** 20, 1)
     smp = dict(SMP, **PEN) if pen else SMP
     lens = None if lengths is None else torch.tensor(lengths, device=idx.device)
     torch.cuda.synchronize()
@@ -350,6 +362,9 @@ def main():
     ap.add_argument("--tall_ab", action="store_true",
                     help="add twins of the graph and rows modes with the tall decode GEMM off (graph_short, "
                          "rows_short)")
+    ap.add_argument("--quantize_prefill", action="store_true",
+                    help="add twins of the quantized rows modes whose prompt runs on the quantized weights "
+                         "(rows_int8_qp, rows_mxfp4_qp); ttft_ms and decoder_mb on the quantized rows lines")
     ap.add_argument("--beams", default="", help="W[,W ...]: only beam search of these widths, interleaved with "
                     "shared-prompt sampling at batch W (the same linears; the select and the gather differ): "
                     "medians of --repeat runs")
@@ -390,6 +405,8 @@ def main():
         modes = [t for m in modes for t in ([m, f"{m}_narrow"] if m in ("graph", "rows") else [m])]
     if a.tall_ab:  # each short twin right after its mode
         modes = [t for m in modes for t in ([m, f"{m}_short"] if m in ("graph", "rows") else [m])]
+    if a.quantize_prefill:  # each twin right after its quantized rows mode
+        modes = [t for m in modes for t in ([m, f"{m}_qp"] if m in ("rows_int8", "rows_mxfp4") else [m])]
     if a.shared_prefix:
         modes = ["prefix_rows", "prefix_shared"]
     block_size = GPTConfig().block_size
@@ -471,10 +488,14 @@ def main():
                     elif base in ("rows", "ragged"):
                         n = a.new
                         lens = ragged_lengths(B, a.prompt) if base == "ragged" else None
-                        run_rows(model, idx, 4, lens, qz, kvq, "shared" in sfx, "pen" in sfx, lp)
-                        dt, t1 = run_rows(model, idx, n, lens, qz, kvq, "shared" in sfx, "pen" in sfx, lp)
-                        if a.shared_prompt:
+                        run_rows(model, idx, 4, lens, qz, kvq, "shared" in sfx, "pen" in sfx, lp, "qp" in sfx)
+                        dt, t1 = run_rows(model, idx, n, lens, qz, kvq, "shared" in sfx, "pen" in sfx, lp, "qp" in sfx)
+                        if a.shared_prompt or (a.quantize_prefill and qz):
                             ttft = {"ttft_ms": round(t1 * 1e3, 3)}
+                        if a.quantize_prefill and qz:
+                            ttft["decoder_mb"] = LAST["decoder_mb"]
+                            if "qp" in sfx:
+                                ttft["expected_drop_mb"] = round(2 * 12 * L * C * C / 2 ** 20, 1)
                     elif mode == "recompute":
                         run_recompute(model, idx, 2)  # warm-up (tuner, allocator)
                         n = a.recompute_new
