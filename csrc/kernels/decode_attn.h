@@ -1,7 +1,7 @@
 // The flash-decoding attention pieces shared by decode.hip (one cache per batch row) and
 // decode_shared.hip (one prompt cache for the whole batch plus per-row caches): the body that
-// turns one 256-key chunk of one (row, head)'s cache into a partial (m, l, o[64]), the int8
-// cache-row quantizer it appends with, and the kernel that combines any number of partials.
+// turns one 256-key chunk of one (row, head)'s cache into a partial (m, l, o[64]), and the
+// kernel that combines any number of partials.
 #pragma once
 
 #include "decode_rows.h"
@@ -9,19 +9,6 @@
 #include <math.h>
 
 namespace {
-
-// One cache row's int8 form: scale = absmax / 127 (1 for an all-zero row), q = rint(x / scale)
-// with a correctly rounded fp32 division (the build uses no fast-math), round-half-to-even and
-// a clamp to +-127: ops.quantize_cache_rows bit for bit.
-__device__ __forceinline__ float kv8_scale(float absmax) { return absmax > 0.0f ? absmax / 127.0f : 1.0f; }
-__device__ __forceinline__ float kv8_quant(float x, float scale) {
-  return fminf(fmaxf(rintf(x / scale), -127.0f), 127.0f);
-}
-// four integer-valued floats as the bytes of one dword (byte 0 first)
-__device__ __forceinline__ uint32_t kv8_pack4(float a, float b, float c, float d) {
-  return ((uint32_t)(int)a & 0xffu) | (((uint32_t)(int)b & 0xffu) << 8) | (((uint32_t)(int)c & 0xffu) << 16) |
-         ((uint32_t)(int)d << 24);
-}
 
 // per-row scales of an int8 cache (fp32 [B, H, Tmax] each); nothing for a bf16 cache
 template <typename CT>

@@ -56,6 +56,20 @@ __device__ __forceinline__ void unpack8q(uint32_t lo, uint32_t hi, float (&f)[8]
   }
 }
 
+// One row's int8 form (the int8 KV-cache rows of decode.hip, the quantized activations of
+// a8_gemm.hip): scale = absmax / 127 (1 for an all-zero row), q = rint(x / scale) with a correctly
+// rounded fp32 division (the build uses no fast-math), round-half-to-even and a clamp to +-127:
+// ops.quantize_cache_rows bit for bit.
+__device__ __forceinline__ float kv8_scale(float absmax) { return absmax > 0.0f ? absmax / 127.0f : 1.0f; }
+__device__ __forceinline__ float kv8_quant(float x, float scale) {
+  return fminf(fmaxf(rintf(x / scale), -127.0f), 127.0f);
+}
+// four integer-valued floats as the bytes of one dword (byte 0 first)
+__device__ __forceinline__ uint32_t kv8_pack4(float a, float b, float c, float d) {
+  return ((uint32_t)(int)a & 0xffu) | (((uint32_t)(int)b & 0xffu) << 8) | (((uint32_t)(int)c & 0xffu) << 16) |
+         ((uint32_t)(int)d << 24);
+}
+
 // Single-row decode linear with its input's producer in the prologue: every workgroup
 // builds the row x[K] (bf16-rounded, in LDS) itself, then streams its NC weight rows:
 //   PRO_LN     s = res + branch (fp32; written to res_out by workgroup 0), x = LN(s)

@@ -58,9 +58,10 @@ def _run(cmd):
 # softmax's adjacent f32 multiplies / adds into v_pk_*_f32, an anti-lever beside MFMAs
 # (MI355X_MICROARCH.md 'price of one filler'; A/B: scripts/attn_ab.py against a variant
 # library built with file_flags={}).
-FILE_FLAGS = {"flash_attn.hip": ["-fno-slp-vectorize"], "flash_attn_f16.hip": ["-fno-slp-vectorize"],
+FILE_FLAGS = {"a8_gemm.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+              "flash_attn.hip": ["-fno-slp-vectorize"], "flash_attn_f16.hip": ["-fno-slp-vectorize"],
               # no packed fp32 arithmetic at all in the beam kernels, the wide (bf16 and quantized) and tall decode
-              # GEMMs, the MXFP4 kernels and the quantized-weight GEMM
+              # GEMMs, the MXFP4 kernels and the quantized-weight GEMMs
               "decode_beam.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
               "decode_mx4.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
               "decode_tall.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],

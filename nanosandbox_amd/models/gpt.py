@@ -447,7 +447,8 @@ class GPT(nn.Module):
     def generate_cached(self, idx, max_new_tokens, temperature=1.0, top_k=None, use_graph=None, decoder=None,
                         top_p=None, min_p=None, quantize=None, kv_quantize=None, shared_prompt=False,
                         speculate=None, spec_ngram=3, spec_table=None, repetition_penalty=None,
-                        presence_penalty=None, frequency_penalty=None, logprobs=None, quantize_prefill=False):
+                        presence_penalty=None, frequency_penalty=None, logprobs=None, quantize_prefill=False,
+                        prefill_act=None):
         """``generate`` with per-layer KV caches: the prompt is encoded once and every
         new token runs one position through the model (a replayed HIP graph on the GPU;
         ``runtime/decode.py``).  Same sampling; falls back to ``generate`` when prompt +
@@ -462,11 +463,14 @@ class GPT(nn.Module):
         ``logprobs=N`` (0 .. 8; None: off): returns ``(tokens, ops.LogProbs)`` over the new tokens, as
         ``generate`` does, recorded by one more launch inside the captured step; not with ``speculate``.
         ``quantize_prefill=True`` (with ``quantize``): the prompt runs on the quantized weights too and no bf16
-        copy of the block linears is kept."""
+        copy of the block linears is kept; ``prefill_act="int8"`` (with both, int8 only): its block linears
+        quantize their activations per token too (``ops.a8_linear``)."""
         from ..runtime.decode import generate_cached
         lpk = {} if logprobs is None else dict(logprobs=logprobs)
         if quantize_prefill:
             lpk["quantize_prefill"] = True
+        if prefill_act:
+            lpk["prefill_act"] = prefill_act
         return generate_cached(self, idx, max_new_tokens, temperature=temperature, top_k=top_k, use_graph=use_graph,
                                decoder=decoder, top_p=top_p, min_p=min_p, quantize=quantize,
                                kv_quantize=kv_quantize, shared_prompt=shared_prompt, speculate=speculate,
@@ -478,7 +482,7 @@ class GPT(nn.Module):
                        decoder=None, top_p=None, min_p=None, quantize=None, kv_quantize=None, shared_prompt=False,
                        shared_prefix=False, batch_size=None, speculate=None, spec_ngram=3, spec_table=None,
                        repetition_penalty=None, presence_penalty=None, frequency_penalty=None, logprobs=None,
-                       quantize_prefill=False):
+                       quantize_prefill=False, prefill_act=None):
         """``generate_cached`` for a list of 1-D prompts of unequal lengths, decoded as one
         batch with a position per row; returns a list of 1-D tensors (prompt + new tokens).
         A row that draws ``stop_token`` ends with it; the others get exactly
@@ -492,11 +496,14 @@ class GPT(nn.Module):
         ``generate_cached``.  ``repetition_penalty`` / ``presence_penalty`` / ``frequency_penalty``: as in
         ``generate_cached``, every row by the counts of its own text.  ``logprobs=N``: returns ``(results,
         records)``, one ``ops.LogProbs`` per prompt over exactly its new tokens, the stop token included.
-        ``quantize_prefill=True``: as in ``generate_cached``, a queue's admissions included."""
+        ``quantize_prefill=True`` / ``prefill_act="int8"``: as in ``generate_cached``, a queue's admissions
+        included."""
         from ..runtime.decode import generate_batch
         lpk = {} if logprobs is None else dict(logprobs=logprobs)
         if quantize_prefill:
             lpk["quantize_prefill"] = True
+        if prefill_act:
+            lpk["prefill_act"] = prefill_act
         return generate_batch(self, prompts, max_new_tokens, temperature=temperature, top_k=top_k,
                               stop_token=stop_token, use_graph=use_graph, decoder=decoder, top_p=top_p, min_p=min_p,
                               quantize=quantize, kv_quantize=kv_quantize, shared_prompt=shared_prompt,

@@ -162,6 +162,12 @@ _SIGNATURES = {
     "nsa_quant_gemm_mx4": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p],
     "nsa_quant_gemm_q8_chunk": [],
     "nsa_quant_gemm_mx4_chunk": [],
+    # W8A8 prompt GEMM (csrc/kernels/a8_gemm.hip): x, q, sx, M, K / xq, sx, Wq, sw, bias, y, M, N, K, act
+    "nsa_quantize_act_rows": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p],
+    "nsa_a8_gemm": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                    c_void_p],
+    "nsa_a8_gemm_chunk": [],
+    "nsa_quantize_act_rows_resident": [],
     # int8 KV caches (csrc/kernels/decode.hip): (q, scale) per cache where the bf16 entry point takes kc / vc
     "nsa_kv_append_kv8": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                           c_int, c_int, c_void_p],

@@ -1809,6 +1809,61 @@ def quant_linear(x, w, b=None, gelu: bool = False):
         return GeluFn.apply(y) if gelu else y
 
 
+# A8_CHUNK of csrc/kernels/a8_gemm.hip: k per LDS chunk of X; QUANT_ACT_RESIDENT_K: the widest row
+# nsa_quantize_act_rows reads once
+A8_GEMM_CHUNK = 256
+QUANT_ACT_RESIDENT_K = 8192
+
+
+def quantize_act_rows(x):
+    """Dynamic per-token int8 of the activations ``x`` [..., K] -> (q int8 [..., K], scale fp32 [...]):
+    ``quantize_cache_rows``' rule over a whole row.  GPU, bf16 and K % 16 == 0: ``nsa_quantize_act_rows``
+    (csrc/kernels/a8_gemm.hip; a row is read once up to K = 8192), bit for bit the torch rule; anything else:
+    ``quantize_cache_rows`` itself."""
+    K = x.shape[-1]
+    if x.is_cuda and x.dtype == BF16 and K % 16 == 0 and x.numel() > 0:
+        rows = x.numel() // K
+        x2 = x.detach().reshape(rows, K).contiguous()
+        q = torch.empty(rows, K, device=x.device, dtype=torch.int8)
+        sx = torch.empty(rows, device=x.device, dtype=F32)
+        _lib.call("nsa_quantize_act_rows", _lib.ptr(x2), _lib.ptr(q), _lib.ptr(sx), rows, K, _lib.stream())
+        return q.view(x.shape), sx.view(x.shape[:-1])
+    return tuple(quantize_cache_rows(x))
+
+
+def a8_linear(x, w, b=None, gelu: bool = False):
+    """The W8A8 prompt linear: act(f32(xq @ w.q^T) * sx[:, None] * w.scale + b), (xq, sx) =
+    ``quantize_act_rows(x)``, ``w`` a ``QuantWeight``: int8 activations (one scale per token) against int8
+    weights, the sum an exact integer (``Decoder(..., prefill_act="int8")``).  The epilogue is the op's
+    definition: the integer sum to fp32, times sx, times w.scale, plus b, each rounded to fp32 on its own, then
+    the exact GELU, then x's dtype.  GPU, bf16 x and K % 64 == 0: the quantizer and one ``nsa_a8_gemm`` launch
+    (csrc/kernels/a8_gemm.hip: v_mfma_i32_32x32x32_i8, no workspace, deterministic), any N, bf16 out.  Anything
+    else (CPU, fp32, other K) runs the same arithmetic in torch (the integer sum as a float64 matmul, exact
+    below 2^53): the reference the kernel matches bit for bit without GELU.  Inference only."""
+    if not isinstance(w, QuantWeight):
+        raise TypeError(f"a8_linear takes a QuantWeight, got {type(w).__name__}")
+    N, K = w.shape
+    assert x.shape[-1] == K, f"x has {x.shape[-1]} columns, the weight {K}"
+    if x.is_cuda and x.dtype == BF16 and K % 64 == 0 and x.numel() > 0:
+        rows = x.numel() // K
+        xq, sx = quantize_act_rows(x.detach().reshape(rows, K))
+        bc = compute_weight(b, BF16) if b is not None else None
+        y = torch.empty(rows, N, device=x.device, dtype=BF16)
+        _lib.call("nsa_a8_gemm", _lib.ptr(xq), _lib.ptr(sx), _lib.ptr(w.q), _lib.ptr(w.scale), _lib.ptr(bc),
+                  _lib.ptr(y), rows, N, K, 1 if gelu else 0, _lib.stream())
+        return y.view(*x.shape[:-1], N)
+    with torch.no_grad():
+        xq, sx = quantize_cache_rows(x)
+        acc = (xq.double() @ w.q.double().t()).float()  # integers below 2^31: exact, then one rounding to fp32
+        y = acc * sx[..., None]
+        y = y * w.scale
+        if b is not None:
+            y = y + b.detach().to(x.dtype).float()
+        if gelu:
+            y = F.gelu(y)
+        return y.to(x.dtype)
+
+
 def decode_linear_ln(res, branch, ln_w, ln_b, w, b=None, gelu: bool = False, out_f32: bool = False,
                      out_dtype=None, pos_inc=None):
     """One decode row through residual add + LayerNorm + linear:

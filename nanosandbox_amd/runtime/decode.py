@@ -51,6 +51,12 @@ dequantized shadow: the embedding gather and the prompt's last-position head rea
 launches and graphs.  Without ``quantize`` the keyword raises ValueError; on the CPU or in fp32 the decoder runs
 the dequantized model through ``quant_linear``'s fallback.  ``fits`` compares the flag and ``release()`` puts back
 whatever shadows the parameters had.  Without the keyword every launch, graph key, shadow and result is what it was.
+``Decoder(..., quantize="int8", quantize_prefill=True, prefill_act="int8")`` (a further opt-in) also quantizes the
+prompt's activations: the four block linears of ``_prefill_layers`` become ``ops.a8_linear`` (W8A8: one dynamic int8
+scale per token, ``nsa_quantize_act_rows``, then ``nsa_a8_gemm`` on the integer MFMA with an exact int32 sum), a numerics
+trade made only in the compute-bound prompt passes.  Steps, the lm_head, the captured graph and its key are untouched;
+``fits`` compares the field.  It needs ``quantize_prefill=True`` and ``quantize="int8"`` (ValueError otherwise, and for
+any value but None, "" and "int8"); on the CPU or in fp32 ``a8_linear``'s fallback runs the same arithmetic in torch.
 ``Decoder(..., kv_quantize="int8")`` keeps the caches as int8 rows with one fp32 scale per
 row (``ops.QuantCache``: 68 bytes per K or V row instead of 128, so a step reads 0.53x the
 cache bytes and the caches take 0.53x the memory).  The prompt goes through flash attention
@@ -300,11 +306,12 @@ class Decoder:
                  per_row: bool = False, quantize: str | None = None, kv_quantize: str | None = None,
                  shared_prompt: bool = False, max_new: int | None = None, speculate: int | None = None,
                  spec_ngram: int = 3, penalize: bool = False, logprobs: int | None = None,
-                 num_beams: int | None = None, quantize_prefill: bool = False):
+                 num_beams: int | None = None, quantize_prefill: bool = False, prefill_act: str | None = None):
         if quantize_prefill and not quantize:
             raise ValueError("quantize_prefill runs the prompt on the quantized weights: it needs quantize='int8' or "
                              "'mxfp4'")
         self.quantize_prefill = bool(quantize_prefill)
+        self.prefill_act = _check_prefill_act(prefill_act, quantize, quantize_prefill)
         self.K, self.N, logprobs = _check(quantize, kv_quantize, shared_prompt, speculate=speculate,
                                           spec_ngram=spec_ngram, penalize=penalize, logprobs=logprobs,
                                           rows=batch_size, max_new=max_new, beams=num_beams)
@@ -484,19 +491,20 @@ class Decoder:
 
     def fits(self, batch_size, per_row=False, quantize=None, kv_quantize=None, shared_prompt=False,
              max_new=None, speculate=None, spec_ngram=3, penalize=False, logprobs=None, num_beams=None,
-             quantize_prefill=False) -> bool:
+             quantize_prefill=False, prefill_act=None) -> bool:
         """Whether a call that needs ``Decoder(model, batch_size, per_row=..., ...)`` can run on this
         one: the same rows and form, (shared) row caches of at least ``max_new`` slots, and the same
         number of drafted tokens and n-gram length (speculative), and a count table if and only if
         the call penalises, and the log-probability buffers of the call's N alternatives, or none, and the
-        same kind of prompt pass (``quantize_prefill``)."""
+        same kind of prompt pass (``quantize_prefill``, ``prefill_act``)."""
         K = int(speculate or 0)
         return (self.B == batch_size and self.per_row == bool(per_row or K) and self.quantize == quantize
                 and self.kv_quantize == kv_quantize and self.shared == bool(shared_prompt)
                 and (not self.shared or self.R >= (max_new or self.T))
                 and self.K == K and (not K or self.N == int(spec_ngram))
                 and (self.cnt is not None) == bool(penalize) and self.logprobs == logprobs
-                and self.W == int(num_beams or 0) and self.quantize_prefill == bool(quantize_prefill))
+                and self.W == int(num_beams or 0) and self.quantize_prefill == bool(quantize_prefill)
+                and self.prefill_act == (prefill_act or ""))
 
     def _quantize_weights(self):
         """int8 / mxfp4 mode: quantize every linear weight and the tied lm_head / wte table, and point
@@ -568,13 +576,15 @@ class Decoder:
         prefix, and every query also attends over prompt-cache rows 0 .. P - 1.  ``rows``
         (``admit``; int64 [n] on the device): row j of x is cache row ``rows[j]``.  ``quantize_prefill``: the
         four linears of a block run on the quantized weights (``ops.quant_linear``, bias and GELU in its
-        epilogue) instead of ``ops.linear`` / the MLP module on bf16 shadows."""
+        epilogue) instead of ``ops.linear`` / the MLP module on bf16 shadows; with ``prefill_act`` through
+        ``ops.a8_linear``, which quantizes their input rows as well."""
         kc, vc = kc or self.kc, vc or self.vc
         if self.quantize_prefill:
             W = self._w
+            qlin = ops.a8_linear if self.prefill_act else ops.quant_linear
 
             def lin(layer, h, gelu=False):
-                return ops.quant_linear(h, W(layer.weight), layer.bias, gelu=gelu)
+                return qlin(h, W(layer.weight), layer.bias, gelu=gelu)
         else:
             def lin(layer, h, gelu=False):
                 return ops.linear(h, layer.weight, layer.bias)
@@ -1278,15 +1288,30 @@ def _mode(B, per_row=False, quantize=None, kv_quantize=None, slots=None, spec=(0
                 penalize=bool(penalize), logprobs=logprobs, num_beams=beams)
 
 
-def _quantized_prefill(mode, quantize_prefill):
-    """``mode`` for a call with ``quantize_prefill``: the same decoder with the prompt passes on the quantized
-    weights; ValueError where the call does not quantize.  Without the keyword ``mode`` itself."""
+def _check_prefill_act(prefill_act, quantize, quantize_prefill):
+    """``prefill_act`` as "" or "int8"; ValueError for any other value, and for "int8" on anything but an int8
+    decoder with ``quantize_prefill`` (the MXFP4 counterpart does not exist)."""
+    if prefill_act not in (None, "", "int8"):
+        raise ValueError(f"prefill_act must be None, '' or 'int8', got {prefill_act!r}")
+    if prefill_act and not quantize_prefill:
+        raise ValueError("prefill_act quantizes the activations of the quantized prompt passes: it needs "
+                         "quantize_prefill=True")
+    if prefill_act and quantize != "int8":
+        raise ValueError(f"prefill_act='int8' runs on int8 weights: it needs quantize='int8', got {quantize!r}")
+    return prefill_act or ""
+
+
+def _quantized_prefill(mode, quantize_prefill, prefill_act=None):
+    """``mode`` for a call with ``quantize_prefill`` (and ``prefill_act``): the same decoder with the prompt passes
+    on the quantized weights (and int8 activations); ValueError where the call does not quantize.  Without the
+    keywords ``mode`` itself."""
+    act = _check_prefill_act(prefill_act, mode["quantize"], quantize_prefill)
     if not quantize_prefill:
         return mode
     if not mode["quantize"]:
         raise ValueError("quantize_prefill runs the prompt on the quantized weights: it needs quantize='int8' or "
                          "'mxfp4'")
-    return dict(mode, quantize_prefill=True)
+    return dict(mode, quantize_prefill=True, **({"prefill_act": act} if act else {}))
 
 
 def _build(model, mode, use_graph=None):
@@ -1349,7 +1374,7 @@ def _cached_mode(model, idx, max_new_tokens, quantize, kv_quantize, shared_promp
 
 def cached_decoder(model, idx, max_new_tokens, use_graph=None, quantize=None, kv_quantize=None, shared_prompt=False,
                    speculate=None, spec_ngram=3, repetition_penalty=None, presence_penalty=None,
-                   frequency_penalty=None, logprobs=None, quantize_prefill=False):
+                   frequency_penalty=None, logprobs=None, quantize_prefill=False, prefill_act=None):
     """The Decoder this ``generate_cached`` call would build, for a caller that keeps it across
     calls (``decoder=``) and releases it.  A call that runs on none (no new tokens, or the
     recompute loop) gets the ordinary one all the same, as ``sample.py`` always has: building it
@@ -1358,7 +1383,7 @@ def cached_decoder(model, idx, max_new_tokens, use_graph=None, quantize=None, kv
     pen = sampling_penalties(repetition_penalty, presence_penalty, frequency_penalty) is not None
     return _build(model, _quantized_prefill(_cached_mode(model, idx, max_new_tokens, quantize, kv_quantize,
                                                          shared_prompt, speculate, spec_ngram, pen, logprobs)[0],
-                                            quantize_prefill), use_graph)
+                                            quantize_prefill, prefill_act), use_graph)
 
 
 @torch.no_grad()
@@ -1370,11 +1395,13 @@ def generate_cached(model, idx: torch.Tensor, max_new_tokens: int, temperature: 
                     speculate: int | None = None, spec_ngram: int = 3, spec_table=None,
                     repetition_penalty: float | None = None, presence_penalty: float | None = None,
                     frequency_penalty: float | None = None, logprobs: int | None = None,
-                    quantize_prefill: bool = False):
+                    quantize_prefill: bool = False, prefill_act: str | None = None):
     """``model.generate`` with KV caches: same sampling, one token's forward per new token.
 
     ``quantize_prefill=True`` (with ``quantize``; ValueError without): the prompt runs on the quantized weights too
     and the decoder keeps no bf16 copy of the block linears (``Decoder(..., quantize_prefill=True)``).
+    ``prefill_act="int8"`` (with ``quantize="int8"`` and ``quantize_prefill=True``; ValueError otherwise): the prompt's
+    block linears also quantize their activations per token (``ops.a8_linear``).
 
     ``logprobs=N`` (0 .. 8; None: off): the call returns ``(tokens, ops.LogProbs)``, the second covering
     exactly the new tokens: ``token`` [B, n] is the log-probability of every drawn token under the
@@ -1417,7 +1444,7 @@ def generate_cached(model, idx: torch.Tensor, max_new_tokens: int, temperature: 
     smp = sampling(temperature, top_k, None, top_p, min_p, repetition_penalty, presence_penalty, frequency_penalty)
     mode, cached = _cached_mode(model, idx, max_new_tokens, quantize, kv_quantize, shared_prompt, speculate, spec_ngram,
                                 smp.penalties is not None, logprobs)
-    mode = _quantized_prefill(mode, quantize_prefill)
+    mode = _quantized_prefill(mode, quantize_prefill, prefill_act)
     logprobs = mode["logprobs"]
     if max_new_tokens <= 0:
         return _with_records(idx, logprobs, lambda: _no_records(idx.shape[0], logprobs, idx.device))
@@ -1606,7 +1633,7 @@ def _batch_plan(model, prompts, max_new_tokens, quantize, kv_quantize, shared_pr
 def batch_decoder(model, prompts, max_new_tokens, use_graph=None, quantize=None, kv_quantize=None,
                   shared_prompt=False, shared_prefix=False, batch_size=None, speculate=None, spec_ngram=3,
                   repetition_penalty=None, presence_penalty=None, frequency_penalty=None, logprobs=None,
-                  quantize_prefill=False):
+                  quantize_prefill=False, prefill_act=None):
     """The Decoder this ``generate_batch`` call would build, for a caller that keeps it across
     calls (``decoder=``; a shared one then keeps the prompt or prefix too) and releases it.  A call
     that shares none (no new tokens, or no prompt that fits the cache) gets the ordinary one of a
@@ -1614,7 +1641,7 @@ def batch_decoder(model, prompts, max_new_tokens, use_graph=None, quantize=None,
     pen = sampling_penalties(repetition_penalty, presence_penalty, frequency_penalty) is not None
     mode = _batch_plan(model, prompts, max_new_tokens, quantize, kv_quantize, shared_prompt, shared_prefix, batch_size,
                        speculate, spec_ngram, pen, logprobs)[-1]
-    return _build(model, _quantized_prefill(mode, quantize_prefill), use_graph)
+    return _build(model, _quantized_prefill(mode, quantize_prefill, prefill_act), use_graph)
 
 
 @torch.no_grad()
@@ -1626,11 +1653,11 @@ def generate_batch(model, prompts, max_new_tokens, temperature: float = 1.0, top
                    shared_prefix: bool = False, batch_size: int | None = None, speculate: int | None = None,
                    spec_ngram: int = 3, spec_table=None, repetition_penalty: float | None = None,
                    presence_penalty: float | None = None, frequency_penalty: float | None = None,
-                   logprobs: int | None = None, quantize_prefill: bool = False):
+                   logprobs: int | None = None, quantize_prefill: bool = False, prefill_act: str | None = None):
     """Generate for a list of prompts of unequal lengths as one batch.
 
     ``quantize_prefill=True``: as in ``generate_cached``; every prompt pass, a queue's admissions included, runs on
-    the quantized weights.
+    the quantized weights; ``prefill_act="int8"``: on int8 activations as well.
 
     ``logprobs=N`` (0 .. 8; None: off): as in ``generate_cached``; the call returns ``(results, records)``,
     ``records[i]`` the ``ops.LogProbs`` of prompt i's new tokens (``token`` [n_i], ``top_ids`` / ``top`` [n_i, N]),
@@ -1699,7 +1726,7 @@ def generate_batch(model, prompts, max_new_tokens, temperature: float = 1.0, top
     prompts, budgets, queue, fit, P, mode = _batch_plan(model, prompts, max_new_tokens, quantize, kv_quantize,
                                                         shared_prompt, shared_prefix, batch_size, speculate,
                                                         spec_ngram, smp.penalties is not None, logprobs)
-    mode = _quantized_prefill(mode, quantize_prefill)
+    mode = _quantized_prefill(mode, quantize_prefill, prefill_act)
     logprobs = mode["logprobs"]
     if budgets is None:
         outs = [p.view(-1) for p in given]
@@ -1711,7 +1738,8 @@ def generate_batch(model, prompts, max_new_tokens, temperature: float = 1.0, top
             y = generate_cached(model, p[None], budgets[i], smp._replace(stop_token=None), use_graph=use_graph,
                                 quantize=quantize, kv_quantize=kv_quantize, speculate=speculate, spec_ngram=spec_ngram,
                                 spec_table=None if spec_table is None else [spec_table[i]], logprobs=logprobs,
-                                **({"quantize_prefill": True} if quantize_prefill else {}))
+                                **({"quantize_prefill": True} if quantize_prefill else {}),
+                                **({"prefill_act": prefill_act} if prefill_act else {}))
             if logprobs is not None:
                 y, rec = y
             outs[i] = _result(p, y[0][p.numel():], smp.stop_token)

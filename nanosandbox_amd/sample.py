@@ -17,7 +17,8 @@ batch of unequal lengths, ``--stop_token=ID`` ends a sample at that token
 ``--quantize=int8`` decodes with int8 weight-only linears (per-row scales; the KV-cache
 path only, so it refuses ``--kv_cache=False``); ``--quantize=mxfp4`` with OCP MXFP4 ones
 (4-bit elements, one scale byte per 32; the same refusal); with either, ``--quantize_prefill=True`` runs the
-prompt on the quantized weights too and keeps no bf16 copy of the block linears.  ``--kv_quantize=int8`` keeps the KV caches
+prompt on the quantized weights too and keeps no bf16 copy of the block linears (with ``--quantize=int8``,
+``--prefill_act=int8`` also quantizes the prompt's activations per token: W8A8 on the integer MFMA).  ``--kv_quantize=int8`` keeps the KV caches
 as int8 rows with one scale each (the same refusal).  ``--shared_prompt=True`` with
 ``--sample_batch=N`` encodes and caches the prompt once for the N rows of a batch and once
 for all rounds (``Decoder(shared_prompt=True)``); it refuses ``--prompts_file``,
@@ -92,6 +93,7 @@ SAMPLE_DEFAULTS = dict(
     stop_token=-1,  # token id that ends a sample (printed text ends before it); -1: none
     quantize="",  # "int8" / "mxfp4": weight-only decoding on the KV-cache path (Decoder(quantize=...)); "": off
     quantize_prefill=False,  # with quantize: the prompt on the quantized weights, no bf16 copy of the block linears
+    prefill_act="",  # "int8" (with quantize="int8" and quantize_prefill): int8 activations in the prompt passes; "": off
     kv_quantize="",  # "int8": int8 KV caches, one scale per cache row (Decoder(kv_quantize="int8")); "": off
     shared_prompt=False,  # sample_batch > 1: encode and cache the prompt once for the batch (Decoder(shared_prompt=True))
     shared_prefix=False,  # prompts_file / sample_batch > 1: encode and cache the prompts' common prefix once for the batch
@@ -153,8 +155,9 @@ def _score_file(model, c, encode, device):
 
 
 def _quantize_prefill(c):
-    """The ``quantize_prefill`` keyword of a call, passed only when the key is on."""
-    return dict(quantize_prefill=True) if c["quantize_prefill"] else {}
+    """The ``quantize_prefill`` / ``prefill_act`` keywords of a call, each passed only when its key is on."""
+    return dict(**(dict(quantize_prefill=True) if c["quantize_prefill"] else {}),
+                **(dict(prefill_act=c["prefill_act"]) if c["prefill_act"] else {}))
 
 
 def _beam_search(model, c, encode, decode, start, device):
@@ -304,6 +307,11 @@ def main(argv=None):
                          "unquantized model")
     if c["quantize_prefill"] and not c["quantize"]:
         raise ValueError("--quantize_prefill runs the prompt on the quantized weights: it needs --quantize")
+    if c["prefill_act"] not in ("", "int8"):
+        raise ValueError(f"prefill_act must be '' or 'int8', got {c['prefill_act']!r}")
+    if c["prefill_act"] and not (c["quantize_prefill"] and c["quantize"] == "int8"):
+        raise ValueError("--prefill_act=int8 quantizes the activations of the quantized prompt passes: it needs "
+                         "--quantize=int8 --quantize_prefill=True")
     if c["quantize_prefill"] and c["num_beams"]:
         raise ValueError("--quantize_prefill is not threaded through the beam search: drop --num_beams")
     if c["kv_quantize"] not in ("", "int8"):

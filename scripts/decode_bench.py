@@ -69,6 +69,10 @@ quantized weights (``nsa_quant_gemm_*``) and which keeps no bf16 copy of the blo
 then carry ``ttft_ms`` and ``decoder_mb`` (bytes allocated by the decoder's construction: caches, shadows and
 quantized weights), and the ``_qp`` lines ``expected_drop_mb``, the bf16 size of the block linears
 (2 * 12 * n_layer * n_embd^2 bytes) that ``decoder_mb`` must fall by.  Batches above 16 need ``NSA_QUANT_MAX_ROWS=64``.
+``--prefill_act int8`` (with ``--quantize int8 --quantize_prefill``) adds ``rows_int8_qp_a8`` right after ``rows_int8_qp``:
+a ``Decoder(quantize_prefill=True, prefill_act="int8")``, whose prompt passes also quantize their activations per token
+(``nsa_quantize_act_rows`` + ``nsa_a8_gemm`` on the int8 MFMA), so one run records ``ttft_ms`` of the three prompt paths
+of the same commit; with ``--repeat 3 --calibrate`` the three are interleaved.
 """
 
 import argparse
@@ -125,6 +129,8 @@ def run_rows(model, idx, new, lengths=None, quantize=None, kv_quantize=None, sha
     sampling with --penalties.  lp: a decoder that records log-probabilities and lp alternatives."""
     B = idx.shape[0]
     qpk = dict(quantize_prefill=True) if qp else {}  # qp: the prompt passes on the quantized weights
+    if qp == "a8":  # ... and on int8 activations
+        qpk["prefill_act"] = "int8"
     torch.cuda.synchronize()
     alloc0 = torch.cuda.memory_allocated()
     if shared:  # slots for the capture step and the timed ones
@@ -365,6 +371,9 @@ def main():
     ap.add_argument("--quantize_prefill", action="store_true",
                     help="add twins of the quantized rows modes whose prompt runs on the quantized weights "
                          "(rows_int8_qp, rows_mxfp4_qp); ttft_ms and decoder_mb on the quantized rows lines")
+    ap.add_argument("--prefill_act", default="", choices=["", "int8"],
+                    help="int8, with --quantize int8 --quantize_prefill: add rows_int8_qp_a8, the quantized prompt passes "
+                         "on int8 activations too")
     ap.add_argument("--beams", default="", help="W[,W ...]: only beam search of these widths, interleaved with "
                     "shared-prompt sampling at batch W (the same linears; the select and the gather differ): "
                     "medians of --repeat runs")
@@ -407,6 +416,10 @@ def main():
         modes = [t for m in modes for t in ([m, f"{m}_short"] if m in ("graph", "rows") else [m])]
     if a.quantize_prefill:  # each twin right after its quantized rows mode
         modes = [t for m in modes for t in ([m, f"{m}_qp"] if m in ("rows_int8", "rows_mxfp4") else [m])]
+    if a.prefill_act:  # right after the weight-only quantized prompt
+        if not a.quantize_prefill:
+            ap.error("--prefill_act needs --quantize int8 --quantize_prefill")
+        modes = [t for m in modes for t in ([m, f"{m}_a8"] if m == "rows_int8_qp" else [m])]
     if a.shared_prefix:
         modes = ["prefix_rows", "prefix_shared"]
     block_size = GPTConfig().block_size
@@ -488,8 +501,9 @@ def main():
                     elif base in ("rows", "ragged"):
                         n = a.new
                         lens = ragged_lengths(B, a.prompt) if base == "ragged" else None
-                        run_rows(model, idx, 4, lens, qz, kvq, "shared" in sfx, "pen" in sfx, lp, "qp" in sfx)
-                        dt, t1 = run_rows(model, idx, n, lens, qz, kvq, "shared" in sfx, "pen" in sfx, lp, "qp" in sfx)
+                        qp = "a8" if "a8" in sfx else "qp" in sfx
+                        run_rows(model, idx, 4, lens, qz, kvq, "shared" in sfx, "pen" in sfx, lp, qp)
+                        dt, t1 = run_rows(model, idx, n, lens, qz, kvq, "shared" in sfx, "pen" in sfx, lp, qp)
                         if a.shared_prompt or (a.quantize_prefill and qz):
                             ttft = {"ttft_ms": round(t1 * 1e3, 3)}
                         if a.quantize_prefill and qz:
