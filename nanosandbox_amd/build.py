@@ -60,11 +60,12 @@ def _run(cmd):
 # library built with file_flags={}).
 FILE_FLAGS = {"a8_gemm.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
               "flash_attn.hip": ["-fno-slp-vectorize"], "flash_attn_f16.hip": ["-fno-slp-vectorize"],
-              # no packed fp32 arithmetic at all in the beam kernels, the wide (bf16 and quantized) and tall decode
-              # GEMMs, the MXFP4 kernels and the quantized-weight GEMMs
+              # no packed fp32 arithmetic at all in the beam kernels, the wide and tall decode GEMMs (bf16 and
+              # quantized), the MXFP4 kernels and the quantized-weight GEMMs
               "decode_beam.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
               "decode_mx4.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
               "decode_tall.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+              "decode_tall_q.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
               "decode_wide.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
               "decode_wide_q.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
               "quant_gemm.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}

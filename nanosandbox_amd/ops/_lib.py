@@ -157,6 +157,17 @@ _SIGNATURES = {
                           c_void_p, c_int64, c_void_p],
     "nsa_wide_gemm_mx4_ws_bytes": [c_int, c_int, c_int, c_int],
     "nsa_wide_gemm_mx4_ksplit": [c_int, c_int, c_int],
+    # 65 .. 128 rows on quantized weights (csrc/kernels/decode_tall_q.hip): the same arguments
+    "nsa_tall_gemm_q8": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                         c_void_p, c_int64, c_void_p],
+    "nsa_tall_gemm_q8_ws_bytes": [c_int, c_int, c_int, c_int],
+    "nsa_tall_gemm_q8_ksplit": [c_int, c_int, c_int],
+    "nsa_tall_gemm_q8_chunk": [],
+    "nsa_tall_gemm_mx4": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                          c_void_p, c_int64, c_void_p],
+    "nsa_tall_gemm_mx4_ws_bytes": [c_int, c_int, c_int, c_int],
+    "nsa_tall_gemm_mx4_ksplit": [c_int, c_int, c_int],
+    "nsa_tall_gemm_mx4_chunk": [],
     # any number of rows on quantized weights (csrc/kernels/quant_gemm.hip): x, Wq, scale, bias, y, M, N, K, act
     "nsa_quant_gemm_q8": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p],
     "nsa_quant_gemm_mx4": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p],
@@ -247,7 +258,8 @@ _SIGNATURES = {
 # entry points whose return value is not a hipError_t
 _RESTYPES = {"nsa_keysort_ws_bytes": c_int64, "nsa_ln_nt_min_bytes": c_int64, "nsa_wide_gemm_ws_bytes": c_int64,
              "nsa_tall_gemm_ws_bytes": c_int64, "nsa_wide_gemm_q8_ws_bytes": c_int64,
-             "nsa_wide_gemm_mx4_ws_bytes": c_int64}
+             "nsa_wide_gemm_mx4_ws_bytes": c_int64, "nsa_tall_gemm_q8_ws_bytes": c_int64,
+             "nsa_tall_gemm_mx4_ws_bytes": c_int64}
 
 
 class KernelLibraryMissing(RuntimeError):

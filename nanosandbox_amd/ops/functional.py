@@ -1687,11 +1687,27 @@ TALL_TILE_N = 128                  # TALL_TILE_N: output columns of its workgrou
 # existed; 64 turns them on for every row count the wide kernel serves.
 QUANT_MAX_ROWS = int(os.environ.get("NSA_QUANT_MAX_ROWS", "16"))
 WIDE_Q_CHUNK = {"q8": 256, "mx4": 512}  # the CHUNK of WqQ8 / WqMx4 (decode_wide_q.hip): k per LDS chunk of X
+# the same weights above both lower caps up to min(TALL_MAX_ROWS, QUANT_MAX_ROWS, 128) rows: the tall kernel's
+# quantized forms (nsa_tall_gemm_q8 / _mx4, csrc/kernels/decode_tall_q.hip: 128-column workgroups owning all rows
+# on 32x32 MFMAs, the same K contracts, any N).  Opt-in as well: NSA_QUANT_MAX_ROWS=128 turns them on for the whole
+# range; at 16 and at 64 the branch is never taken.
+_TALL_Q_LIMIT = 128                     # TQ_MAX_ROWS (decode_tall_q.hip): the rows those entries accept
+TALL_Q_CHUNK = {"q8": 256, "mx4": 128}  # the CHUNK of TqQ8 / TqMx4: k per LDS chunk of X
+
+
+def quant_max_rows():
+    """The most rows a ``QuantWeight`` / ``MxWeight`` streams through a quantized kernel in ``decode_linear`` (its
+    K contract met): the skinny cap, the wide forms' range or the tall forms', whichever reaches furthest under
+    ``NSA_QUANT_MAX_ROWS``.  The ranges are adjacent, so every row count up to it has a kernel; the quantized
+    ``Decoder`` refuses more."""
+    tall = min(TALL_MAX_ROWS, QUANT_MAX_ROWS, _TALL_Q_LIMIT)
+    below = max(SKINNY_MAX_ROWS, WIDE_MAX_ROWS)
+    return max(SKINNY_MAX_ROWS, min(WIDE_MAX_ROWS, QUANT_MAX_ROWS), tall if tall > below else 0)
 
 
 def _wide_workspace(entry, device, rows, N, K):
-    """(pointer, bytes) of the device's split-K workspace of ``entry`` (``nsa_wide_gemm``, its ``_q8`` / ``_mx4``
-    forms or ``nsa_tall_gemm``),
+    """(pointer, bytes) of the device's split-K workspace of ``entry`` (``nsa_wide_gemm``, ``nsa_tall_gemm`` or a
+    ``_q8`` / ``_mx4`` form of either),
     large enough for this shape under the rule's split; (None, 0) where the launch needs none.  One buffer
     per device and entry (the two kernels lay their counters out differently, so neither's partials may
     land in the other's buffer), zero when allocated (every launch leaves its counters zero), shared by
@@ -1735,7 +1751,9 @@ def decode_linear(x, w, b=None, gelu: bool = False, out_f32: bool = False):
     ``nsa_gemv_mx4``, 2 .. 16 rows on ``nsa_skinny_gemm_mx4``), with the same fallback.  With
     ``NSA_QUANT_MAX_ROWS`` raised above 16 (opt-in; 64 for the whole range) either quantized weight at 17 ..
     min(``NSA_WIDE_MAX_ROWS``, ``NSA_QUANT_MAX_ROWS``) rows runs on ``nsa_wide_gemm_q8`` / ``nsa_wide_gemm_mx4``
-    (the wide kernel's workgroup and split-K; K % 64 / K % 32 == 0, any N) instead of the fallback."""
+    (the wide kernel's workgroup and split-K; K % 64 / K % 32 == 0, any N) instead of the fallback, and with it at
+    128 the rows above both lower caps up to min(``NSA_TALL_MAX_ROWS``, ``NSA_QUANT_MAX_ROWS``, 128) run on
+    ``nsa_tall_gemm_q8`` / ``nsa_tall_gemm_mx4`` (the tall kernel's workgroup and split-K, the same K and N)."""
     form = _weight_form(w)
     q8 = form != "bf16"  # a quantized stream: any N, the wide kernel by QUANT_MAX_ROWS only, the dequantize fallback
     N = w.shape[0]
@@ -1766,6 +1784,11 @@ def decode_linear(x, w, b=None, gelu: bool = False, out_f32: bool = False):
             and K % _SKINNY_K["bf16"] == 0 and not (gelu and out_f32)):
         kind = "tall_gemm"
         extra = (0, *_wide_workspace("nsa_tall_gemm", x.device, rows, N, K))
+    elif (x.is_cuda and x.dtype == BF16 and q8
+            and max(SKINNY_MAX_ROWS, WIDE_MAX_ROWS) < rows <= min(TALL_MAX_ROWS, QUANT_MAX_ROWS, _TALL_Q_LIMIT)
+            and K % _SKINNY_K[form] == 0 and not (gelu and out_f32)):
+        kind = "tall_gemm"
+        extra = (0, *_wide_workspace("nsa_tall_gemm" + _stream_weight(w)[0], x.device, rows, N, K))
     if kind:
         x2 = x.reshape(rows, K).contiguous()
         y = _stream_call(kind, (_lib.ptr(x2),), w, b, (rows, N), x.device, (rows, N, K), gelu, out_f32, *extra)

@@ -347,10 +347,9 @@ class Decoder:
                                  f"rows on the GPU ({ops.functional.SKINNY_MAX_ROWS} step rows), got batch size "
                                  f"{batch_size}")
         if quantize:
-            # the int8 / MXFP4 kernels are the single-row and skinny ones, and the wide one's up to
+            # the int8 / MXFP4 kernels are the single-row and skinny ones, and the wide and tall ones' up to
             # NSA_QUANT_MAX_ROWS (opt-in: 16 by default); no silent bf16 step above them
-            fn = ops.functional
-            cap = max(fn.SKINNY_MAX_ROWS, min(fn.WIDE_MAX_ROWS, fn.QUANT_MAX_ROWS))
+            cap = ops.functional.quant_max_rows()
             if on_gpu and batch_size > cap:
                 raise ValueError(f"quantize={quantize!r} decodes at most {cap} rows on the GPU (the skinny {quantize} "
                                  f"kernels, and the wide ones up to NSA_QUANT_MAX_ROWS), got batch size {batch_size}")

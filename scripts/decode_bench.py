@@ -68,7 +68,8 @@ instead of ``nsa_wide_gemm``: the path before the wide kernel, launch for launch
 quantized weights (``nsa_quant_gemm_*``) and which keeps no bf16 copy of the block linears.  The quantized rows lines
 then carry ``ttft_ms`` and ``decoder_mb`` (bytes allocated by the decoder's construction: caches, shadows and
 quantized weights), and the ``_qp`` lines ``expected_drop_mb``, the bf16 size of the block linears
-(2 * 12 * n_layer * n_embd^2 bytes) that ``decoder_mb`` must fall by.  Batches above 16 need ``NSA_QUANT_MAX_ROWS=64``.
+(2 * 12 * n_layer * n_embd^2 bytes) that ``decoder_mb`` must fall by.  Batches above 16 need ``NSA_QUANT_MAX_ROWS=64``, above 64
+``NSA_QUANT_MAX_ROWS=128``.
 ``--prefill_act int8`` (with ``--quantize int8 --quantize_prefill``) adds ``rows_int8_qp_a8`` right after ``rows_int8_qp``:
 a ``Decoder(quantize_prefill=True, prefill_act="int8")``, whose prompt passes also quantize their activations per token
 (``nsa_quantize_act_rows`` + ``nsa_a8_gemm`` on the int8 MFMA), so one run records ``ttft_ms`` of the three prompt paths
